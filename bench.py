@@ -24,9 +24,16 @@ run, `--tol`) does it after every solve, overlapped with the next one.  Rank 0 p
 Before the W warm-up steps the GPU clocks are ramped with 150 ms of untimed solves (set-up, like building the
 solver); the timed region is exactly K steps, bracketed by barrier + synchronize, max over ranks.
 
-On one GPU the same line also carries `configs`: five timed steps each of BASELINE configs[2] (quadrotor 65 536),
-configs[3] (rocket + cones 32 768) and one rank's shard of configs[4] (quadrotor 131 072, tolerance-terminated),
-each with its kernel time and roofline (`--no-extras` skips them), and `cpu_baseline`.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs (`--dump-outputs DIR`)
+and the result line.  With `--full`, on one GPU, the same line also carries `configs`: five timed steps each of BASELINE
+configs[2] (quadrotor 65 536), configs[3] (rocket + cones 32 768) and one rank's shard of configs[4] (quadrotor 131 072,
+tolerance-terminated), each with its kernel time and roofline (`--no-extras` skips them), `specialised`, and
+`cpu_baseline` (`--no-cpu-baseline` skips it).
+
+`--dump-outputs DIR` writes what the timed path returned after its last step (rank 0's shard) as DIR/<name>.npy in
+float64: `states` (nx, N, B), `controls` (nu, N-1, B), `iterations` (B,), `solved` (B,), `residuals` (B, 4).  The inputs
+are seeded, so two builds run with the same arguments can be compared output for output.  Beyond 64 MB in all, a fixed
+seeded sample of the instances is written instead, with their indices in `instances.npy`.
 
 `--dry --backend gloo` rehearses the launch / sharding / status-fold path on CPUs (no GPU, no solver): the CPU test
 of the N > 1 launch.
@@ -93,8 +100,13 @@ def parse(argv=None):
     ap.add_argument("--mpc-max-iter", type=int, default=10)
     ap.add_argument("--status-every-step", action="store_true",
                     help="N > 1: all-reduce the status block after every solve (always on with --tol)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `configs` block (configs 3, 4, 5-shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: also the CPU baseline, the `configs` block and the `specialised` block (a plain run "
+                         "measures the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the solution and status of the last timed step as DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the `configs` block (configs 3, 4, 5-shard)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--sharded-capi", action="store_true",
                     help="ONE process drives all --gpus devices through the in-process multi-GPU handle of the C-ABI "
@@ -183,6 +195,29 @@ def build_solver(t, name, prob, x0, refs, device, iters, tol, check, precision, 
         bs.set_u_ref(refs[1])
     bs.set_profiling(True)
     return bs
+
+
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(path, solver):
+    """`--dump-outputs DIR`: the solution and per-instance status of the solver's last solve, in float64, as the caller
+    of the timed path receives them.  Over DUMP_BYTES, a fixed seeded sample of the instances (written as instances.npy)."""
+    import numpy as np
+    sol, st = solver.get_solution(), solver.get_status()
+    # (array, axis of the instance)
+    arrays = {"states": (sol["states"], 2), "controls": (sol["controls"], 2), "iterations": (st["iter"], 0),
+              "solved": (st["solved"], 0), "residuals": (st["residuals"], 0)}
+    batch = solver.batch
+    per_instance = 8 * sum(a.size // batch for a, _ in arrays.values())
+    if per_instance * batch > DUMP_BYTES:
+        n = (DUMP_BYTES - 4096) // (per_instance + 8)          # (room for the index array and the .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(batch, size=n, replace=False))
+        arrays = {k: (np.take(a, keep, axis=ax), ax) for k, (a, ax) in arrays.items()}
+        arrays["instances"] = (keep, 0)
+    os.makedirs(path, exist_ok=True)
+    for k, (a, _) in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -569,6 +604,8 @@ def run_sharded_capi(args):
     if tol <= 0.0:
         assert int(st["iter"].min()) == args.iters == int(st["iter"].max()), "work skipped"
     res, unsolved = sh.global_status()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sh)
     it_mean = float(np.mean(st["iter"]))
     ms = 1e3 * elapsed / args.steps
     how = (f"tol={tol:g}, check every {check}, max_iter={args.iters}" if tol > 0 else f"fixed {args.iters} ADMM iters")
@@ -620,6 +657,8 @@ def main():
         return run_sharded_capi(args)
     if args.backend == "gloo" and not args.dry:
         raise SystemExit("--backend gloo is the CPU rehearsal: use it with --dry (the solver has no CPU path)")
+    if args.dump_outputs and args.dry:
+        raise SystemExit("--dump-outputs writes the solver's outputs: a --dry run has none")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))          # before torch / HIP are even imported
 
@@ -763,6 +802,8 @@ def main():
             assert int(st["iter"].min()) == args.iters and int(st["iter"].max()) == args.iters, "work skipped"
         it_mean = float(np.mean(st["iter"]))
         iters_total = float(np.sum(st["iter"], dtype=np.float64))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, bs)
     if dist_on:
         # ADMM iterations executed per step over all ranks (tolerance-terminated runs: data-dependent)
         tsum = torch.tensor([iters_total], device=dev, dtype=torch.float64)
@@ -808,11 +849,11 @@ def main():
     if not args.dry and rank == 0 and world == 1 and not dist_on:
         if args.mode == "mpc":
             out["mpc_closed_loop"] = run_mpc_mode(args, bs, prob, x0, dev, torch)
-        if not args.no_cpu_baseline and name != "rocket_soc" and tol <= 0:
+        if args.full and not args.no_cpu_baseline and name != "rocket_soc" and tol <= 0:
             out["cpu_baseline"] = cpu_baseline(prob, x0, refs, args.iters, args.cpu_seconds)
     if bs is not None:
         bs.close()
-    if not args.dry and rank == 0 and world == 1 and not dist_on and not args.no_extras and args.config is None \
+    if args.full and not args.dry and rank == 0 and world == 1 and not dist_on and not args.no_extras and args.config is None \
             and args.scaling == "weak" and tol <= 0 and args.mode == "solve":
         # BASELINE configs[2], [3] and one rank's shard of configs[4]; a few hundred ms in total
         ex = {}

@@ -177,6 +177,37 @@ def case_adaptive(name, prob, x0s, settings, adaptive, sens=None, solves=2, note
                 dKinf_drho=_l(sens[0]), dPinf_drho=_l(sens[1]), x0=_l(x0s), batch=int(x0s.shape[1]), expect=inst)
 
 
+def case_live_batch(name, runs, settings, note=""):
+    """The compiled snapshot's batch entry (solve_batch "ref") on the inputs of tests/test_oracle.py's live check, recorded
+    so that the check runs where the snapshot cannot be built.  runs: [(label, prob, x0s)]."""
+    from oracle.cpu_oracle import solve_batch
+    out = []
+    for label, prob, x0s in runs:
+        r = solve_batch("ref", prob, x0s, **settings)
+        out.append(dict(label=label, problem=_prob_dict(prob), x0=_l(x0s), batch=int(x0s.shape[1]),
+                        expect=dict(x=_l(r["x"]), u=_l(r["u"]), iter=r["iter"].tolist(), solved=r["solved"].tolist())))
+    return dict(case=name, note=note, settings=settings, runs=out)
+
+
+def case_live_adaptive(name, prob, x0s, settings, adaptive, note=""):
+    """One adaptive-rho solve per instance on the zero-initialised snapshot ("refa") with its built-in tables (stored as
+    inputs): the live adaptive check of tests/test_oracle.py, recorded."""
+    inst, sens = [], None
+    for b in range(x0s.shape[1]):
+        s = CpuSolver("refa", prob.A, prob.B, prob.Q, prob.R, prob.rho, prob.N)
+        s.update_settings(**settings)
+        s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+        sens = sens or s.get_builtin_sensitivity()
+        s.set_sensitivity(*sens)
+        s.set_adaptive_rho(1, adaptive["rho_min"], adaptive["rho_max"], adaptive["clip"])
+        s.set_x0(x0s[:, b])
+        o = _sol(s, s.solve())
+        o["rho"] = s.get_adapted()["rho"]
+        inst.append(o)
+    return dict(case=name, note=note, problem=_prob_dict(prob), settings=settings, adaptive=adaptive,
+                dKinf_drho=_l(sens[0]), dPinf_drho=_l(sens[1]), x0=_l(x0s), batch=int(x0s.shape[1]), expect=inst)
+
+
 def main():
     only = sys.argv[1] if len(sys.argv) > 1 else ""
     build(port=False, ref=True)
@@ -260,6 +291,16 @@ def main():
     cases.append(case_adaptive("G9d_cartpole_adaptive_noclip", pc9, P.cartpole_x0(2, seed=5), fixed100,
                                dict(rho_min=0.5, rho_max=4.0, clip=False), sens=_fd_sensitivity(pc9), solves=1,
                                note="clipping off"))
+
+    # L: the live checks of tests/test_oracle.py on their own fresh seeds, recorded for hosts without the snapshot
+    cases.append(case_live_batch("L1_live_reference", [("cartpole", P.cartpole(20, u_bound=0.4), P.cartpole_x0(16, seed=77)),
+                                                       ("quadrotor", P.quadrotor(20), P.quadrotor_x0(8, seed=78))],
+                                 dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=60),
+                                 note="tests/test_oracle.py::test_live_reference_when_present"))
+    cases.append(case_live_adaptive("L2_live_reference_adaptive", P.quadrotor(30), P.quadrotor_x0(3, seed=11),
+                                    dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=60, check_termination=1),
+                                    dict(rho_min=1.0, rho_max=20.0, clip=True),
+                                    note="tests/test_oracle.py::test_adaptive_rho_live_reference"))
 
     for c in cases:
         if only and not c["case"].startswith(only):

@@ -23,5 +23,5 @@ for cfg in ${CFGS:-cartpole quadrotor rocket_soc rocket_soc_workspace_kept rocke
   fi
   echo "profiled $cfg"
 done
-cd $R && python bench.py --steps 20 --warmup 3 > gpurun_out/bench_${tag}_default.json 2> gpurun_out/bench_${tag}_default.err
-tail -c 1500 gpurun_out/bench_${tag}_default.json
+cd $R && python bench.py --full --steps 20 --warmup 3 > profiles/${tag}_bench_default.json
+tail -c 1500 profiles/${tag}_bench_default.json

@@ -104,11 +104,91 @@ def test_no_gpu_is_refused_loudly():
     assert p.returncode != 0 and not lines and "no CPU fallback" in p.stderr
 
 
-def test_bench_library_hash_matches_package():
-    """bench.py labels replayed counters with the library's source hash; it must be the package's own digest"""
+def _bench_module():
     import importlib.util
-    import tinympc_julia_amd as t
-    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    assert mod.LIB_HASH == t.source_hash()
+    return mod
+
+
+def test_bench_library_hash_matches_package():
+    """bench.py labels replayed counters with the library's source hash; it must be the package's own digest"""
+    import tinympc_julia_amd as t
+    assert _bench_module().LIB_HASH == t.source_hash()
+
+
+class _StubSolver:
+    """what dump_outputs reads of a solver: batch, get_solution(), get_status()"""
+
+    def __init__(self, nx, nu, N, batch):
+        import numpy as np
+        rng = np.random.default_rng(5)
+        self.batch = batch
+        self.sol = dict(states=rng.standard_normal((nx, N, batch)), controls=rng.standard_normal((nu, N - 1, batch)))
+        self.st = dict(iter=np.arange(batch, dtype=np.int32), solved=np.ones(batch, dtype=np.int32),
+                       residuals=rng.standard_normal((batch, 4)))
+
+    def get_solution(self):
+        return self.sol
+
+    def get_status(self):
+        return self.st
+
+
+def test_dump_outputs_whole_batch_and_seeded_sample(tmp_path):
+    """--dump-outputs: float64 arrays as the caller receives them; past 64 MB in all, the same fixed sample of instances
+    every time, within the cap"""
+    import numpy as np
+    mod = _bench_module()
+    small = _StubSolver(4, 1, 20, 1000)
+    mod.dump_outputs(str(tmp_path / "small"), small)
+    names = sorted(os.listdir(tmp_path / "small"))
+    assert names == ["controls.npy", "iterations.npy", "residuals.npy", "solved.npy", "states.npy"]
+    for n, want in (("states", small.sol["states"]), ("controls", small.sol["controls"]), ("iterations", small.st["iter"]),
+                    ("solved", small.st["solved"]), ("residuals", small.st["residuals"])):
+        a = np.load(tmp_path / "small" / f"{n}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, want)
+
+    big = _StubSolver(12, 4, 30, 40000)                      # 40 000 x 3 856 B = 154 MB: sampled
+    for d in ("big0", "big1"):
+        mod.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(tmp_path / "big0" / n) for n in os.listdir(tmp_path / "big0"))
+    assert total <= mod.DUMP_BYTES
+    keep = np.load(tmp_path / "big0" / "instances.npy").astype(np.int64)
+    assert len(keep) > 10000 and np.all(np.diff(keep) > 0)
+    assert np.array_equal(np.load(tmp_path / "big0" / "states.npy"), big.sol["states"][:, :, keep])
+    assert np.array_equal(np.load(tmp_path / "big0" / "residuals.npy"), big.st["residuals"][keep])
+    for n in os.listdir(tmp_path / "big0"):
+        assert np.array_equal(np.load(tmp_path / "big0" / n), np.load(tmp_path / "big1" / n))
+
+
+def test_dump_outputs_refused_on_a_dry_run(tmp_path):
+    p, lines = _run("--dry", "--backend", "gloo", "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode != 0 and not lines and "--dump-outputs" in p.stderr
+    assert not os.path.exists(tmp_path / "out")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """a plain run times the headline only (the CPU baseline, `configs` and `specialised` come with --full); --steps sets the
+    timed steps; --dump-outputs writes what the last step returned, the same on a second run with the same arguments"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        p, lines = _run("--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d))
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["metric"] == "qp_solves_per_sec" and r["steps"] == 7 and r["ms_per_step"] > 0 and r["solve_status"] == 1
+        assert abs(r["value"] - 65536 / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+        assert not {"cpu_baseline", "configs", "specialised"} & set(r)
+        dumps.append({n[:-4]: np.load(d / n) for n in os.listdir(d)})
+    out = dumps[0]
+    assert sorted(out) == ["controls", "iterations", "residuals", "solved", "states"]
+    assert out["states"].shape == (4, 20, 65536) and out["controls"].shape == (1, 19, 65536)
+    assert np.all(out["iterations"] == 100) and out["residuals"].shape == (65536, 4)
+    assert np.all(np.abs(out["controls"]) <= 0.5 + 1e-6) and np.isfinite(out["states"]).all()
+    for n in out:
+        assert np.allclose(out[n], dumps[1][n], rtol=1e-6, atol=1e-9)

@@ -141,20 +141,23 @@ def test_orc32_model_within_fp32_budget(oracle_built, name):
 
 
 def test_live_reference_when_present(oracle_built):
-    """Dev container only: the compiled reference snapshot (oracle/_ref) re-run against the restatement
-    on fresh random inputs — guards the fixtures against staleness.  Skipped on the GPU box / CI where
-    /root/reference (and so the prebuilt .so) may be absent."""
-    if not oracle_built.have_ref():
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    rng = np.random.default_rng(123)
-    for prob, x0 in ((t.problems.cartpole(20, u_bound=0.4), t.problems.cartpole_x0(16, seed=77)),
-                     (t.problems.quadrotor(20), t.problems.quadrotor_x0(8, seed=78))):
-        kw = dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=60)
-        a = oracle_built.solve_batch("ref", prob, x0, **kw)
+    """The compiled reference snapshot (oracle/_ref) against the restatement on inputs no other fixture uses: re-run live
+    where the snapshot is built (guards the fixtures against staleness), else its outputs on these inputs as recorded
+    in tests/golden/L1_live_reference.json."""
+    g = load_golden("L1_live_reference")
+    kw = g["settings"]
+    for run, (prob, x0) in zip(g["runs"], ((t.problems.cartpole(20, u_bound=0.4), t.problems.cartpole_x0(16, seed=77)),
+                                           (t.problems.quadrotor(20), t.problems.quadrotor_x0(8, seed=78)))):
+        assert np.array_equal(cm(run["x0"], prob.nx, run["batch"]), x0)
+        if oracle_built.have_ref():
+            a = oracle_built.solve_batch("ref", prob, x0, **kw)
+        else:
+            e = run["expect"]
+            a = dict(x=np.reshape(e["x"], (prob.nx, prob.N, -1), order="F"), u=np.reshape(e["u"], (prob.nu, prob.N - 1, -1), order="F"),
+                     iter=np.asarray(e["iter"]), solved=np.asarray(e["solved"]))
         b = oracle_built.solve_batch("orc64", prob, x0, **kw)
         assert np.array_equal(a["iter"], b["iter"]) and np.array_equal(a["solved"], b["solved"])
         assert np.abs(a["x"] - b["x"]).max() <= 1e-11 and np.abs(a["u"] - b["u"]).max() <= 1e-11
-    del rng
 
 
 ADAPTIVE = [n for n in golden_names() if n.startswith("G9")]
@@ -197,17 +200,22 @@ def test_orc64_adaptive_rho(oracle_built, name):
 
 
 def test_adaptive_rho_live_reference(oracle_built):
-    """dev container only: the zero-initialised build of the snapshot re-run against the restatement on a fresh seed."""
+    """The zero-initialised build of the snapshot against the restatement on a fresh seed: re-run live where it is built,
+    else its outputs as recorded in tests/golden/L2_live_reference_adaptive.json (with the built-in tables it hands over)."""
     import os
-    if not os.path.isfile(oracle_built.REF_ADAPT_LIB):
-        pytest.skip("compiled reference not present")
+    live = os.path.isfile(oracle_built.REF_ADAPT_LIB)
+    g = load_golden("L2_live_reference_adaptive")
     prob = t.problems.quadrotor(30)
     x0 = t.problems.quadrotor_x0(3, seed=11)
-    st = dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=60, check_termination=1)
+    assert np.array_equal(cm(g["x0"], prob.nx, 3), x0)
+    st = g["settings"]
     for b in range(3):
         out = []
-        sens = None
-        for kind in ("refa", "orc64"):
+        sens = None if live else (cm(g["dKinf_drho"], prob.nu, prob.nx), cm(g["dPinf_drho"], prob.nx, prob.nx))
+        if not live:
+            e = g["expect"][b]
+            out.append(dict(iter=e["iter"], rho=e["rho"], x=cm(e["x"], prob.nx, prob.N), u=cm(e["u"], prob.nu, prob.N - 1)))
+        for kind in ("refa", "orc64") if live else ("orc64",):
             s = oracle_built.CpuSolver(kind, prob.A, prob.B, prob.Q, prob.R, prob.rho, prob.N)
             s.update_settings(**st)
             s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
