@@ -5,7 +5,7 @@ next to round 3's census of quad<4,1,20,g1>.  Output: profiles/<tag>_cartpole_is
 import collections, json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
-asm = "/tmp/lean20_census.s"
+asm = os.path.join(os.environ.get("TMPDIR", "/tmp"), "lean20_census.s")
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-honor-nans", "-fno-slp-vectorize", "--cuda-device-only",
                 "-I" + os.path.join(ROOT, "tinympc-julia_amd/csrc"), "-S", os.path.join(ROOT, "tinympc-julia_amd/csrc/linst_4_1_20.hip"), "-o", asm], check=True,
                stderr=subprocess.DEVNULL)
@@ -52,6 +52,9 @@ out = {"kernel": "lean<4,1,20> = admm_lean_kernel<4,1,20, LIVE=false, UBK=true, 
        "necessary_share_of_valu": counts["fp64 FMA / mul / add (the recurrences)"] / valu,
        "floor_ms_100_iterations_at_4_cycles_2.4GHz": 4 * valu * 100 / 2.4e9 * 1e3,
        "round3_quad_g1": {"valu_instructions": 1506, "fp64": 911, "conversions": 228, "agpr_moves": 268, "kernel_ms": 0.3537},
+       "round4_lean_dense": {"instructions": 1029, "valu_instructions": 1025, "fp64": 911},
+       "coordinates": "controller-Hessenberg (x = T x^, T orthogonal; HB = !LIVE && !XB && ONE): banded M^ = T'MT, trapezoidal b^ = T'B" if tag >= "r05" else "plain",
+       "scratch_instructions_in_kernel": sum(1 for l in body if re.match(r"\s+scratch_", l)),
        "measured": "profiles/r04_lean_timeline.txt: 4.09 core cycles per loop instruction in-kernel (s_memtime), 2.08 GHz with every CU busy (2.35 GHz at 80 CUs)"}
 json.dump(out, open(os.path.join(ROOT, "profiles", f"{tag}_cartpole_isa_census.json"), "w"), indent=1)
 print(json.dumps(out, indent=1))

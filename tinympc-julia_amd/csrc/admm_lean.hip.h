@@ -53,7 +53,7 @@ namespace tmpc {
 template <int NX, int NU>
 struct LeanPack {
     static constexpr LeanLayout LL = lean_layout(NX, NU);
-    static constexpr int O_M = LL.oM, O_K = LL.oK, O_B = LL.oB, O_C = LL.oC, O_P = LL.oP, LEN = LL.len;
+    static constexpr int O_M = LL.oM, O_K = LL.oK, O_B = LL.oB, O_C = LL.oC, O_H = LL.oH, O_P = LL.oP, O_T = LL.oT, LEN = LL.len;
     static constexpr int NLOADS = LL.padded / 8;     // s_load_dwordx16 per 8 doubles
 };
 
@@ -83,6 +83,17 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #endif
     using L = LeanPack<NX, NU>;
     constexpr int EX = NX * N, EU = NU * (N - 1);
+    // Fixed-iteration solves without an active state bound iterate in controller-Hessenberg coordinates x = T x^ (T
+    // orthogonal, admm_params.h: LeanLayout): M^ = T' M T has lower bandwidth NU and b^ = T' B is upper trapezoidal, so the
+    // sweeps skip M^[m][j] (j < m - NU) and b^[m][a] (m > a) at compile time — cartpole: 37 fp64 FMAs per knot for 49.  The
+    // recursion keeps its form (p^ = x^ + M^' p^ - k^' r~ needs T' T = I); u, z, y, d, r~ are input-space and unchanged.  The
+    // state is mapped back (x = T x^) only where it leaves the sweeps: the residual iteration and the store.  LIVE would pay
+    // that at every check, XB needs x at every knot: both keep the plain coordinates.  So does the 256-register form: it
+    // sits at 246 registers and the reordered residual iteration spills 30-50 of them there (and its launches are bound by
+    // two wavefronts sharing a SIMD's issue, not by one wavefront's instruction count alone).
+    constexpr bool HB = !LIVE && !XB && ONE;
+    auto mh_zero = [](int m, int j) { return HB && j < m - NU; };               // M^[m][j] outside the band
+    auto bh_zero = [](int m, int a) { return HB && m > a; };                    // b^[m][a] below the trapezoid
     constexpr int BW = 2 * NX + 2 * NU;              // the quad kernel's bounds pack, one lane per instance: [N][xmin xmax umin umax]
     static_assert(L::NLOADS <= 4, "coefficient block too large for SGPRs");
 
@@ -102,22 +113,51 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         // -(Xref .* Q~) / (-rho), -(Uref .* R~) / (-rho), (Xref_{N-1}' Pinf)' / rho  (admm.cpp:77-82 on the scaled recursion)
         const float *qd = P.bounds + N * BW, *rd = qd + NX;                      // diag(Q) + rho, diag(R) + rho behind the bounds
         const double irho = 1.0 / P.rho_family;
-        for (int i = tid; i < NX * N; i += 256) s_cq[i] = (double)P.xref[i] * (double)qd[i % NX] * irho;
         for (int i = tid; i < NU * (N - 1); i += 256) s_cr[i] = (double)P.uref[i] * (double)rd[i % NU] * irho;
-        if (tid < NX) {
-            double acc = 0.0;
-            for (int j = 0; j < NX; ++j) acc = fma(P.lean[L::O_P + j * NX + tid], (double)P.xref[(N - 1) * NX + j], acc);
-            s_cpt[tid] = acc * irho;
+        if constexpr (HB) {   // the state terms in the sweeps' coordinates: T' (Q~ xref_k / rho), T' (Pinf' xref_{N-1} / rho)
+            const double *T = P.lean + L::O_T;
+            for (int k = tid; k < N; k += 256) {
+                double c[NX];
+                for (int j = 0; j < NX; ++j) c[j] = (double)P.xref[k * NX + j] * (double)qd[j] * irho;
+                for (int m = 0; m < NX; ++m) {
+                    double acc = 0.0;
+                    for (int j = 0; j < NX; ++j) acc = fma(T[j * NX + m], c[j], acc);
+                    s_cq[k * NX + m] = acc;
+                }
+            }
+            if (tid == 0) {
+                double c[NX];
+                for (int i = 0; i < NX; ++i) {
+                    double acc = 0.0;
+                    for (int j = 0; j < NX; ++j) acc = fma(P.lean[L::O_P + j * NX + i], (double)P.xref[(N - 1) * NX + j], acc);
+                    c[i] = acc * irho;
+                }
+                for (int m = 0; m < NX; ++m) {
+                    double acc = 0.0;
+                    for (int j = 0; j < NX; ++j) acc = fma(T[j * NX + m], c[j], acc);
+                    s_cpt[m] = acc;
+                }
+            }
+        } else {
+            for (int i = tid; i < NX * N; i += 256) s_cq[i] = (double)P.xref[i] * (double)qd[i % NX] * irho;
+            if (tid < NX) {
+                double acc = 0.0;
+                for (int j = 0; j < NX; ++j) acc = fma(P.lean[L::O_P + j * NX + tid], (double)P.xref[(N - 1) * NX + j], acc);
+                s_cpt[tid] = acc * irho;
+            }
         }
     }
-    if constexpr (!UBK || XB || REFS == REF_SHARED) __syncthreads();
+    __shared__ double s_T[HB ? NX * NX : 1];                                    // HB: T, for the residual iteration and the store
+    if constexpr (HB)
+        if (tid < NX * NX) s_T[tid] = P.lean[L::O_T + tid];
+    if constexpr (!UBK || XB || REFS == REF_SHARED || HB) __syncthreads();
     const long b = (long)blockIdx.x * 256 + tid;     // (no index list: the solver sends compacted / chunked solves to the quad kernel)
     const bool active = b < P.batch;
     const int lane = tid & 63;
     // staging of a wavefront's solution for the final store (below): [64 instances][16 + 1 floats], or [64][nu (N-1)]
     __shared__ float s_stage[4][wave_stage_floats(EU)];
 
-    const SBlock<double, L::NLOADS> blk(P.lean);
+    const SBlock<double, L::NLOADS> blk(P.lean + (HB ? L::O_H : 0));
     const auto cM = blk.at(L::O_M), cK = blk.at(L::O_K), cB = blk.at(L::O_B), cC = blk.at(L::O_C);
 
     ST lo[NU], hi[NU];
@@ -133,6 +173,18 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     DT D[N - 1][NU];
 #pragma unroll
     for (int m = 0; m < NX; ++m) X[0][m] = active ? (double)P.x0[b * NX + m] : 0.0;
+    if constexpr (HB) {                                                         // x^_0 = T' x0
+        double x0[NX];
+#pragma unroll
+        for (int m = 0; m < NX; ++m) x0[m] = X[0][m];
+#pragma unroll
+        for (int m = 0; m < NX; ++m) {
+            double acc = P.lean[L::O_T + m] * x0[0];
+#pragma unroll
+            for (int j = 1; j < NX; ++j) acc = fma(P.lean[L::O_T + j * NX + m], x0[j], acc);
+            X[0][m] = acc;
+        }
+    }
 #pragma unroll
     for (int k = 1; k < (XB ? 1 : N); ++k)
 #pragma unroll
@@ -176,6 +228,21 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         }
     };
 
+    // HB: element m of x = T x^, in fp64.  T comes from LDS (s_T) through an opaque pointer at each use (a knot of the
+    // residual iteration, the store): left alone the compiler keeps its 16 values live across the whole solve
+    auto load_T = [&](double (&Tm)[NX * NX]) {
+        const double *tp = s_T;
+        asm volatile("" : "+v"(tp));
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) Tm[i] = tp[i];
+    };
+    auto to_x = [](const double (&Tm)[NX * NX], const double (&xh)[NX], int m) {
+        double acc = Tm[m * NX] * xh[0];
+#pragma unroll
+        for (int j = 1; j < NX; ++j) acc = fma(Tm[m * NX + j], xh[j], acc);
+        return acc;
+    };
+
     // ================= fused forward sweep: forward_pass (admm.cpp:25-35) + update_slack (:43-59) + update_dual (:65-69)
     // (+ RES: the residual maxima of termination_condition, :93-96) =================
     auto forward = [&](auto res_tag, bool first_iter) {
@@ -185,9 +252,22 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             if constexpr (!XB)
                 if (first_iter) {   // cold start: the previous state slack is the zero workspace at knot 0 too, where vnew is x0 (admm.cpp:94)
 #pragma unroll
-                    for (int m = 0; m < NX; ++m) dua_x = fmax(dua_x, fabs(X[0][m]));
+                    for (int m = 0; m < NX; ++m) {
+                        if constexpr (HB) {
+                            double Tm[NX * NX];
+                            load_T(Tm);
+                            dua_x = fmax(dua_x, fabs(to_x(Tm, X[0], m)));
+                        } else {
+                            dua_x = fmax(dua_x, fabs(X[0][m]));
+                        }
+                    }
                 }
         }
+        // HB: x^_0 is loop-invariant, and so are the products of its band rows that no b^ term starts: hoisted out of the
+        // iteration loop they would stay live across it (18 registers for cartpole)
+        if constexpr (HB)
+#pragma unroll
+            for (int m = 0; m < NX; ++m) asm volatile("" : "+v"(X[0][m]));
         double xr[NX];                                                          // XB: the running x_k
 #pragma unroll
         for (int m = 0; m < NX; ++m) xr[m] = X[0][m];
@@ -200,18 +280,26 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             double dk[NU], u[NU], xn[NX];
 #pragma unroll
             for (int a = 0; a < NU; ++a) dk[a] = (double)D[k][a];
-            // x+ = (A - B Kinf) x - B d: NX independent chains, none waits for u
+            // x+ = (A - B Kinf) x - B d: NX independent chains, none waits for u (HB: the chains start at their band)
+            bool started[NX];
 #pragma unroll
             for (int m = 0; m < NX; ++m) {
-                double acc = -(cB[m * NU] * dk[0]);
+                started[m] = false;
 #pragma unroll
-                for (int a = 1; a < NU; ++a) acc = fma(-cB[m * NU + a], dk[a], acc);
-                xn[m] = acc;
+                for (int a = 0; a < NU; ++a) {
+                    if (bh_zero(m, a)) continue;
+                    xn[m] = started[m] ? fma(-cB[m * NU + a], dk[a], xn[m]) : -(cB[m * NU + a] * dk[a]);
+                    started[m] = true;
+                }
             }
 #pragma unroll
             for (int j = 0; j < NX; ++j)
 #pragma unroll
-                for (int m = 0; m < NX; ++m) xn[m] = fma(cM[m * NX + j], xk[j], xn[m]);
+                for (int m = 0; m < NX; ++m) {
+                    if (mh_zero(m, j)) continue;
+                    xn[m] = started[m] ? fma(cM[m * NX + j], xk[j], xn[m]) : cM[m * NX + j] * xk[j];
+                    started[m] = true;
+                }
             // u = -Kinf x - d
 #pragma unroll
             for (int a = 0; a < NU; ++a) {
@@ -248,9 +336,17 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 if constexpr (XB) {
                     xr[m] = xn[m];
                 } else {
-                    if constexpr (RES) dua_x = fmax(dua_x, fabs(X[k + 1][m] - xn[m]));   // v - vnew with v = the previous x  (:94)
-                    X[k + 1][m] = xn[m];
+                    if constexpr (RES && !HB) dua_x = fmax(dua_x, fabs(X[k + 1][m] - xn[m]));   // v - vnew with v = the previous x  (:94)
+                    if constexpr (!(RES && HB)) X[k + 1][m] = xn[m];
                 }
+            }
+            if constexpr (RES && HB) {                                          // ... in the original coordinates: T (x^_prev - x^_new)
+                double dl[NX], Tm[NX * NX];
+                load_T(Tm);                                                     // (per knot: live for these 16 FMAs only)
+#pragma unroll
+                for (int m = 0; m < NX; ++m) dl[m] = X[k + 1][m] - xn[m], X[k + 1][m] = xn[m];
+#pragma unroll
+                for (int m = 0; m < NX; ++m) dua_x = fmax(dua_x, fabs(to_x(Tm, dl, m)));
             }
             // (the residual maxima are only read under `!conv`: left alone, the compiler sinks the whole chain into that
             // branch, behind the sweep, and keeps every knot's u, znew and previous x alive for it — 190 spilled registers)
@@ -287,7 +383,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #pragma unroll
             for (int j = 0; j < NX; ++j)
 #pragma unroll
-                for (int a = 0; a < NU; ++a) t[a] = fma(cB[j * NU + a], p[j], t[a]);   // B' p~_{k+1} + r~_k
+                for (int a = 0; a < NU; ++a)
+                    if (!bh_zero(j, a)) t[a] = fma(cB[j * NU + a], p[j], t[a]);         // B' p~_{k+1} + r~_k
 #pragma unroll
             for (int a = 0; a < NU; ++a) {                                      // d_k = Quu_inv (B' p_{k+1} + r_k)  (:17)
                 double acc = cC[a * NU] * t[0];
@@ -308,7 +405,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #pragma unroll
                 for (int j = 0; j < NX; ++j)
 #pragma unroll
-                    for (int m = 0; m < NX; ++m) ap[m] = fma(cM[j * NX + m], p[j], ap[m]);   // + AmBKt p~_{k+1}  (:18)
+                    for (int m = 0; m < NX; ++m)
+                        if (!mh_zero(j, m)) ap[m] = fma(cM[j * NX + m], p[j], ap[m]);   // + AmBKt p~_{k+1}  (:18)
 #pragma unroll
                 for (int m = 0; m < NX; ++m) p[m] = ap[m];
             }
@@ -321,9 +419,11 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // a time; the final store below goes through LDS
     // element (k, m) of the solution: the state slack vnew — x itself, or q~ + g brought back inside the bounds it was clamped
     // to (fp32 rounding of the sum can leave them by an ulp)
+    double Ts[HB ? NX * NX : 1];                                               // HB: T, loaded at the final store
     auto vnew_at = [&](auto kk, auto mm) -> float {
         constexpr int k = decltype(kk)::value, m = decltype(mm)::value;
         if constexpr (XB) return (float)clamp3(QT[k][m] + G[k][m], (ST)s_xb[k * 2 * NX + m], (ST)s_xb[k * 2 * NX + NX + m]);
+        else if constexpr (HB) return (float)to_x(Ts, X[k], m);
         else return (float)X[XB ? 0 : k][m];
     };
     auto store = [&](bool solved_flag) {
@@ -396,6 +496,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         const bool mine = active && !conv;
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
         if (mask) {
+            if constexpr (HB) load_T(Ts);
             const long w0 = (long)blockIdx.x * 256 + (tid & ~63);          // the wavefront's first instance
             store_wave_coalesced<EX, EU>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask,
                                          [&](auto ee) { constexpr int e = decltype(ee)::value; return vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{}); },

@@ -100,6 +100,10 @@ struct AdmmParams {
 enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4, HF_LEAN_ONE = 8 };
 
 // Coefficient pack of the lean kernel (admm_lean.hip.h), fp64, all wave-uniform; filled by build_lean_pack (kernels.hip).
+// Two coefficient blocks of the same layout: the plain one (what the tolerance-terminated and state-bounded variants read)
+// and, at oH, the same four matrices in controller-Hessenberg coordinates x = T x^ (host_setup.h: staircase_form) — T' M T
+// with lower bandwidth nu, T' B upper trapezoidal, Kinf T, and the input-space -rho Quu_inv unchanged — which the
+// fixed-iteration variants' sweeps read.
 struct LeanLayout {
     int oM;      // A - B Kinf     [nx][nx] row-major (its transpose is the AmBKt the backward sweep reads)
     int oK;      // Kinf           [nu][nx]
@@ -107,13 +111,17 @@ struct LeanLayout {
     int oC;      // -rho Quu_inv   [nu][nu]
     int len;
     int padded;  // rounded up to whole 8-double scalar loads (what the kernel keeps in SGPRs)
-    int oP;      // Pinf           [nx][nx] row-major, behind the padded block (read once, for the terminal reference term)
+    int oH;      // the transformed block (oM .. oC relative to it), padded likewise
+    int oP;      // Pinf           [nx][nx] row-major, behind the padded blocks (read once, for the terminal reference term)
+    int oT;      // T              [nx][nx] row-major, orthogonal (read at entry, at the residual iteration and at the store)
     int total;
 };
 constexpr LeanLayout lean_layout(int nx, int nu) {
     return LeanLayout{0, nx * nx, nx * nx + nu * nx, nx * nx + 2 * nu * nx, nx * nx + 2 * nu * nx + nu * nu,
                       (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8, (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8,
-                      (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8 + nx * nx};
+                      2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8),
+                      2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + nx * nx,
+                      2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + 2 * nx * nx};
 }
 
 #ifdef __HIPCC__

@@ -163,3 +163,51 @@ int compute_sensitivity(const Mat &A, const Mat &B, const Mat &Q, const Mat &R, 
 }
 
 }  // namespace tmpc
+
+namespace tmpc {
+
+void staircase_form(int nx, int nu, const double *M, const double *B, double *T, double *Mh, double *Bh) {
+    std::vector<double> W(M, M + (size_t)nx * nx), V(B, B + (size_t)nx * nu), v(nx);
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < nx; ++j) T[i * nx + j] = i == j ? 1.0 : 0.0;
+    // H = I - 2 v v' / v'v on rows r0.. zeroes rows r0 + 1.. of the column c; applied as W <- H W H, V <- H V, T <- T H
+    auto reflect = [&](int r0, auto col) {
+        double below = 0.0;
+        for (int i = r0 + 1; i < nx; ++i) below += col(i) * col(i);
+        if (below == 0.0) return;
+        const double c0 = col(r0), nrm = std::sqrt(c0 * c0 + below), alpha = c0 >= 0.0 ? -nrm : nrm;
+        for (int i = r0; i < nx; ++i) v[i] = col(i);
+        v[r0] -= alpha;
+        const double s = 2.0 / ((v[r0] * v[r0]) + below);
+        for (int j = 0; j < nx; ++j) {   // rows of W
+            double d = 0.0;
+            for (int i = r0; i < nx; ++i) d += v[i] * W[i * nx + j];
+            for (int i = r0; i < nx; ++i) W[i * nx + j] -= s * d * v[i];
+        }
+        for (int a = 0; a < nu; ++a) {   // rows of V
+            double d = 0.0;
+            for (int i = r0; i < nx; ++i) d += v[i] * V[i * nu + a];
+            for (int i = r0; i < nx; ++i) V[i * nu + a] -= s * d * v[i];
+        }
+        for (int i = 0; i < nx; ++i) {   // columns of W and T
+            double dw = 0.0, dt = 0.0;
+            for (int j = r0; j < nx; ++j) dw += W[i * nx + j] * v[j], dt += T[i * nx + j] * v[j];
+            for (int j = r0; j < nx; ++j) W[i * nx + j] -= s * dw * v[j], T[i * nx + j] -= s * dt * v[j];
+        }
+    };
+    for (int a = 0; a < nu && a < nx - 1; ++a) reflect(a, [&](int i) { return V[i * nu + a]; });           // T' B: QR
+    for (int j = 0; j + nu < nx - 1; ++j) reflect(j + nu, [&](int i) { return W[i * nx + j]; });           // band of T' M T
+    for (int m = 0; m < nx; ++m) {
+        for (int j = 0; j < nx; ++j) Mh[m * nx + j] = j < m - nu ? 0.0 : W[m * nx + j];
+        for (int a = 0; a < nu; ++a) Bh[m * nu + a] = m > a ? 0.0 : V[m * nu + a];
+    }
+}
+
+}  // namespace tmpc
+
+// (test hook, not part of the public boundary include/tinympc_hip.h: the reduction build_lean_pack applies)
+extern "C" int tmpc_lean_staircase(int nx, int nu, const double *M, const double *B, double *T, double *Mh, double *Bh) {
+    if (nx < 1 || nu < 1 || !M || !B || !T || !Mh || !Bh) return 1;
+    tmpc::staircase_form(nx, nu, M, B, T, Mh, Bh);
+    return 0;
+}

@@ -32,4 +32,10 @@ int precompute_cache(const Mat &A, const Mat &B, const Mat &Q, const Mat &R, dou
 int compute_sensitivity(const Mat &A, const Mat &B, const Mat &Q, const Mat &R, double rho, Mat &dK, Mat &dP, Mat &dC1,
                         Mat &dC2);
 
+// Controller-Hessenberg (staircase) form of the pair (M, B), nx x nx and nx x nu, row-major: an orthogonal T (row-major,
+// x = T x^) with Bh = T' B upper trapezoidal (Bh[m][a] = 0 for m > a) and Mh = T' M T of lower bandwidth nu (Mh[m][j] = 0
+// for j < m - nu), by Householder reflections (no iteration; any pair, an uncontrollable one only gains zeros).  The
+// entries outside that pattern are returned as exact zeros.
+void staircase_form(int nx, int nu, const double *M, const double *B, double *T, double *Mh, double *Bh);
+
 }  // namespace tmpc

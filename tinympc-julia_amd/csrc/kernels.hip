@@ -6,6 +6,7 @@
 #include <limits>
 
 #include "admm_generic.hip.h"
+#include "host_setup.h"
 #include "solver.h"
 
 namespace tmpc {
@@ -93,6 +94,20 @@ bool build_lean_pack(const Solver &sv, std::vector<double> &out) {
         for (int b2 = 0; b2 < nu; ++b2) out[L.oC + a * nu + b2] = -c.rho * c.Quu_inv(a, b2);
     for (int i = 0; i < nx; ++i)
         for (int j = 0; j < nx; ++j) out[L.oP + i * nx + j] = c.Pinf(i, j);
+    // the same coefficients in controller-Hessenberg coordinates x = T x^ (T orthogonal): M^ = T' M T, b^ = T' B, k^ = Kinf T;
+    // the input-space C does not change
+    std::vector<double> Mh((size_t)nx * nx), Bh((size_t)nx * nu);
+    staircase_form(nx, nu, out.data() + L.oM, out.data() + L.oB, out.data() + L.oT, Mh.data(), Bh.data());
+    const double *T = out.data() + L.oT;
+    for (int i = 0; i < nx * nx; ++i) out[L.oH + L.oM + i] = Mh[i];
+    for (int i = 0; i < nx * nu; ++i) out[L.oH + L.oB + i] = Bh[i];
+    for (int a = 0; a < nu; ++a)
+        for (int j = 0; j < nx; ++j) {
+            double s = 0.0;
+            for (int l = 0; l < nx; ++l) s += c.Kinf(a, l) * T[l * nx + j];
+            out[L.oH + L.oK + a * nx + j] = s;
+        }
+    for (int i = 0; i < nu * nu; ++i) out[L.oH + L.oC + i] = out[L.oC + i];
     return true;
 }
 
