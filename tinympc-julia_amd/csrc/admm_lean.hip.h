@@ -53,7 +53,7 @@ namespace tmpc {
 template <int NX, int NU>
 struct LeanPack {
     static constexpr LeanLayout LL = lean_layout(NX, NU);
-    static constexpr int O_M = LL.oM, O_K = LL.oK, O_B = LL.oB, O_C = LL.oC, O_H = LL.oH, O_P = LL.oP, O_T = LL.oT, LEN = LL.len;
+    static constexpr int O_M = LL.oM, O_K = LL.oK, O_B = LL.oB, O_C = LL.oC, O_H = LL.oH, O_S = LL.oS, O_P = LL.oP, O_T = LL.oT, LEN = LL.len;
     static constexpr int NLOADS = LL.padded / 8;     // s_load_dwordx16 per 8 doubles
 };
 
@@ -73,7 +73,8 @@ __device__ __forceinline__ double lean_abs(double a) { return fabs(a); }
 // ST: the type of the slack / dual state.  float: the library's precision 0 (fp64 recurrences, fp32 state).  double: the
 // reference's own arithmetic end to end (types.hpp:15) — precision 2 for one-shot solves of the shapes this kernel holds, at
 // this kernel's speed instead of the generic kernel's; only ever specialised on request (jit.cpp), in the ONE form.
-template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB = false, int REFS = REF_ZERO, class ST = float>
+// SP: the zero / unit pattern of the model's (A, B) the kernel is built for (admm_params.h: lean_pattern_covers), 0: none.
+template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB = false, int REFS = REF_ZERO, class ST = float, uint64_t SP = 0>
 __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const AdmmParams P) {
     constexpr bool F64 = std::is_same<ST, double>::value;
     static_assert(!F64 || ONE, "fp64 state: the 512-register form");
@@ -91,9 +92,18 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // that at every check, XB needs x at every knot: both keep the plain coordinates.  So does the 256-register form: it
     // sits at 246 registers and the reordered residual iteration spills 30-50 of them there (and its launches are bound by
     // two wavefronts sharing a SIMD's issue, not by one wavefront's instruction count alone).
-    constexpr bool HB = !LIVE && !XB && ONE;
+    // SP != 0 (any variant): the sweeps in the plain coordinates on the model's own sparse A and B instead of the dense
+    // A - B Kinf — u = -Kinf x - d, x+ = A x + B u; t = B' p~ + r~, d = C t, p~ = x + A' p~ - Kinf' t (the recursion above with
+    // AmBKt = A' - Kinf' B') — skipping the zeros of the pattern at compile time and never reading its units: a row of x+
+    // starts from x_j where A[m][j] is 1, a unit of A' p~ is an add.  Cartpole: 27 fp64 FMAs per knot for 37 (HB) or 49.
+    constexpr bool SPR = SP != 0;
+    static_assert(!SPR || (NX <= 4 && NU <= 4), "sparse pattern: nx, nu <= 4");
+    constexpr bool HB = !SPR && !LIVE && !XB && ONE;
     auto mh_zero = [](int m, int j) { return HB && j < m - NU; };               // M^[m][j] outside the band
     auto bh_zero = [](int m, int a) { return HB && m > a; };                    // b^[m][a] below the trapezoid
+    auto a_nz = [](int m, int j) { return !SPR || lsp_a(SP, NX, m, j); };       // SP: A[m][j] is not zero
+    auto a_one = [](int m, int j) { return SPR && lsp_one(SP, NX, m, j); };     //     A[m][j] is exactly 1
+    auto b_nz = [](int m, int a) { return !SPR || lsp_b(SP, NU, m, a); };       //     B[m][a] is not zero
     constexpr int BW = 2 * NX + 2 * NU;              // the quad kernel's bounds pack, one lane per instance: [N][xmin xmax umin umax]
     static_assert(L::NLOADS <= 4, "coefficient block too large for SGPRs");
 
@@ -157,7 +167,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // staging of a wavefront's solution for the final store (below): [64 instances][16 + 1 floats], or [64][nu (N-1)]
     __shared__ float s_stage[4][wave_stage_floats(EU)];
 
-    const SBlock<double, L::NLOADS> blk(P.lean + (HB ? L::O_H : 0));
+    const SBlock<double, L::NLOADS> blk(P.lean + (HB ? L::O_H : (SPR ? L::O_S : 0)));   // (SPR: A where M is)
     const auto cM = blk.at(L::O_M), cK = blk.at(L::O_K), cB = blk.at(L::O_B), cC = blk.at(L::O_C);
 
     ST lo[NU], hi[NU];
@@ -264,8 +274,9 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 }
         }
         // HB: x^_0 is loop-invariant, and so are the products of its band rows that no b^ term starts: hoisted out of the
-        // iteration loop they would stay live across it (18 registers for cartpole)
-        if constexpr (HB)
+        // iteration loop they would stay live across it (18 registers for cartpole; SPR: A x_0 likewise — except in the
+        // 256-register form without a state bound, which spills 33 registers with the opaque use and none without)
+        if constexpr (HB || (SPR && (ONE || XB)))
 #pragma unroll
             for (int m = 0; m < NX; ++m) asm volatile("" : "+v"(X[0][m]));
         double xr[NX];                                                          // XB: the running x_k
@@ -282,28 +293,42 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             for (int a = 0; a < NU; ++a) dk[a] = (double)D[k][a];
             // x+ = (A - B Kinf) x - B d: NX independent chains, none waits for u (HB: the chains start at their band)
             bool started[NX];
-#pragma unroll
-            for (int m = 0; m < NX; ++m) {
-                started[m] = false;
-#pragma unroll
-                for (int a = 0; a < NU; ++a) {
-                    if (bh_zero(m, a)) continue;
-                    xn[m] = started[m] ? fma(-cB[m * NU + a], dk[a], xn[m]) : -(cB[m * NU + a] * dk[a]);
-                    started[m] = true;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < NX; ++j)
+            if constexpr (!SPR) {
 #pragma unroll
                 for (int m = 0; m < NX; ++m) {
-                    if (mh_zero(m, j)) continue;
-                    xn[m] = started[m] ? fma(cM[m * NX + j], xk[j], xn[m]) : cM[m * NX + j] * xk[j];
-                    started[m] = true;
+                    started[m] = false;
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) {
+                        if (bh_zero(m, a)) continue;
+                        xn[m] = started[m] ? fma(-cB[m * NU + a], dk[a], xn[m]) : -(cB[m * NU + a] * dk[a]);
+                        started[m] = true;
+                    }
                 }
-            // u = -Kinf x - d
+#pragma unroll
+                for (int j = 0; j < NX; ++j)
+#pragma unroll
+                    for (int m = 0; m < NX; ++m) {
+                        if (mh_zero(m, j)) continue;
+                        xn[m] = started[m] ? fma(cM[m * NX + j], xk[j], xn[m]) : cM[m * NX + j] * xk[j];
+                        started[m] = true;
+                    }
+            }
+            // u = -Kinf x - d  (SPR: x_k's rows without a B term first — the others wait for the previous knot's u)
 #pragma unroll
             for (int a = 0; a < NU; ++a) {
-                if constexpr (TMPC_LEAN_SPLITK && NX >= 4) {
+                if constexpr (SPR) {
+                    double acc = -dk[a];
+#pragma unroll
+                    for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+                        for (int j = 0; j < NX; ++j) {
+                            bool late = false;
+#pragma unroll
+                            for (int c = 0; c < NU; ++c) late = late || b_nz(j, c);
+                            if (late == (pass == 1)) acc = fma(-cK[a * NX + j], xk[j], acc);
+                        }
+                    u[a] = acc;
+                } else if constexpr (TMPC_LEAN_SPLITK && NX >= 4) {
                     double u0 = -dk[a], u1 = -(cK[a * NX + NX / 2] * xk[NX / 2]);
 #pragma unroll
                     for (int j = 0; j < NX / 2; ++j) u0 = fma(-cK[a * NX + j], xk[j], u0);
@@ -315,6 +340,30 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #pragma unroll
                     for (int j = 0; j < NX; ++j) acc = fma(-cK[a * NX + j], xk[j], acc);
                     u[a] = acc;
+                }
+            }
+            if constexpr (SPR) {   // x+ = A x + B u: a row's chain starts from x_j at its first unit; the u terms last
+#pragma unroll
+                for (int m = 0; m < NX; ++m) {
+                    int s = -1;
+#pragma unroll
+                    for (int j = NX - 1; j >= 0; --j)
+                        if (a_one(m, j)) s = j;
+                    started[m] = s >= 0;
+                    xn[m] = 0.0;                                                // (a row without terms)
+                    if (s >= 0) xn[m] = xk[s];
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) {
+                        if (!a_nz(m, j) || j == s) continue;
+                        xn[m] = !started[m] ? cM[m * NX + j] * xk[j] : (a_one(m, j) ? xn[m] + xk[j] : fma(cM[m * NX + j], xk[j], xn[m]));
+                        started[m] = true;
+                    }
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) {
+                        if (!b_nz(m, a)) continue;
+                        xn[m] = started[m] ? fma(cB[m * NU + a], u[a], xn[m]) : cB[m * NU + a] * u[a];
+                        started[m] = true;
+                    }
                 }
             }
 #pragma unroll
@@ -384,7 +433,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             for (int j = 0; j < NX; ++j)
 #pragma unroll
                 for (int a = 0; a < NU; ++a)
-                    if (!bh_zero(j, a)) t[a] = fma(cB[j * NU + a], p[j], t[a]);         // B' p~_{k+1} + r~_k
+                    if (!bh_zero(j, a) && b_nz(j, a)) t[a] = fma(cB[j * NU + a], p[j], t[a]);   // B' p~_{k+1} + r~_k
 #pragma unroll
             for (int a = 0; a < NU; ++a) {                                      // d_k = Quu_inv (B' p_{k+1} + r_k)  (:17)
                 double acc = cC[a * NU] * t[0];
@@ -392,7 +441,22 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 for (int c = 1; c < NU; ++c) acc = fma(cC[a * NU + c], t[c], acc);
                 D[k][a] = (DT)acc;
             }
-            if constexpr (k > 0) {                                              // (p_0 is never read)
+            if constexpr (k > 0 && SPR) {                                       // p~_k = q~_k + A' p~_{k+1} - Kinf' t_k
+                double ap[NX];
+#pragma unroll
+                for (int m = 0; m < NX; ++m) {
+                    double acc = XB ? (double)QT[k][m] : X[XB ? 0 : k][m];
+                    if constexpr (REFS == REF_SHARED) acc += s_cq[k * NX + m];
+#pragma unroll
+                    for (int j = 0; j < NX; ++j)
+                        if (a_nz(j, m)) acc = a_one(j, m) ? acc + p[j] : fma(cM[j * NX + m], p[j], acc);
+#pragma unroll
+                    for (int a = 0; a < NU; ++a) acc = fma(-cK[a * NX + m], t[a], acc);
+                    ap[m] = acc;
+                }
+#pragma unroll
+                for (int m = 0; m < NX; ++m) p[m] = ap[m];
+            } else if constexpr (k > 0) {                                       // (p_0 is never read)
                 double ap[NX];
 #pragma unroll
                 for (int m = 0; m < NX; ++m) {                                  // q~_k - Kinf' r~_k
@@ -486,7 +550,9 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             }
             if (!__builtin_amdgcn_ballot_w64(active && !conv)) break;           // every instance of this wavefront finished
         }
-        backward();
+        // (after the last iteration its d is never read; the 256-register and state-bounded forms keep the unconditional call:
+        // an exit before it costs them 2-50 spilled registers)
+        if (!(ONE && !XB) || i < max_iter) backward();
     }
     // ---- final store of every instance that has not stored at its convergence: through LDS, so that a store instruction
     // writes whole 64-byte pieces (X: 16 consecutive floats of 4 instances) or one contiguous 256 bytes (U) instead of 64

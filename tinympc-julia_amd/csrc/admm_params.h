@@ -100,18 +100,19 @@ struct AdmmParams {
 enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4, HF_LEAN_ONE = 8 };
 
 // Coefficient pack of the lean kernel (admm_lean.hip.h), fp64, all wave-uniform; filled by build_lean_pack (kernels.hip).
-// Two coefficient blocks of the same layout: the plain one (what the tolerance-terminated and state-bounded variants read)
-// and, at oH, the same four matrices in controller-Hessenberg coordinates x = T x^ (host_setup.h: staircase_form) — T' M T
+// Three coefficient blocks of the same layout: the plain one (what the tolerance-terminated and state-bounded variants read);
+// at oH, the same four matrices in controller-Hessenberg coordinates x = T x^ (host_setup.h: staircase_form) — T' M T
 // with lower bandwidth nu, T' B upper trapezoidal, Kinf T, and the input-space -rho Quu_inv unchanged — which the
-// fixed-iteration variants' sweeps read.
+// fixed-iteration variants' sweeps read; at oS, the model's own A where M is (the sparse variants, lean_pattern below).
 struct LeanLayout {
-    int oM;      // A - B Kinf     [nx][nx] row-major (its transpose is the AmBKt the backward sweep reads)
+    int oM;      // A - B Kinf     [nx][nx] row-major (its transpose is the AmBKt the backward sweep reads); A in the oS block
     int oK;      // Kinf           [nu][nx]
     int oB;      // B              [nx][nu]
     int oC;      // -rho Quu_inv   [nu][nu]
     int len;
     int padded;  // rounded up to whole 8-double scalar loads (what the kernel keeps in SGPRs)
     int oH;      // the transformed block (oM .. oC relative to it), padded likewise
+    int oS;      // the sparse variants' block [A, Kinf, B, C] (oM .. oC relative to it), padded likewise
     int oP;      // Pinf           [nx][nx] row-major, behind the padded blocks (read once, for the terminal reference term)
     int oT;      // T              [nx][nx] row-major, orthogonal (read at entry, at the residual iteration and at the store)
     int total;
@@ -120,8 +121,61 @@ constexpr LeanLayout lean_layout(int nx, int nu) {
     return LeanLayout{0, nx * nx, nx * nx + nu * nx, nx * nx + 2 * nu * nx, nx * nx + 2 * nu * nx + nu * nu,
                       (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8, (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8,
                       2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8),
-                      2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + nx * nx,
-                      2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + 2 * nx * nx};
+                      3 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8),
+                      3 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + nx * nx,
+                      3 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + 2 * nx * nx};
+}
+
+// Zero / unit pattern of a model's (A, B), nx, nu <= 4, as a lean kernel's compile-time parameter SP: bits 0-15 the nonzeros
+// of A (bit i * nx + j: A[i][j]), bits 16-31 the entries of A that are exactly 1.0 (a subset of the nonzeros), bits 32-47
+// the nonzeros of B (bit i * nu + a), bit 48 set in every pattern.  SP == 0: no pattern, the dense sweeps.
+enum : int { LSP_UNIT = 16, LSP_B = 32, LSP_ON = 48 };
+constexpr bool lsp_a(uint64_t sp, int nx, int i, int j) { return (sp >> (i * nx + j)) & 1; }
+constexpr bool lsp_one(uint64_t sp, int nx, int i, int j) { return (sp >> (LSP_UNIT + i * nx + j)) & 1; }
+constexpr bool lsp_b(uint64_t sp, int nu, int i, int a) { return (sp >> (LSP_B + i * nu + a)) & 1; }
+// the pattern of A [nx][nx] and B [nx][nu], row-major: nonzero is != 0.0, unit is == 1.0 exactly (0: nx or nu above 4)
+constexpr uint64_t lean_pattern_rm(int nx, int nu, const double *A, const double *B) {
+    if (nx < 1 || nu < 1 || nx > 4 || nu > 4) return 0;
+    uint64_t sp = 1ull << LSP_ON;
+    for (int i = 0; i < nx; ++i) {
+        for (int j = 0; j < nx; ++j) {
+            if (A[i * nx + j] != 0.0) sp |= 1ull << (i * nx + j);
+            if (A[i * nx + j] == 1.0) sp |= 1ull << (LSP_UNIT + i * nx + j);
+        }
+        for (int a = 0; a < nu; ++a)
+            if (B[i * nu + a] != 0.0) sp |= 1ull << (LSP_B + i * nu + a);
+    }
+    return sp;
+}
+// fp64 instructions per knot of each form (both sweeps, zero references): the sparse sweeps of pattern sp — u = -Kinf x - d,
+// x+ = A x + B u with a row's chain started from x_j where A[i][j] is a unit; t = B' p~ + r~, d = C t, p~ = x + A' p~ - Kinf' t
+constexpr int lean_cost_sparse(uint64_t sp, int nx, int nu) {
+    int c = 2 * nx * nu + nu * nu;                  // u, Kinf' t, C t
+    for (int i = 0; i < nx; ++i) {
+        int terms = 0;
+        bool unit = false;
+        for (int j = 0; j < nx; ++j) terms += lsp_a(sp, nx, i, j), unit = unit || lsp_one(sp, nx, i, j);
+        for (int a = 0; a < nu; ++a) terms += 2 * lsp_b(sp, nu, i, a);   // (B u forward, B' p~ backward)
+        for (int j = 0; j < nx; ++j) terms += lsp_a(sp, nx, j, i);       // (A' p~: a unit is an add)
+        c += terms - (unit ? 1 : 0);
+    }
+    return c;
+}
+// ... controller-Hessenberg (band of T'MT, trapezoid of T'B) and plain dense (A - B Kinf, B)
+constexpr int lean_cost_hessenberg(int nx, int nu) {
+    int band = 0, trap = 0;
+    for (int m = 0; m < nx; ++m) {
+        for (int j = 0; j < nx; ++j) band += j >= m - nu;
+        for (int a = 0; a < nu; ++a) trap += m <= a;
+    }
+    return 2 * band + 2 * trap + 2 * nx * nu + nu * nu;
+}
+constexpr int lean_cost_dense(int nx, int nu) { return 2 * nx * nx + 4 * nx * nu + nu * nu; }
+// a kernel built for pattern `built` computes a model of pattern `model` exactly when the model's nonzeros lie inside the
+// built pattern's and every entry the kernel takes as 1 is 1 in the model (the kernel never reads those entries)
+constexpr bool lean_pattern_covers(uint64_t built, uint64_t model) {
+    const uint64_t nz = 0xFFFFull | (0xFFFFull << LSP_B), one = 0xFFFFull << LSP_UNIT;
+    return built != 0 && model != 0 && (model & nz & ~built) == 0 && ((built & one) & ~(model & one)) == 0;
 }
 
 #ifdef __HIPCC__

@@ -108,8 +108,47 @@ bool build_lean_pack(const Solver &sv, std::vector<double> &out) {
             out[L.oH + L.oK + a * nx + j] = s;
         }
     for (int i = 0; i < nu * nu; ++i) out[L.oH + L.oC + i] = out[L.oC + i];
+    // the sparse variants' block: the model's A where M is, Kinf, B and C as in the plain one
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < nx; ++j) out[L.oS + L.oM + i * nx + j] = sv.A(i, j);
+    for (int i = L.oK; i < L.len; ++i) out[L.oS + i] = out[i];
     return true;
 }
+
+uint64_t lean_pattern(const Mat &A, const Mat &B) {
+    const int nx = A.r, nu = B.c;
+    if (nx < 1 || nu < 1 || nx > 4 || nu > 4) return 0;
+    double a[16], b[16];
+    for (int i = 0; i < nx; ++i) {
+        for (int j = 0; j < nx; ++j) a[i * nx + j] = A(i, j);
+        for (int c = 0; c < nu; ++c) b[i * nu + c] = B(i, c);
+    }
+    return lean_pattern_rm(nx, nu, a, b);
+}
+
+}  // namespace tmpc
+
+// (test hooks, not part of the public boundary include/tinympc_hip.h: the lean kernel's sparse-form routing, Solver::launch_pass)
+// the pattern of row-major A [nx][nx], B [nx][nu]; the per-knot fp64 costs {sparse of sp, Hessenberg, dense}; the coverage
+// rule; the form a launch would take; the pattern of the built-in entry of a shape (0: none, or no sparse kernels)
+extern "C" unsigned long long tmpc_lean_pattern(int nx, int nu, const double *A, const double *B) {
+    return (A && B) ? tmpc::lean_pattern_rm(nx, nu, A, B) : 0;
+}
+extern "C" int tmpc_lean_costs(int nx, int nu, unsigned long long sp, int *out3) {
+    if (nx < 1 || nu < 1 || nx > 4 || nu > 4 || !out3) return 1;
+    out3[0] = tmpc::lean_cost_sparse(sp, nx, nu), out3[1] = tmpc::lean_cost_hessenberg(nx, nu), out3[2] = tmpc::lean_cost_dense(nx, nu);
+    return 0;
+}
+extern "C" int tmpc_lean_covers(unsigned long long built, unsigned long long model) { return tmpc::lean_pattern_covers(built, model) ? 1 : 0; }
+extern "C" int tmpc_lean_pick_form(int nx, int nu, unsigned long long built, unsigned long long model, int one, int live, int xb) {
+    return tmpc::lean_pick_form(nx, nu, built, model, one != 0, live != 0, xb != 0, true);
+}
+extern "C" unsigned long long tmpc_lean_builtin_pattern(int nx, int nu, int N) {
+    const tmpc::LeanEntry *e = tmpc::find_lean_kernel(nx, nu, N);
+    return (e && e->launch_sparse) ? e->sp : 0;
+}
+
+namespace tmpc {
 
 // Lanes per instance for a batch size.  Fewer lanes per instance means fewer cross-lane moves and no redundant
 // work, but also fewer wavefronts.  A launch with at most one wavefront per SIMD takes about the same time

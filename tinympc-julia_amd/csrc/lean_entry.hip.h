@@ -8,11 +8,11 @@ namespace tmpc {
 template <int NX, int NU, int N, bool XB, int REFS>
 hipError_t launch_lean_v(const AdmmParams &P, bool live, bool knot_bounds, hipStream_t stream) {
     const int grid = (P.batch + 255) / 256;
-    // The 512-register variant when the launch has at most one workgroup per CU (= one wavefront per SIMD), and — at any batch —
+    // (lean_one_form, solver.h)  The 512-register variant when the launch has at most one workgroup per CU (= one wavefront per SIMD), and — at any batch —
     // for tolerance-terminated solves: held to 256 registers the LIVE variants spill (73-187 registers) and lose to 512-register
     // wavefronts taking turns (batch 131 072, check live: 0.92 against 0.69 ms; with a state bound 2.95 against 1.05;
     // fixed-iteration solves: 0.47 / 0.61 against 0.46 / 0.69 — scripts/lean_time.py "big").  TINYMPC_HIP_LEAN_ONE: always (tuning aid).
-    const bool one = grid <= device_cu_count() || live || (P.host_flags & HF_LEAN_ONE);
+    const bool one = lean_one_form(P.batch, live, (P.host_flags & HF_LEAN_ONE) != 0);
 #define TMPC_LEAN_LAUNCH(LIVE_, UBK_, ONE_) \
     hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE_, UBK_, ONE_, XB, REFS>), dim3(grid), dim3(256), 0, stream, P)
 #define TMPC_LEAN_LAUNCH2(LIVE_, UBK_) \
@@ -38,29 +38,58 @@ hipError_t launch_lean(const AdmmParams &P, bool live, bool knot_bounds, bool st
                         : launch_lean_v<NX, NU, N, false, REF_ZERO>(P, live, knot_bounds, stream);
 }
 
+// The sparse kernels of one (A, B) pattern SP (admm_lean.hip.h): zero references and input bounds that do not depend on the
+// knot only, in the (LIVE, ONE, XB) combinations launch_lean_v picks — six kernels (the routing, Solver::launch_pass, sends
+// nothing else here)
+template <int NX, int NU, int N, uint64_t SP>
+hipError_t launch_lean_sparse(const AdmmParams &P, bool live, bool knot_bounds, bool state_bounds, hipStream_t stream) {
+    if (P.ref_mode != REF_ZERO || knot_bounds) return hipErrorInvalidValue;
+    const int grid = (P.batch + 255) / 256;
+    const bool one = lean_one_form(P.batch, live, (P.host_flags & HF_LEAN_ONE) != 0);
+#define TMPC_LEAN_LAUNCH(LIVE_, ONE_, XB_) \
+    hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE_, true, ONE_, XB_, REF_ZERO, float, SP>), dim3(grid), dim3(256), 0, stream, P)
+#define TMPC_LEAN_LAUNCH2(LIVE_, ONE_) \
+    do { if (state_bounds) TMPC_LEAN_LAUNCH(LIVE_, ONE_, true); else TMPC_LEAN_LAUNCH(LIVE_, ONE_, false); } while (0)
+    if (live) TMPC_LEAN_LAUNCH2(true, true);
+    else if (one) TMPC_LEAN_LAUNCH2(false, true);
+    else TMPC_LEAN_LAUNCH2(false, false);
+#undef TMPC_LEAN_LAUNCH2
+#undef TMPC_LEAN_LAUNCH
+    return hipGetLastError();
+}
+
 // ---- one variant specialised at the first solve that needs it (jit.cpp: jit_lean_for) ----
 // The headline kernel for a shape the library has no lean instantiation of (cartpole at another horizon, a smaller system):
 // the reference accepts any (nx, nu, N) at run time (tiny_api.cpp:21-71).  A whole entry is 24 kernels and 45-90 s of compiler;
 // one variant — the (LIVE, UBK, ONE, XB, REFS) the launch in hand needs — is a few seconds, so a unit carries exactly one.
-// (ST = double: the fp64-state form, precision 2 — only ever built this way)
-template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB, int REFS, class ST>
+// (ST = double: the fp64-state form, precision 2 — only ever built this way; SP: the model's exact pattern, the sparse sweeps)
+template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB, int REFS, class ST, uint64_t SP = 0>
 hipError_t launch_lean_exact(const AdmmParams &P, bool, bool, bool, hipStream_t stream) {
-    hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE, UBK, ONE, XB, REFS, ST>), dim3((P.batch + 255) / 256), dim3(256), 0, stream, P);
+    hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE, UBK, ONE, XB, REFS, ST, SP>), dim3((P.batch + 255) / 256), dim3(256), 0, stream, P);
     return hipGetLastError();
 }
-#define TMPC_DEFINE_LEAN_JIT_ENTRY(NAME, NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST)                                    \
-    namespace tmpc {                                                                                                \
-    const LeanEntry *lean_jit_entry() {                                                                             \
-        static const LeanEntry e = {NX, NU, NN, NAME, &launch_lean_exact<NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST>}; \
-        return &e;                                                                                                  \
-    }                                                                                                               \
-    }                                                                                                               \
+#define TMPC_DEFINE_LEAN_JIT_ENTRY_SP(NAME, NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST, SP)                                  \
+    namespace tmpc {                                                                                                     \
+    const LeanEntry *lean_jit_entry() {                                                                                  \
+        static const LeanEntry e = {NX, NU, NN, NAME, &launch_lean_exact<NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST, SP>, SP}; \
+        return &e;                                                                                                       \
+    }                                                                                                                    \
+    }                                                                                                                    \
     extern "C" const void *tmpc_jit_entry() { return tmpc::lean_jit_entry(); }
+#define TMPC_DEFINE_LEAN_JIT_ENTRY(NAME, NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST) \
+    TMPC_DEFINE_LEAN_JIT_ENTRY_SP(NAME, NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST, 0)
 
 #define TMPC_DEFINE_LEAN_ENTRY(NX, NU, NN)                                                          \
     const LeanEntry *lean_entry_##NX##_##NU##_##NN() {                                              \
         static const LeanEntry e = {NX, NU, NN, "lean<" #NX "," #NU "," #NN ">", &launch_lean<NX, NU, NN>}; \
         return &e;                                                                                  \
+    }
+// ... with the sparse kernels of one (A, B) pattern beside it (lean_pattern_rm, admm_params.h)
+#define TMPC_DEFINE_LEAN_ENTRY_SP(NX, NU, NN, SP)                                                                  \
+    const LeanEntry *lean_entry_##NX##_##NU##_##NN() {                                                             \
+        static const LeanEntry e = {NX, NU, NN, "lean<" #NX "," #NU "," #NN ">", &launch_lean<NX, NU, NN>, (SP),   \
+                                    &launch_lean_sparse<NX, NU, NN, (SP)>};                                          \
+        return &e;                                                                                                 \
     }
 
 }  // namespace tmpc

@@ -46,11 +46,31 @@ struct LeanEntry {
     int nx, nu, N;
     const char *name;
     hipError_t (*launch)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t);
+    uint64_t sp = 0;   // the (A, B) pattern of the sparse kernels (admm_params.h: lean_pattern_rm): launch_sparse's, or a
+                       // specialised variant's own (launch); 0: none
+    hipError_t (*launch_sparse)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t) = nullptr;
 };
 const LeanEntry *find_lean_kernel(int nx, int nu, int N);
-// ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel)
-enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_COUNT = 64 };
-const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, int verbose);
+// ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel);
+// LV_SPARSE: on the model's own pattern sp
+enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_COUNT = 128 };
+const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, int verbose);
+// the lean kernel's 512-register form (one wavefront per SIMD): at most one workgroup per CU, tolerance-terminated solves,
+// TINYMPC_HIP_LEAN_ONE (lean_entry.hip.h: launch_lean_v)
+int device_cu_count();   // CU count of the current device (cached per device: a sharded handle launches on several)
+inline bool lean_one_form(int batch, bool live, bool force) { return (batch + 255) / 256 <= device_cu_count() || live || force; }
+// The sweeps a lean launch runs: the dense plain form, controller-Hessenberg (fixed iterations, no state bound, 512 registers)
+// or the sparse form of a pattern.  A kernel built for pattern `built` takes a model of pattern `model` when it covers it and
+// costs fewer fp64 instructions per knot than the form it replaces.
+enum { LF_NONE = 0, LF_PLAIN = 1, LF_HB = 2, LF_SPARSE = 3 };
+inline int lean_pick_form(int nx, int nu, uint64_t built, uint64_t model, bool one, bool live, bool xb, bool sparse_allowed) {
+    const bool hb = one && !live && !xb;
+    const int dense = hb ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
+    if (sparse_allowed && lean_pattern_covers(built, model) && lean_cost_sparse(built, nx, nu) < dense) return LF_SPARSE;
+    return hb ? LF_HB : LF_PLAIN;
+}
+// the (A, B) pattern of a solver's model (0: nx or nu above 4)
+uint64_t lean_pattern(const Mat &A, const Mat &B);
 // the lean kernel's fp64 pack (lean_layout); false when the family does not qualify (cache.AmBKt is not (A - B Kinf)')
 bool build_lean_pack(const Solver &, std::vector<double> &);
 // One (nx, nu) instantiation of the run-time-horizon stream kernel (admm_streamg.hip.h).
@@ -83,8 +103,6 @@ struct ConeEntry {
 };
 const ConeEntry *find_cone_kernel(int nx, int nu, int N);   // N = 0: the run-time-horizon entry only
 const ConeEntry *find_trans_kernel(int nx, int nu, int N);  // the transposed-sets kernel of the shape (admm_mfmat.hip.h), or null
-// CU count of the current device (cached per device: a sharded handle launches on several)
-int device_cu_count();
 hipError_t launch_generic(const AdmmParams &, int precision, hipStream_t);
 void build_generic_coef(const Solver &, std::vector<unsigned char> &);
 void build_generic_bounds(const Solver &, std::vector<float> &);
@@ -96,7 +114,8 @@ struct Switches {
          mfma_oneshot_only = false, no_stream = false, no_stream_adp = false, no_mfmar = false, no_mfmac = false, mfmac_all = false,
          no_mfmat = false, mfmat_all = false, mfmat_ws_only = false, no_lean = false, no_refill = false,
          no_uni = false, no_os = false, lean_one = false,   // lean_one: TINYMPC_HIP_LEAN_ONE — the lean kernel's 512-register variant at any batch
-         no_jit = false;                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
+         no_jit = false,                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
+         lean_dense = false;                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
     int mfmac_debug = 0;    // timing probe builds only
 };
 Switches read_switches();
@@ -185,6 +204,9 @@ struct Solver {
     double *d_lean = nullptr;
     bool lean_ok = false, lean_knot_bounds = false;
     bool lean_enabled = true;             // TINYMPC_HIP_NO_LEAN, read once at creation
+    uint64_t lean_sp = 0;                 // the (A, B) pattern of the model (lean_pattern), set with the pack
+    int last_lean_form = LF_NONE;         // the sweeps of the most recent launch (LF_*), and the per-knot fp64 costs it
+    int last_lean_cost[2] = {0, 0};       // weighed: the sparse form's (its pattern's), the form it replaces
     std::string last_launch_name;         // the kernel the most recent launch actually ran (family or its lean variant)
     // device buffers
     unsigned char *d_coef = nullptr;

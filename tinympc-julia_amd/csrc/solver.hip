@@ -349,6 +349,7 @@ Switches read_switches() {
     w.no_uni = on("TINYMPC_HIP_NO_UNI");
     w.no_os = on("TINYMPC_HIP_NO_OS");
     w.lean_one = on("TINYMPC_HIP_LEAN_ONE");
+    w.lean_dense = on("TINYMPC_HIP_LEAN_DENSE");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     return w;
 }
@@ -665,6 +666,7 @@ int Solver::upload_packs() {
     if (precision == 2 && !ke && !se && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise) lean_jit = true;
     std::fill(le_var_tried, le_var_tried + LV_COUNT, false);
     lean_ok = false;
+    lean_sp = lean_pattern(A, B);
     if (le || lean_jit) {
         std::vector<double> lp;
         if (build_lean_pack(*this, lp)) {
@@ -1241,16 +1243,33 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
                            ref_mode != REF_PER_INSTANCE && !st.adaptive_rho && max_iter_pass >= 1;
     const bool lean_live = st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0;
     const LeanEntry *lk = lean_call ? le : nullptr;
+    // the sweeps: the sparse form where a kernel's (A, B) pattern covers the model's and costs less per knot than the dense
+    // form it replaces (lean_pick_form; TINYMPC_HIP_LEAN_DENSE: never).  The built-in entry's sparse kernels take zero
+    // references and uniform input bounds; a specialised variant carries the model's own pattern, any calling pattern
+    int form = LF_NONE;
+    uint64_t form_sp = 0;
+    bool one = false;
+    if (lean_call && le) {
+        one = lean_one_form(P.batch, lean_live, sw.lean_one);
+        const bool can = le->launch_sparse && !sw.lean_dense && ref_mode == REF_ZERO && !lean_knot_bounds;
+        form_sp = le->launch_sparse ? le->sp : 0;
+        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, state_bounds_active, can);
+    }
     if (lean_call && !le && lean_jit) {
         // the one variant this launch needs (lean_entry.hip.h: launch_lean_v's choices), compiled on first use
-        bool one = (P.batch + 255) / 256 <= device_cu_count() || lean_live || sw.lean_one || lean_f64;
+        one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_f64;
         if (2 * N * nx + 3 * N * nu + 50 > 250) one = true;   // (the 256-register form does not hold this horizon)
+        form_sp = lean_sp;
+        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, state_bounds_active, !sw.lean_dense);
         const int v = (lean_live ? LV_LIVE : 0) | (lean_knot_bounds ? 0 : LV_UBK) | (one ? LV_ONE : 0) | (state_bounds_active ? LV_XB : 0) |
-                      (ref_mode == REF_SHARED ? LV_SHARED : 0) | (lean_f64 ? LV_F64 : 0);
-        if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, verbose), le_var_tried[v] = true;
+                      (ref_mode == REF_SHARED ? LV_SHARED : 0) | (lean_f64 ? LV_F64 : 0) | (form == LF_SPARSE ? LV_SPARSE : 0);
+        if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, form == LF_SPARSE ? lean_sp : 0, verbose), le_var_tried[v] = true;
         lk = le_var[v];
     }
     const bool lean = lk != nullptr;
+    last_lean_form = lean ? form : LF_NONE;
+    last_lean_cost[0] = lean && form_sp ? lean_cost_sparse(form_sp, nx, nu) : 0;
+    last_lean_cost[1] = !lean ? 0 : (one && !lean_live && !state_bounds_active) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
     if (lean && !le && (!ke || ke->G != 1)) P.bounds = reinterpret_cast<const float *>(d_lean + lean_layout(nx, nu).total);   // (upload_packs)
     P.lean = d_lean;
     P.ws64 = d_ws64;
@@ -1259,7 +1278,8 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0) | (sw.lean_one ? HF_LEAN_ONE : 0);
     last_launch_name = lean ? lk->name : kernel_name;
     if (lean) {
-        HIP_TRY(lk->launch(P, lean_live, lean_knot_bounds, state_bounds_active, stream));
+        if (form == LF_SPARSE && le) HIP_TRY(le->launch_sparse(P, lean_live, lean_knot_bounds, state_bounds_active, stream));
+        else HIP_TRY(lk->launch(P, lean_live, lean_knot_bounds, state_bounds_active, stream));
     } else
     HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
                : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
@@ -1530,3 +1550,15 @@ int Solver::set_workspace(const double *d, const double *y, const double *g, con
 }
 
 }  // namespace tmpc
+
+// (test hook, not part of the public boundary include/tinympc_hip.h: the lean sweeps of a solver's most recent launch) the
+// model's (A, B) pattern; the per-knot fp64 costs weighed — the sparse form's (0: no sparse kernel was on offer) and that of
+// the dense form it replaces; the form taken (LF_*: 0 no lean launch, 1 plain dense, 2 Hessenberg, 3 sparse)
+extern "C" int tmpc_lean_last_form(tinympc_solver *s, unsigned long long *pattern, int *cost_sparse, int *cost_dense, int *form) {
+    if (!s) return 1;
+    if (pattern) *pattern = s->s.lean_sp;
+    if (cost_sparse) *cost_sparse = s->s.last_lean_cost[0];
+    if (cost_dense) *cost_dense = s->s.last_lean_cost[1];
+    if (form) *form = s->s.last_lean_form;
+    return 0;
+}
