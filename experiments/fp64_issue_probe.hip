@@ -3,14 +3,17 @@
 // core cycles per instruction (s_memtime), the sustained core clock (s_memtime over s_memrealtime, 100 MHz) and wall-clock
 // nanoseconds per instruction (HIP events), for a grid of 64 workgroups (a quarter of the CUs) and of 256 x 4 wavefronts
 // (one per SIMD, the whole chip: the headline launch's shape) and 256 x 8 (two per SIMD).
+// v_pk_add_f32 (two fp32 adds on a register pair): what a lone wavefront pays to issue one, next to v_fma_f32 of the same run.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 #include <algorithm>
+typedef float v2f __attribute__((ext_vector_type(2)));
 template <int CH, int OP>
 __global__ __launch_bounds__(256) void k(float *out, long *cyc, int n, double cs) {
-    double d[8]; float f[8];
-    for (int i = 0; i < 8; ++i) d[i] = 0.5 + threadIdx.x * 1e-3 + i, f[i] = 0.25f + i;
+    double d[8]; float f[8]; v2f p[8];
+    for (int i = 0; i < 8; ++i) d[i] = 0.5 + threadIdx.x * 1e-3 + i, f[i] = 0.25f + i, p[i] = v2f{0.25f + i, 0.75f + i};
+    const v2f ep = {1e-9f, 2e-9f};
     const double cd = 1.0000001, ed = 1e-9;
     const float cf = 1.0000001f, ef = 1e-9f;
     long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
@@ -29,6 +32,7 @@ __global__ __launch_bounds__(256) void k(float *out, long *cyc, int n, double cs
             if (OP == 4) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(f[c]) : "v"(cf), "v"(ef));
             if (OP == 5) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(d[c]) : "v"(cd));
             if (OP == 6) asm volatile("v_add_f64 %0, %0, %1" : "+v"(d[c]) : "v"(ed));
+            if (OP == 7) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(p[c]) : "v"(ep));
         }
     }
     long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -37,7 +41,7 @@ __global__ __launch_bounds__(256) void k(float *out, long *cyc, int n, double cs
         cyc[2 * (blockIdx.x * 4 + threadIdx.x / 64) + 1] = r1 - r0;
     }
     double s = 0; float sf = 0;
-    for (int i = 0; i < 8; ++i) s += d[i], sf += f[i];
+    for (int i = 0; i < 8; ++i) s += d[i], sf += f[i] + p[i].x + p[i].y;
     out[blockIdx.x * 256 + threadIdx.x] = (float)s + sf;
 }
 template <int CH, int OP> void run(const char *name, float *d, long *c, int grid) {
@@ -70,6 +74,7 @@ int main() {
         run<4, 3>("6 fma64 : cvt : add32", d, c, grid); run<8, 3>("6 fma64 : cvt : add32", d, c, grid);
         run<1, 4>("v_fma_f32", d, c, grid); run<4, 4>("v_fma_f32", d, c, grid); run<8, 4>("v_fma_f32", d, c, grid);
         run<4, 5>("v_mul_f64", d, c, grid); run<4, 6>("v_add_f64", d, c, grid);
+        run<4, 7>("v_pk_add_f32", d, c, grid); run<8, 7>("v_pk_add_f32", d, c, grid);
     }
     return 0;
 }

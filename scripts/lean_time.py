@@ -1,6 +1,7 @@
 """Headline workload (cartpole (4,1,20), 100 fixed iterations, cold one-shot) on the lean kernel, the quad kernel it replaces and
 any variant libraries given (scripts/lean_variants.sh), all in ONE run (same box, same clocks); then a batch sweep and the
-termination-check-live / state-bound patterns.  usage: lean_time.py [variant.so ...]"""
+termination-check-live / state-bound patterns.  usage: lean_time.py [--clock-only] [variant.so ...]
+(--clock-only: the in-kernel timeline of the clock-probe libraries given — any *clk*.so — and nothing else)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r'''
@@ -36,6 +37,9 @@ elif mode == "clock":   # a library built with -DTMPC_LEAN_CLOCK_PROBE: the resi
         bs.set_warm_start(False); bs.set_x0(x0); bs.set_profiling(True)
         for _ in range(20): bs.solve()
         stt = bs.get_status(); r = stt["residuals"]; ms = bs.kernel_elapsed_ms(12); bs.close()
+        # (res[1]: 100 MHz ticks of the iteration loop; entry + that = the wavefront's loop end, prologue of < 1 us aside)
+        le = r[::64, 2] + r[::64, 1]
+        print(f"    first entry -> loop end of the first / median / last wavefront {(le.min() - r[:, 2].min()) * 1e-5:.4f} / {(np.median(le) - r[:, 2].min()) * 1e-5:.4f} / {(le.max() - r[:, 2].min()) * 1e-5:.4f} ms")
         print(f"    first entry -> last: stores issued {(stt['iter'].max() - r[:, 2].min()) * 1e-5:.4f} ms, stores acknowledged {(stt['solved'].max() - r[:, 2].min()) * 1e-5:.4f} ms, "
               f"status fold done {(r[:, 3].max() - r[:, 2].min()) * 1e-5:.4f} ms (kernel by events {ms:.4f} ms)")
         clk = r[:, 0] / r[:, 1] * 0.1
@@ -69,10 +73,14 @@ elif mode == "patterns":
         ms, name, _ = run(65536, kw, xb=xb)
         print(f"{tag:34s} {name:18s} {label:32s}: {ms:.4f} ms", flush=True)
 '''
-clk = [a for a in sys.argv[1:] if "clk" in os.path.basename(a)]
+clock_only = "--clock-only" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--clock-only"]
+clk = [a for a in args if "clk" in os.path.basename(a)]
 for lib in clk:
     subprocess.run([sys.executable, "-c", code, lib, "clock"], cwd=ROOT, check=False)
-libs = ["-"] + [a for a in sys.argv[1:] if a not in clk]
+if clock_only:
+    sys.exit(0)
+libs = ["-"] + [a for a in args if a not in clk]
 for rep in range(2):
     for lib in libs:
         subprocess.run([sys.executable, "-c", code, lib, "head"], cwd=ROOT, check=False)

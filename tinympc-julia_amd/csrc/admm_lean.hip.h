@@ -48,6 +48,20 @@
 #define TMPC_LEAN_SPLITK 0    // 1: Kinf x as two chains of two (+ an add): shorter dependent chain, one more instruction
 #endif
 
+#ifndef TMPC_LEAN_WIDE_STORE
+#define TMPC_LEAN_WIDE_STORE 1    // 0: the final store in 4-byte pieces (store_wave_coalesced) at every shape
+#endif
+#ifndef TMPC_LEAN_STORE_W
+#define TMPC_LEAN_STORE_W 0       // floats per instance and pass of the wide store; 0: wide_stage_width(EX) (tuning aid)
+#endif
+#ifndef TMPC_LEAN_FOLD_FIRST
+// 1: the status fold ahead of the final store (its fence then has no solution stores to wait for).  Tried and left off: the
+// folding wavefront's stores then wait for the fold's atomics and ticket (the fold is 11-20 us behind 256 workgroups, not 3),
+// while the other three wavefronts' stores already fill the L2 its fence writes back — the headline step 0.1352 -> 0.1405 ms
+// (profiles/r07_lean_ab.txt)
+#define TMPC_LEAN_FOLD_FIRST 0
+#endif
+
 namespace tmpc {
 
 template <int NX, int NU>
@@ -164,8 +178,15 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     const long b = (long)blockIdx.x * 256 + tid;     // (no index list: the solver sends compacted / chunked solves to the quad kernel)
     const bool active = b < P.batch;
     const int lane = tid & 63;
-    // staging of a wavefront's solution for the final store (below): [64 instances][16 + 1 floats], or [64][nu (N-1)]
-    __shared__ float s_stage[4][wave_stage_floats(EU)];
+    // staging of a wavefront's solution for the final store (below): the wide form's [64 instances][W (+ 4) floats] / flat
+    // [64][nu (N-1)] where the shape takes it (nx N a multiple of 4), else [64][16 + 1 floats] / [64][nu (N-1) | 1]
+    constexpr int SW = !TMPC_LEAN_WIDE_STORE ? 0 : (TMPC_LEAN_STORE_W ? TMPC_LEAN_STORE_W : wide_stage_width(EX));
+    static_assert(SW == 0 || (SW % 4 == 0 && EX % SW == 0), "wide store: W a multiple of 4 that divides nx N");
+    constexpr int STAGE = SW ? wave_stage_floats_wide(EU, SW) : wave_stage_floats(EU);
+    // (the wide image is held to 48 KiB by wide_stage_width; the predicated controls' [64][nu (N-1) | 1] may exceed it at long
+    // horizons, as it always could: the workgroup's 64 KiB of static LDS is the compiler's to check)
+    static_assert(SW == 0 || 4 * 64 * wide_stage_stride(SW) * sizeof(float) <= 48 * 1024, "wide store: staging beyond its 48 KiB");
+    __shared__ __attribute__((aligned(16))) float s_stage[4][STAGE];
 
     const SBlock<double, L::NLOADS> blk(P.lean + (HB ? L::O_H : (SPR ? L::O_S : 0)));   // (SPR: A where M is)
     const auto cM = blk.at(L::O_M), cK = blk.at(L::O_K), cB = blk.at(L::O_B), cC = blk.at(L::O_C);
@@ -554,34 +575,9 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         // an exit before it costs them 2-50 spilled registers)
         if (!(ONE && !XB) || i < max_iter) backward();
     }
-    // ---- final store of every instance that has not stored at its convergence: through LDS, so that a store instruction
-    // writes whole 64-byte pieces (X: 16 consecutive floats of 4 instances) or one contiguous 256 bytes (U) instead of 64
-    // scattered 16-byte / 4-byte ones — with every wavefront finishing at once the scattered form took 50 us of a 300 us
-    // launch (26 MB at 0.5 TB/s) ----
-    {
-        const bool mine = active && !conv;
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
-        if (mask) {
-            if constexpr (HB) load_T(Ts);
-            const long w0 = (long)blockIdx.x * 256 + (tid & ~63);          // the wavefront's first instance
-            store_wave_coalesced<EX, EU>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask,
-                                         [&](auto ee) { constexpr int e = decltype(ee)::value; return vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{}); },
-                                         [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Z[e / NU][e % NU]; });
-            if (mine) {
-                float *ro = P.res + b * 4;
-                P.iter[b] = P.iter_offset + it;
-                P.solved[b] = 0;
-                ro[0] = (float)res0, ro[1] = (float)res1, ro[2] = (float)res2, ro[3] = (float)res3;
-#ifdef TMPC_LEAN_CLOCK_PROBE
-                ro[0] = (float)(__builtin_amdgcn_s_memtime() - probe_t0);          // core clocks of the iteration loop (+ store issue)
-                ro[1] = (float)(__builtin_amdgcn_s_memrealtime() - probe_r0);      // ... in 100 MHz ticks
-                ro[2] = (float)(probe_entry & 0xFFFFFFull);                        // kernel entry on the chip-wide 100 MHz counter
-#endif
-            }
-        }
-    }
-
-    {   // global status block: wavefront max of the residuals, count of unsolved instances
+    // ---- global status block: wavefront max of the residuals, count of unsolved instances; behind the final store, or
+    // (TMPC_LEAN_FOLD_FIRST) ahead of it ----
+    auto fold = [&]() {
         float m0 = active ? (float)res0 : 0.f, m1 = active ? (float)res1 : 0.f, m2 = active ? (float)res2 : 0.f, m3 = active ? (float)res3 : 0.f;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -591,16 +587,60 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             m3 = fmaxf(m3, __shfl_xor(m3, o, 64));
         }
         const unsigned long long unsolved = __builtin_amdgcn_ballot_w64(active && !conv);
-#ifdef TMPC_LEAN_CLOCK_PROBE
-        if (active) P.iter[b] = (int)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);     // stores issued
-        __builtin_amdgcn_s_waitcnt(0);
-        if (active) P.solved[b] = (int)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);   // ... and acknowledged
-#endif
         fold_status(P, m0, m1, m2, m3, __popcll(unsolved), tid);   // (one set of atomics per workgroup)
+    };
 #ifdef TMPC_LEAN_CLOCK_PROBE
-        if (active) P.res[b * 4 + 3] = (float)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);   // after the status fold
+    const unsigned long long probe_t1 = __builtin_amdgcn_s_memtime(), probe_r1 = __builtin_amdgcn_s_memrealtime();   // loop end
+    unsigned long long probe_fold = 0;
+#endif
+    if constexpr (TMPC_LEAN_FOLD_FIRST) {
+        fold();
+#ifdef TMPC_LEAN_CLOCK_PROBE
+        probe_fold = __builtin_amdgcn_s_memrealtime();
 #endif
     }
+    // ---- final store of every instance that has not stored at its convergence: through LDS, so that a store instruction
+    // writes 1 KiB — consecutive lanes consecutive 16 bytes (store_wave_wide, admm_quad.hip.h) — or, where the shape does not
+    // take the wide form, whole 64-byte pieces (X: 16 consecutive floats of 4 instances) / one contiguous 256 bytes (U),
+    // instead of 64 scattered 16-byte / 4-byte ones — with every wavefront finishing at once the scattered form took 50 us
+    // of a 300 us launch (26 MB at 0.5 TB/s) ----
+    {
+        const bool mine = active && !conv;
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
+        if (mask) {
+            if constexpr (HB) load_T(Ts);
+            const long w0 = (long)blockIdx.x * 256 + (tid & ~63);          // the wavefront's first instance
+            auto getx = [&](auto ee) { constexpr int e = decltype(ee)::value; return vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{}); };
+            auto getu = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Z[e / NU][e % NU]; };
+            if constexpr (SW != 0) store_wave_wide<EX, EU, SW>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask, getx, getu);
+            else store_wave_coalesced<EX, EU>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask, getx, getu);
+            if (mine) {
+                float *ro = P.res + b * 4;
+                P.iter[b] = P.iter_offset + it;
+                P.solved[b] = 0;
+                ro[0] = (float)res0, ro[1] = (float)res1, ro[2] = (float)res2, ro[3] = (float)res3;
+            }
+        }
+    }
+#ifdef TMPC_LEAN_CLOCK_PROBE
+    if (active) P.iter[b] = (int)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);     // stores issued
+    __builtin_amdgcn_s_waitcnt(0);
+    if (active) P.solved[b] = (int)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);   // ... and acknowledged
+#endif
+    if constexpr (!TMPC_LEAN_FOLD_FIRST) {
+        fold();
+#ifdef TMPC_LEAN_CLOCK_PROBE
+        probe_fold = __builtin_amdgcn_s_memrealtime();
+#endif
+    }
+#ifdef TMPC_LEAN_CLOCK_PROBE
+    if (active) {
+        P.res[b * 4 + 0] = (float)(probe_t1 - probe_t0);                                // core clocks of the iteration loop
+        P.res[b * 4 + 1] = (float)(probe_r1 - probe_r0);                                // ... in 100 MHz ticks
+        P.res[b * 4 + 2] = (float)(probe_entry & 0xFFFFFFull);                          // kernel entry on the chip-wide 100 MHz counter
+        P.res[b * 4 + 3] = (float)(probe_fold & 0xFFFFFFull);                           // after the status fold
+    }
+#endif
 }
 
 }  // namespace tmpc

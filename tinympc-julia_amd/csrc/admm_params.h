@@ -222,10 +222,13 @@ __device__ __forceinline__ void fold_status(const AdmmParams &P, float m0, float
         __threadfence();  // this workgroup's contributions before its ticket
         if (atomicAdd(&P.gacc[7], 1u) == gridDim.x - 1) {
             __threadfence();
+            uint32_t tot[5];              // (the swaps issued together and waited for once: this is the tail of the launch)
 #pragma unroll
-            for (int i = 0; i < 5; ++i) P.gstat[i] = atomicExch(&P.gacc[i], 0u);
+            for (int i = 0; i < 5; ++i) tot[i] = atomicExch(&P.gacc[i], 0u);
             atomicExch(&P.gacc[6], 0u);   // (persistent kernels' tile counter)
             atomicExch(&P.gacc[7], 0u);
+#pragma unroll
+            for (int i = 0; i < 5; ++i) P.gstat[i] = tot[i];
         }
     }
 }

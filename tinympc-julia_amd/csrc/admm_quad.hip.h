@@ -334,6 +334,88 @@ __device__ __forceinline__ void store_wave_coalesced(float *so, float *__restric
         store_wave_u<EU, false>(so, uo, lane, mask, getu);
     }
 }
+// The wide form of the same store (lean kernel): 16 bytes per lane, so that one store instruction writes 1 KiB instead of
+// 256 bytes — a wavefront's 64 instances own ONE contiguous block of each array (64 EX and 64 EU floats), and with every
+// wavefront of a launch storing at the same moment the tail is bound by the issue of store instructions, not by bytes.
+// States: W floats per instance and pass (W a multiple of 4 that divides EX).  A lane stages its W floats as float4
+// (ds_write_b128: groups of 8 consecutive lanes, bank = dword address mod 32 — conflict-free when the row stride S is an odd
+// number of float4, wide_stage_stride); float4 q = 64 i + lane of the pass's [64][W] image is then read back by lane
+// (ds_read_b128 of consecutive 16-byte slots; the pad word shifts the slots of a group that straddles two instances, at most
+// 2-way on one slot) and stored at its place: consecutive lanes write consecutive 16 bytes within an instance's W floats.
+// A float4 never spans two instances, so the predicated form (FULL = false) masks whole lanes.
+constexpr int wide_stage_stride(int W) { return (W / 4) % 2 ? W : W + 4; }
+// the widest pass whose staging (four wavefronts, padded rows) stays within 48 KiB: three quarters of the 64 KiB a workgroup
+// may declare statically, the rest left to the caller's other arrays (bounds, reference terms) — two such workgroups fit a
+// CU's 160 KB either way; 0: the shape does not fit the wide form (EX not a multiple of 4)
+constexpr int wide_stage_width(int EX) {
+    int w = 0;
+    for (int c = 4; c <= EX && c <= 44; c += 4)
+        if (EX % c == 0) w = c;
+    return EX % 4 == 0 ? w : 0;
+}
+template <int EX, int W, bool FULL, class FX>
+__device__ __forceinline__ void store_wave_x_wide(float *so, float *__restrict__ xo, int lane, unsigned long long mask, FX &&getx) {
+    static_assert(W % 4 == 0 && EX % W == 0, "wide store: W a multiple of 4 that divides EX");
+    constexpr int S = wide_stage_stride(W), Q = W / 4;          // Q float4 per instance and pass = store instructions per pass
+    sfor<0, EX / W>([&](auto pp) {
+        constexpr int p = decltype(pp)::value;
+        sfor<0, Q>([&](auto jj) {
+            constexpr int e = p * W + 4 * decltype(jj)::value;
+            const float4 v = make_float4(getx(std::integral_constant<int, e>{}), getx(std::integral_constant<int, e + 1>{}),
+                                         getx(std::integral_constant<int, e + 2>{}), getx(std::integral_constant<int, e + 3>{}));
+            *reinterpret_cast<float4 *>(so + lane * S + 4 * decltype(jj)::value) = v;
+        });
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        float4 r[Q];
+#pragma unroll
+        for (int i = 0; i < Q; ++i) {                             // float4 q of the pass's image: instance q / Q, its float4 q % Q
+            const int q = i * 64 + lane, inst = q / Q;
+            r[i] = *reinterpret_cast<const float4 *>(so + 4 * q + inst * (S - W));
+        }
+#pragma unroll
+        for (int i = 0; i < Q; ++i) {
+            const int q = i * 64 + lane, inst = q / Q;
+            if (FULL || ((mask >> inst) & 1ull)) *reinterpret_cast<float4 *>(xo + 4 * q + inst * (EX - W) + p * W) = r[i];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    });
+}
+// Controls of a wavefront whose every instance stores: the flat [64][EU] image (4-byte writes at stride EU: conflict-free for
+// odd EU, gcd(EU, 32)-way otherwise — 2-way costs a ds_write_b32 nothing, a multiple of 4 doubles the EU writes; the image
+// cannot be padded, a float4 of it crosses instances) read back as its 16 EU float4 — the last instruction ragged, predicated by lane — and stored contiguously.
+// (Lanes of a ragged wavefront keep store_wave_u: a float4 of the flat image may span two instances.)
+template <int EU, class FU>
+__device__ __forceinline__ void store_wave_u_wide(float *so, float *__restrict__ uo, int lane, FU &&getu) {
+    sfor<0, EU>([&](auto ee) {
+        constexpr int e = decltype(ee)::value;
+        so[lane * EU + e] = getu(std::integral_constant<int, e>{});
+    });
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    constexpr int NV = 16 * EU, NI = (NV + 63) / 64;             // float4 of the image; store instructions
+    float4 r[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+        if ((i + 1) * 64 <= NV || i * 64 + lane < NV) r[i] = reinterpret_cast<const float4 *>(so)[i * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+        if ((i + 1) * 64 <= NV || i * 64 + lane < NV) reinterpret_cast<float4 *>(uo)[i * 64 + lane] = r[i];
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+template <int EX, int EU, int W, class FX, class FU>
+__device__ __forceinline__ void store_wave_wide(float *so, float *__restrict__ xo, float *__restrict__ uo, int lane,
+                                                unsigned long long mask, FX &&getx, FU &&getu) {
+    if (mask == ~0ull) {   // every instance of the wavefront stores (the usual case): no predicates
+        store_wave_x_wide<EX, W, true>(so, xo, lane, mask, getx);
+        store_wave_u_wide<EU>(so, uo, lane, getu);
+    } else {
+        store_wave_x_wide<EX, W, false>(so, xo, lane, mask, getx);
+        store_wave_u<EU, false>(so, uo, lane, mask, getu);
+    }
+}
 // ... and the way in: a wavefront's instances' arrays from HBM — a load instruction reads whole 64-byte pieces / contiguous
 // 256 bytes — through LDS into the registers of the lane that owns the instance (the kept workspace at the start of a solve:
 // read in per-lane strides it cost as much again as the strided stores).  setx(e, value) / setu(e, value): element e of this
@@ -386,6 +468,12 @@ __device__ __forceinline__ void load_wave_u(float *so, const float *__restrict__
     __builtin_amdgcn_wave_barrier();
 }
 constexpr int wave_stage_floats(int EU) { return 64 * 17 > 64 * (EU | 1) ? 64 * 17 : 64 * (EU | 1); }
+// floats of one wavefront's staging for the wide stores (states: [64][S]; controls: the flat [64][EU] image), a multiple of 4
+constexpr int wave_stage_floats_wide(int EU, int W) {
+    const int x = 64 * wide_stage_stride(W), u = 64 * EU, o = wave_stage_floats(EU);
+    const int m = x > u ? (x > o ? x : o) : (u > o ? u : o);
+    return (m + 3) / 4 * 4;
+}
 
 __device__ __forceinline__ float tfma(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double tfma(double a, double b, double c) { return fma(a, b, c); }

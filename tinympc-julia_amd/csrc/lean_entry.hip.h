@@ -1,12 +1,22 @@
 // Launcher of one lean-kernel instantiation (admm_lean.hip.h); one translation unit per shape (linst_*.hip).
 #pragma once
+#include <hip/hip_ext.h>
+
 #include "admm_lean.hip.h"
 #include "solver.h"
 
 namespace tmpc {
 
+// One dispatch.  ev0 / ev1 (a profiled solve): the kernel's start and end, carried by the dispatch packet itself instead of
+// marker packets of their own before and behind it (Solver::launch_pass); null events: the plain launch.
+template <class K>
+inline void lean_dispatch(K kernel, int grid, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const AdmmParams &P) {
+    if (ev0 || ev1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, ev0, ev1, 0, P);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, P);
+}
+
 template <int NX, int NU, int N, bool XB, int REFS>
-hipError_t launch_lean_v(const AdmmParams &P, bool live, bool knot_bounds, hipStream_t stream) {
+hipError_t launch_lean_v(const AdmmParams &P, bool live, bool knot_bounds, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     const int grid = (P.batch + 255) / 256;
     // (lean_one_form, solver.h)  The 512-register variant when the launch has at most one workgroup per CU (= one wavefront per SIMD), and — at any batch —
     // for tolerance-terminated solves: held to 256 registers the LIVE variants spill (73-187 registers) and lose to 512-register
@@ -14,7 +24,7 @@ hipError_t launch_lean_v(const AdmmParams &P, bool live, bool knot_bounds, hipSt
     // fixed-iteration solves: 0.47 / 0.61 against 0.46 / 0.69 — scripts/lean_time.py "big").  TINYMPC_HIP_LEAN_ONE: always (tuning aid).
     const bool one = lean_one_form(P.batch, live, (P.host_flags & HF_LEAN_ONE) != 0);
 #define TMPC_LEAN_LAUNCH(LIVE_, UBK_, ONE_) \
-    hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE_, UBK_, ONE_, XB, REFS>), dim3(grid), dim3(256), 0, stream, P)
+    lean_dispatch(admm_lean_kernel<NX, NU, N, LIVE_, UBK_, ONE_, XB, REFS>, grid, stream, ev0, ev1, P)
 #define TMPC_LEAN_LAUNCH2(LIVE_, UBK_) \
     do { if (one) TMPC_LEAN_LAUNCH(LIVE_, UBK_, true); else TMPC_LEAN_LAUNCH(LIVE_, UBK_, false); } while (0)
     if (live) {   // (always the 512-register variant: the 256-register LIVE kernels are not even built)
@@ -30,24 +40,26 @@ hipError_t launch_lean_v(const AdmmParams &P, bool live, bool knot_bounds, hipSt
 // live: positive tolerances (residuals at every check, per-instance exits); knot_bounds: the input bounds depend on the knot;
 // state_bounds: some enabled state bound is finite; P.ref_mode: REF_ZERO or REF_SHARED
 template <int NX, int NU, int N>
-hipError_t launch_lean(const AdmmParams &P, bool live, bool knot_bounds, bool state_bounds, hipStream_t stream) {
+hipError_t launch_lean(const AdmmParams &P, bool live, bool knot_bounds, bool state_bounds, hipStream_t stream, hipEvent_t ev0,
+                       hipEvent_t ev1) {
     if (P.ref_mode == REF_SHARED)
-        return state_bounds ? launch_lean_v<NX, NU, N, true, REF_SHARED>(P, live, knot_bounds, stream)
-                            : launch_lean_v<NX, NU, N, false, REF_SHARED>(P, live, knot_bounds, stream);
-    return state_bounds ? launch_lean_v<NX, NU, N, true, REF_ZERO>(P, live, knot_bounds, stream)
-                        : launch_lean_v<NX, NU, N, false, REF_ZERO>(P, live, knot_bounds, stream);
+        return state_bounds ? launch_lean_v<NX, NU, N, true, REF_SHARED>(P, live, knot_bounds, stream, ev0, ev1)
+                            : launch_lean_v<NX, NU, N, false, REF_SHARED>(P, live, knot_bounds, stream, ev0, ev1);
+    return state_bounds ? launch_lean_v<NX, NU, N, true, REF_ZERO>(P, live, knot_bounds, stream, ev0, ev1)
+                        : launch_lean_v<NX, NU, N, false, REF_ZERO>(P, live, knot_bounds, stream, ev0, ev1);
 }
 
 // The sparse kernels of one (A, B) pattern SP (admm_lean.hip.h): zero references and input bounds that do not depend on the
 // knot only, in the (LIVE, ONE, XB) combinations launch_lean_v picks — six kernels (the routing, Solver::launch_pass, sends
 // nothing else here)
 template <int NX, int NU, int N, uint64_t SP>
-hipError_t launch_lean_sparse(const AdmmParams &P, bool live, bool knot_bounds, bool state_bounds, hipStream_t stream) {
+hipError_t launch_lean_sparse(const AdmmParams &P, bool live, bool knot_bounds, bool state_bounds, hipStream_t stream, hipEvent_t ev0,
+                              hipEvent_t ev1) {
     if (P.ref_mode != REF_ZERO || knot_bounds) return hipErrorInvalidValue;
     const int grid = (P.batch + 255) / 256;
     const bool one = lean_one_form(P.batch, live, (P.host_flags & HF_LEAN_ONE) != 0);
 #define TMPC_LEAN_LAUNCH(LIVE_, ONE_, XB_) \
-    hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE_, true, ONE_, XB_, REF_ZERO, float, SP>), dim3(grid), dim3(256), 0, stream, P)
+    lean_dispatch(admm_lean_kernel<NX, NU, N, LIVE_, true, ONE_, XB_, REF_ZERO, float, SP>, grid, stream, ev0, ev1, P)
 #define TMPC_LEAN_LAUNCH2(LIVE_, ONE_) \
     do { if (state_bounds) TMPC_LEAN_LAUNCH(LIVE_, ONE_, true); else TMPC_LEAN_LAUNCH(LIVE_, ONE_, false); } while (0)
     if (live) TMPC_LEAN_LAUNCH2(true, true);
@@ -64,8 +76,8 @@ hipError_t launch_lean_sparse(const AdmmParams &P, bool live, bool knot_bounds, 
 // one variant — the (LIVE, UBK, ONE, XB, REFS) the launch in hand needs — is a few seconds, so a unit carries exactly one.
 // (ST = double: the fp64-state form, precision 2 — only ever built this way; SP: the model's exact pattern, the sparse sweeps)
 template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB, int REFS, class ST, uint64_t SP = 0>
-hipError_t launch_lean_exact(const AdmmParams &P, bool, bool, bool, hipStream_t stream) {
-    hipLaunchKernelGGL((admm_lean_kernel<NX, NU, N, LIVE, UBK, ONE, XB, REFS, ST, SP>), dim3((P.batch + 255) / 256), dim3(256), 0, stream, P);
+hipError_t launch_lean_exact(const AdmmParams &P, bool, bool, bool, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    lean_dispatch(admm_lean_kernel<NX, NU, N, LIVE, UBK, ONE, XB, REFS, ST, SP>, (P.batch + 255) / 256, stream, ev0, ev1, P);
     return hipGetLastError();
 }
 #define TMPC_DEFINE_LEAN_JIT_ENTRY_SP(NAME, NX, NU, NN, LIVE, UBK, ONE, XB, REFS, ST, SP)                                  \

@@ -45,10 +45,12 @@ const KernelEntry *find_mfma_kernel(int nx, int nu, int N);
 struct LeanEntry {
     int nx, nu, N;
     const char *name;
-    hipError_t (*launch)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t);
+    // ev0 / ev1: timing events carried by the kernel's own dispatch packet (its start and its end); null: none
+    hipError_t (*launch)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0, hipEvent_t ev1);
     uint64_t sp = 0;   // the (A, B) pattern of the sparse kernels (admm_params.h: lean_pattern_rm): launch_sparse's, or a
                        // specialised variant's own (launch); 0: none
-    hipError_t (*launch_sparse)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t) = nullptr;
+    hipError_t (*launch_sparse)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
+                                hipEvent_t ev1) = nullptr;
 };
 const LeanEntry *find_lean_kernel(int nx, int nu, int N);
 // ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel);
@@ -115,7 +117,8 @@ struct Switches {
          no_mfmat = false, mfmat_all = false, mfmat_ws_only = false, no_lean = false, no_refill = false,
          no_uni = false, no_os = false, lean_one = false,   // lean_one: TINYMPC_HIP_LEAN_ONE — the lean kernel's 512-register variant at any batch
          no_jit = false,                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
-         lean_dense = false;                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
+         lean_dense = false,                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
+         event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
     int mfmac_debug = 0;    // timing probe builds only
 };
 Switches read_switches();
@@ -259,7 +262,8 @@ struct Solver {
     // sensitivities, precision / warm-start / compaction switches): what set_gpus() replays onto fresh shards
     int copy_family_state(const Solver &o);
     // last launch of this solver, whatever stream it went to: every getter waits for it first
-    hipEvent_t ev_done = nullptr;
+    // (a profiled lean launch carries its timing events in its own packet: its stop event is then the one waited for)
+    hipEvent_t ev_done = nullptr, ev_wait = nullptr;
     bool ev_done_pending = false;
     int wait_last_launch();
     int select_kernel(bool rollout = false);  // rollout: the next launch is the fused closed loop

@@ -160,7 +160,7 @@ Solver::~Solver() {
 // event recorded behind the last launch rather than relying on null-stream ordering, which a non-blocking stream escapes.
 int Solver::wait_last_launch() {
     if (ev_done_pending) {
-        HIP_TRY(hipEventSynchronize(ev_done));
+        HIP_TRY(hipEventSynchronize(ev_wait));
         ev_done_pending = false;
     }
     return 0;
@@ -350,6 +350,7 @@ Switches read_switches() {
     w.no_os = on("TINYMPC_HIP_NO_OS");
     w.lean_one = on("TINYMPC_HIP_LEAN_ONE");
     w.lean_dense = on("TINYMPC_HIP_LEAN_DENSE");
+    w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     return w;
 }
@@ -1230,7 +1231,6 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
         }
         ev0 = ev_ring[2 * (launches % EV_RING)];
         ev1 = ev_ring[2 * (launches % EV_RING) + 1];
-        HIP_TRY(hipEventRecord(ev0, stream));
     }
     // the workspace's state dual is non-zero only if some solve since the last reset had a finite state bound (or the
     // caller wrote one in): the matrix-core kernel (G == 16) carries g only then
@@ -1277,23 +1277,35 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     P.abs_dua_tol64 = st.abs_dua_tol;
     P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0) | (sw.lean_one ? HF_LEAN_ONE : 0);
     last_launch_name = lean ? lk->name : kernel_name;
+    // A profiled lean launch carries its two timing events in the kernel's own dispatch packet (start and end of the kernel):
+    // recorded on their own they are marker packets the command processor handles between two kernels that are already
+    // serialised, and a third one for the completion wait — four packets per solve where one does.  The stop event then
+    // serves the completion wait too.  TINYMPC_HIP_EVENT_MARKERS: the separate records (timing aid).
+    const bool attached = profiling && lean && !sw.event_markers;
+    if (profiling && !attached) HIP_TRY(hipEventRecord(ev0, stream));
     if (lean) {
-        if (form == LF_SPARSE && le) HIP_TRY(le->launch_sparse(P, lean_live, lean_knot_bounds, state_bounds_active, stream));
-        else HIP_TRY(lk->launch(P, lean_live, lean_knot_bounds, state_bounds_active, stream));
+        hipEvent_t a0 = attached ? ev0 : nullptr, a1 = attached ? ev1 : nullptr;
+        if (form == LF_SPARSE && le) HIP_TRY(le->launch_sparse(P, lean_live, lean_knot_bounds, state_bounds_active, stream, a0, a1));
+        else HIP_TRY(lk->launch(P, lean_live, lean_knot_bounds, state_bounds_active, stream, a0, a1));
     } else
     HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
                : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
                      : (se ? se->launch(P, precision, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), hetero, stream)
                            : launch_generic(P, precision, stream))));
     if (profiling) {
-        HIP_TRY(hipEventRecord(ev1, stream));
+        if (!attached) HIP_TRY(hipEventRecord(ev1, stream));
         launches += 1;
     }
     // the status block stays on the device; solve_status() fetches it when asked (nothing but the kernel and the
     // 32-byte clear is enqueued per solve)
     solved_once = true;
-    if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ev_done, stream));
+    if (attached) {
+        ev_wait = ev1;
+    } else {
+        if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ev_done, stream));
+        ev_wait = ev_done;
+    }
     ev_done_pending = true;
     return 0;
 }
@@ -1363,6 +1375,7 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     mpc_steps_last = mpc_steps;
     if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ev_done, stream));
+    ev_wait = ev_done;
     ev_done_pending = true;
     return 0;
 }
