@@ -1,11 +1,13 @@
 // Fused TinyMPC ADMM kernel for gfx950 — "lean" layout: the benchmark's calling pattern of the small shapes with as few
 // vector instructions per ADMM iteration as the arithmetic allows.
 //
-// What it computes: the reference's solve() loop (src/codegen_src/tinympc/admm.cpp:109-207; phases :13-107) for one-shot
-// solves — cold start (the zero workspace tiny_setup leaves, tiny_api.cpp:73-88), nothing of the workspace kept — of a
-// box-constrained family, zero or shared references, fp64 recurrences.  One lane per instance, like quad<..., g1>
-// (admm_quad.hip.h), which stays the kernel of every other calling pattern of the shape (workspace kept, closed loop,
-// per-instance references, adaptive rho, fp32 recurrences).  The benchmark's pattern — no active state bound, zero
+// What it computes: the reference's solve() loop (src/codegen_src/tinympc/admm.cpp:109-207; phases :13-107) of a
+// box-constrained family, zero or shared references, fp64 recurrences: one-shot solves — cold start (the zero workspace
+// tiny_setup leaves, tiny_api.cpp:73-88), nothing of the workspace kept — and, in the WS form (described at the kernel, routed
+// to with TINYMPC_HIP_LEAN_WS), solves that go on from the kept workspace and leave it as the reference does, which is what a
+// host-stepped or chained closed loop is made of.  One lane per instance, like quad<..., g1> (admm_quad.hip.h), which stays the
+// kernel of every other calling pattern of the shape (per-instance references, adaptive rho, fp32 recurrences, chunked
+// solves, the in-kernel closed loop — and, without the switch, every kept-workspace solve).  The benchmark's pattern — no active state bound, zero
 // references — is the XB = false, REFS = REF_ZERO instantiation described first; XB / REF_SHARED add what they need and
 // nothing to that instantiation (profiles/r04_cartpole_isa_census.json is its loop).
 //
@@ -88,10 +90,22 @@ __device__ __forceinline__ double lean_abs(double a) { return fabs(a); }
 // reference's own arithmetic end to end (types.hpp:15) — precision 2 for one-shot solves of the shapes this kernel holds, at
 // this kernel's speed instead of the generic kernel's; only ever specialised on request (jit.cpp), in the ONE form.
 // SP: the zero / unit pattern of the model's (A, B) the kernel is built for (admm_params.h: lean_pattern_covers), 0: none.
-template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB = false, int REFS = REF_ZERO, class ST = float, uint64_t SP = 0>
+// WS: the workspace-keeping form.  P.cold_start / P.save_state are honoured at run time, as the quad kernel does: a warm solve
+// goes on from the d, y, g, v, z the previous one left (admm.cpp:111-115), a saving one leaves what the reference's workspace
+// holds at its exit — and the plant state comes from P.x0d (fp64) when the caller chains a closed loop.  The arrays travel
+// through the wavefront's LDS staging both ways (load_wave_x / load_wave_u, the staged stores below).  A converged exit
+// returns BEFORE v = vnew, z = znew and the backward pass (admm.cpp:181-193), so the workspace then holds the PREVIOUS
+// iteration's v, z and d: d is still in its registers; v and z are parked in LDS as floats (what the workspace holds anyway)
+// by the residual iteration just before each knot overwrites them.  A converging wavefront stores solution and workspace
+// through the staging with the ballot of its converging lanes as the mask — in the steady state of a warm-started loop every
+// lane of a wavefront converges at the same check — and its lanes idle on as in the one-shot form; nothing of them is
+// stored again.  Without XB the form assumes the workspace's g is zero and leaves it alone (the host picks XB otherwise).
+constexpr int lean_park_stride(int EX) { return (((EX + 3) / 4) % 2 ? (EX + 3) / 4 : (EX + 3) / 4 + 1) * 4; }   // an odd number of float4
+template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB = false, int REFS = REF_ZERO, class ST = float, uint64_t SP = 0, bool WS = false>
 __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const AdmmParams P) {
     constexpr bool F64 = std::is_same<ST, double>::value;
     static_assert(!F64 || ONE, "fp64 state: the 512-register form");
+    static_assert(!WS || !F64, "kept workspace: fp32 state (the fp64 workspace has another format)");
     static_assert(REFS == REF_ZERO || REFS == REF_SHARED, "lean kernel: zero or shared references");
 #ifdef TMPC_LEAN_CLOCK_PROBE
     const unsigned long long probe_entry = __builtin_amdgcn_s_memrealtime();
@@ -187,6 +201,12 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // horizons, as it always could: the workgroup's 64 KiB of static LDS is the compiler's to check)
     static_assert(SW == 0 || 4 * 64 * wide_stage_stride(SW) * sizeof(float) <= 48 * 1024, "wide store: staging beyond its 48 KiB");
     __shared__ __attribute__((aligned(16))) float s_stage[4][STAGE];
+    // WS, LIVE: the previous iteration's v and z of every lane (rows of an odd number of float4, written 16 bytes at a time —
+    // park_v — / of an odd number of floats, written 4 bytes at a time: conflict-free both)
+    constexpr bool PARK = WS && LIVE;
+    constexpr int PVS = lean_park_stride(EX), PZS = EU | 1;
+    __shared__ __attribute__((aligned(16))) float s_pv[PARK ? 256 * PVS : 4];
+    __shared__ float s_pz[PARK ? 256 * PZS : 1];
 
     const SBlock<double, L::NLOADS> blk(P.lean + (HB ? L::O_H : (SPR ? L::O_S : 0)));   // (SPR: A where M is)
     const auto cM = blk.at(L::O_M), cK = blk.at(L::O_K), cB = blk.at(L::O_B), cC = blk.at(L::O_C);
@@ -203,7 +223,10 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     using DT = std::conditional_t<ONE, double, float>;
     DT D[N - 1][NU];
 #pragma unroll
-    for (int m = 0; m < NX; ++m) X[0][m] = active ? (double)P.x0[b * NX + m] : 0.0;
+    for (int m = 0; m < NX; ++m) {
+        if constexpr (WS) X[0][m] = !active ? 0.0 : (P.x0d ? P.x0d[b * NX + m] : (double)P.x0[b * NX + m]);
+        else X[0][m] = active ? (double)P.x0[b * NX + m] : 0.0;
+    }
     if constexpr (HB) {                                                         // x^_0 = T' x0
         double x0[NX];
 #pragma unroll
@@ -228,6 +251,42 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     for (int k = 0; k < N - 1; ++k)
 #pragma unroll
         for (int a = 0; a < NU; ++a) Y[k][a] = (ST)0, Z[k][a] = (ST)0, D[k][a] = (DT)0;
+    if constexpr (WS) {
+        if (!P.cold_start) {                                                    // go on from the kept workspace (admm.cpp:111-115)
+            const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
+            int td = tid;                                                       // (opaque, as at the stores: nothing of the
+            asm volatile("" : "+v"(td));                                        // loads' addressing stays live across the loop)
+            const int ln = td & 63;
+            const long w0 = (long)blockIdx.x * 256 + (td & ~63);
+            float *so = s_stage[td >> 6];
+            if (mask) {
+                if constexpr (XB) {
+                    load_wave_x<EX>(so, P.sg + w0 * EX, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; G[e / NX][e % NX] = val; });
+                    load_wave_x<EX>(so, P.sv + w0 * EX, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; QT[e / NX][e % NX] = val - G[e / NX][e % NX]; });
+                } else {   // v is the trajectory; knot 0 is the new x0 (the kept v_0 is read where it matters: forward)
+                    load_wave_x<EX>(so, P.sv + w0 * EX, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; if constexpr (e >= NX) X[e / NX][e % NX] = (double)val; });
+                    if constexpr (HB) {                                         // x^_k = T' v_k
+#pragma unroll
+                        for (int k = 1; k < N; ++k) {
+                            double vk[NX];
+#pragma unroll
+                            for (int m = 0; m < NX; ++m) vk[m] = X[k][m];
+#pragma unroll
+                            for (int m = 0; m < NX; ++m) {
+                                double acc = P.lean[L::O_T + m] * vk[0];
+#pragma unroll
+                                for (int j = 1; j < NX; ++j) acc = fma(P.lean[L::O_T + j * NX + m], vk[j], acc);
+                                X[k][m] = acc;
+                            }
+                        }
+                    }
+                }
+                load_wave_u<EU>(so, P.sy + w0 * EU, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; Y[e / NU][e % NU] = val; });
+                load_wave_u<EU>(so, P.sz + w0 * EU, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; Z[e / NU][e % NU] = val; });
+                load_wave_u<EU>(so, P.sd + w0 * EU, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; D[e / NU][e % NU] = (DT)val; });
+            }
+        }
+    }
 
 #ifdef TMPC_LEAN_CLOCK_PROBE
     const unsigned long long probe_t0 = __builtin_amdgcn_s_memtime(), probe_r0 = __builtin_amdgcn_s_memrealtime();
@@ -240,6 +299,19 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     const ST ptol = F64 ? (ST)P.abs_pri_tol64 : (ST)P.abs_pri_tol, dtol = F64 ? (ST)P.abs_dua_tol64 : (ST)P.abs_dua_tol;
     double dua_x = 0.0;
     ST pri_u = 0, dua_u = 0, pri_xf = 0, dua_xf = 0;                             // (XB: the state residuals in the slack's own type)
+    // PARK: knot k's previous state slack into the lane's row — whole float4 where nx allows (16-byte writes at a row stride of
+    // an odd number of float4: conflict-free), written as such rather than left to the compiler to merge
+    auto park_v = [&](int k, const float (&pv)[NX]) {
+        float *row = s_pv + tid * PVS + k * NX;
+        if constexpr (NX % 4 == 0) {
+#pragma unroll
+            for (int q = 0; q < NX / 4; ++q)
+                *reinterpret_cast<float4 *>(row + 4 * q) = make_float4(pv[4 * q], pv[4 * q + 1], pv[4 * q + 2], pv[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (int m = 0; m < NX; ++m) row[m] = pv[m];
+        }
+    };
     // XB: knot k's state slack / dual from the rollout's x_k  (admm.cpp:46, 55-58, 68; q~ for :79-80)
     auto state_sets = [&](auto res_tag, auto kk, const double (&x)[NX]) {
         constexpr bool RES = decltype(res_tag)::value;
@@ -250,6 +322,9 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             const ST t = xf + G[k][m];                                          // vnew = x + g
             const ST vn = clamp3(t, (ST)s_xb[k * 2 * NX + m], (ST)s_xb[k * 2 * NX + NX + m]);
             const ST gn = t - vn;                                               // g = g + x - vnew
+            // PARK: the previous v, kept for a converged exit (element by element here: gathered into a float4 of its own the
+            // four values cost this form 12 parked registers; the compiler merges a knot's four writes — tests/test_lean_ws_asm.py)
+            if constexpr (RES && PARK) s_pv[tid * PVS + k * NX + m] = (float)(QT[k][m] + G[k][m]);
             if constexpr (RES) {
                 pri_xf = lean_max(pri_xf, lean_abs(xf - vn));
                 dua_xf = lean_max(dua_xf, lean_abs((QT[k][m] + G[k][m]) - vn)); // v = the previous vnew = q~ + g
@@ -280,7 +355,39 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         constexpr bool RES = decltype(res_tag)::value;
         if constexpr (RES) {
             dua_x = 0.0, pri_u = 0, dua_u = 0, pri_xf = 0, dua_xf = 0;
-            if constexpr (!XB)
+            if constexpr (WS && !XB) {
+                // knot 0: vnew is x0; the previous slack is the workspace's v_0 in the first iteration (zero when cold) and
+                // x0 after any iteration (admm.cpp:94)
+                float v0p[NX];
+#pragma unroll
+                for (int m = 0; m < NX; ++m) v0p[m] = (float)X[0][m];          // (parked by the LIVE kernels only, which are never HB)
+                if (first_iter) {
+                    // (the instance's index opaque here: the address of its v_0 is then formed in this branch, not ahead of the
+                    // iteration loop and kept across it)
+                    int td = tid;
+                    asm volatile("" : "+v"(td));
+                    const long bb = (long)blockIdx.x * 256 + td;
+                    const bool warm0 = bb < P.batch && !P.cold_start;
+                    double x0v[NX];
+                    if constexpr (HB) {
+                        double Tm[NX * NX];                                   // (T from the pack, once per solve at most)
+#pragma unroll
+                        for (int i = 0; i < NX * NX; ++i) Tm[i] = P.lean[L::O_T + i];
+#pragma unroll
+                        for (int m = 0; m < NX; ++m) x0v[m] = to_x(Tm, X[0], m);
+                    } else {
+#pragma unroll
+                        for (int m = 0; m < NX; ++m) x0v[m] = X[0][m];
+                    }
+#pragma unroll
+                    for (int m = 0; m < NX; ++m) {
+                        v0p[m] = warm0 ? P.sv[bb * EX + m] : 0.f;
+                        dua_x = fmax(dua_x, fabs((double)v0p[m] - x0v[m]));
+                    }
+                }
+                if constexpr (PARK) park_v(0, v0p);
+            }
+            if constexpr (!WS && !XB)
                 if (first_iter) {   // cold start: the previous state slack is the zero workspace at knot 0 too, where vnew is x0 (admm.cpp:94)
 #pragma unroll
                     for (int m = 0; m < NX; ++m) {
@@ -398,8 +505,15 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 if constexpr (RES) {
                     pri_u = lean_max(pri_u, lean_abs(uf - zn));                 // (:95)
                     dua_u = lean_max(dua_u, lean_abs(Z[k][a] - zn));            // (:96), times rho at the check
+                    if constexpr (PARK) s_pz[tid * PZS + k * NU + a] = (float)Z[k][a];
                 }
                 Z[k][a] = zn;
+            }
+            if constexpr (RES && PARK && !XB) {                                 // the previous v of knot k + 1, before it is overwritten
+                float pv[NX];
+#pragma unroll
+                for (int m = 0; m < NX; ++m) pv[m] = (float)X[k + 1][m];
+                park_v(k + 1, pv);
             }
 #pragma unroll
             for (int m = 0; m < NX; ++m) {
@@ -533,6 +647,55 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         ro[3] = (float)res3;
     };
 
+    // WS: solution, workspace and status of the lanes in `mask`, through the wavefront's staging.  CV: a converged exit — the
+    // workspace's v, z are the parked previous ones and d is the previous backward pass's; otherwise (exit at max_iter) v, z
+    // are the solution's and d is the backward pass's behind the last iteration (admm.cpp:195-205)
+    auto store_ws = [&](unsigned long long mask, bool mine, auto conv_tag) {
+        constexpr bool CV = decltype(conv_tag)::value;
+        // (the lane's index opaque at each use of the store: left alone the compiler forms every store address once, outside
+        // the iteration loop — the converged exit stores inside it — and spills a hundred registers for them)
+        int td = tid;
+        asm volatile("" : "+v"(td));
+        const int ln = td & 63;
+        const long bb = (long)blockIdx.x * 256 + td;
+        float *so = s_stage[td >> 6];
+        const long w0 = (long)blockIdx.x * 256 + (td & ~63);
+        auto pair = [&](float *xo, float *uo, auto &&gx, auto &&gu) {
+            if constexpr (SW != 0) store_wave_wide<EX, EU, SW>(so, xo, uo, ln, mask, gx, gu);
+            else store_wave_coalesced<EX, EU>(so, xo, uo, ln, mask, gx, gu);
+        };
+        auto single = [&](float *uo, auto &&gu) {
+            if constexpr (SW != 0) {
+                if (mask == ~0ull) store_wave_u_wide<EU>(so, uo, ln, gu);
+                else store_wave_u<EU, false>(so, uo, ln, mask, gu);
+            } else {
+                store_wave_u<EU, false>(so, uo, ln, mask, gu);
+            }
+        };
+        auto getx = [&](auto ee) { constexpr int e = decltype(ee)::value; return vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{}); };
+        auto getu = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Z[e / NU][e % NU]; };
+        auto gety = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Y[e / NU][e % NU]; };
+        auto getd = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)D[e / NU][e % NU]; };
+        pair(P.xout + w0 * EX, P.uout + w0 * EU, getx, getu);
+        if (P.save_state) {
+            if constexpr (CV) {
+                pair(P.sv + w0 * EX, P.sz + w0 * EU, [&](auto ee) { return s_pv[td * PVS + decltype(ee)::value]; },
+                     [&](auto ee) { return s_pz[td * PZS + decltype(ee)::value]; });
+            } else {
+                pair(P.sv + w0 * EX, P.sz + w0 * EU, getx, getu);
+            }
+            if constexpr (XB) pair(P.sg + w0 * EX, P.sy + w0 * EU, [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)G[e / NX][e % NX]; }, gety);
+            else single(P.sy + w0 * EU, gety);
+            single(P.sd + w0 * EU, getd);
+        }
+        if (mine) {
+            float *ro = P.res + bb * 4;
+            P.iter[bb] = P.iter_offset + it;
+            P.solved[bb] = CV ? 1 : 0;
+            ro[0] = (float)res0, ro[1] = (float)res1, ro[2] = (float)res2, ro[3] = (float)res3;
+        }
+    };
+
     // Iterations whose termination check can matter carry the residual arithmetic (every check when the tolerances are
     // positive; otherwise nobody can converge and only the last check's values are ever reported); all others run in a
     // tight loop of their own, so that the two forms of the forward sweep never meet at a join (a join costs a copy per
@@ -565,6 +728,11 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         }
         if constexpr (LIVE) {
             const bool now = active && !conv && res0 < ptol && res2 < ptol && res1 < dtol && res3 < dtol;
+            if constexpr (WS) {                                                 // returns before v = vnew and the backward pass (:181-193)
+                const unsigned long long cm = __builtin_amdgcn_ballot_w64(now);
+                if (cm) store_ws(cm, now, std::true_type{});
+                if (now) conv = 1;
+            } else
             if (now) {                                                          // returns before v = vnew and the backward pass (:181-193)
                 store(true);
                 conv = 1;
@@ -573,7 +741,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         }
         // (after the last iteration its d is never read; the 256-register and state-bounded forms keep the unconditional call:
         // an exit before it costs them 2-50 spilled registers)
-        if (!(ONE && !XB) || i < max_iter) backward();
+        // (WS: a saving solve leaves that d in the workspace, admm.cpp:195-205)
+        if (!(ONE && !XB) || WS || i < max_iter) backward();
     }
     // ---- global status block: wavefront max of the residuals, count of unsolved instances; behind the final store, or
     // (TMPC_LEAN_FOLD_FIRST) ahead of it ----
@@ -609,16 +778,20 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
         if (mask) {
             if constexpr (HB) load_T(Ts);
-            const long w0 = (long)blockIdx.x * 256 + (tid & ~63);          // the wavefront's first instance
-            auto getx = [&](auto ee) { constexpr int e = decltype(ee)::value; return vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{}); };
-            auto getu = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Z[e / NU][e % NU]; };
-            if constexpr (SW != 0) store_wave_wide<EX, EU, SW>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask, getx, getu);
-            else store_wave_coalesced<EX, EU>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask, getx, getu);
-            if (mine) {
-                float *ro = P.res + b * 4;
-                P.iter[b] = P.iter_offset + it;
-                P.solved[b] = 0;
-                ro[0] = (float)res0, ro[1] = (float)res1, ro[2] = (float)res2, ro[3] = (float)res3;
+            if constexpr (WS) {
+                store_ws(mask, mine, std::false_type{});                    // ... and the workspace, when the solve saves it
+            } else {
+                const long w0 = (long)blockIdx.x * 256 + (tid & ~63);      // the wavefront's first instance
+                auto getx = [&](auto ee) { constexpr int e = decltype(ee)::value; return vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{}); };
+                auto getu = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Z[e / NU][e % NU]; };
+                if constexpr (SW != 0) store_wave_wide<EX, EU, SW>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask, getx, getu);
+                else store_wave_coalesced<EX, EU>(s_stage[tid >> 6], P.xout + w0 * EX, P.uout + w0 * EU, lane, mask, getx, getu);
+                if (mine) {
+                    float *ro = P.res + b * 4;
+                    P.iter[b] = P.iter_offset + it;
+                    P.solved[b] = 0;
+                    ro[0] = (float)res0, ro[1] = (float)res1, ro[2] = (float)res2, ro[3] = (float)res3;
+                }
             }
         }
     }

@@ -19,6 +19,7 @@
 //                    rows, other cone rows, another horizon (bindings.cpp:414-490 takes them at run time);
 //   jit_lean_for     at the launch that needs it: ONE variant of the lean kernel (the headline's) for a cartpole-class shape
 //                    without a built-in lean instantiation, and its fp64-state form for precision 2.
+#include <algorithm>
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <spawn.h>
@@ -261,22 +262,50 @@ const ConeEntry *jit_trans_for(const Solver &sv, int verbose) {
 // (A, B) pattern sp (admm_params.h: lean_pattern_rm) — it joins the unit's name.  The kernel holds one lane's
 // whole solve in registers and its coefficients in scalar registers: 32 coefficient doubles and ~490 registers at most —
 // cartpole-class systems ((4,1) to N = 36, (3,2), (2,x)); anything else: nullptr, the quad / stream kernels as before.
+// Whether a workspace-keeping variant (LV_WS) of the shape fits a workgroup's 160 KiB of LDS — what admm_lean.hip.h declares:
+// the four wavefronts' staging (wide_stage_width / wave_stage_floats_wide, admm_quad.hip.h), the per-knot bounds and reference
+// terms, and, tolerance-terminated, every lane's parked previous slack: 256 x (nx N padded to an odd number of float4 +
+// nu (N-1) | 1) floats.  Cartpole-class (4,1): tolerance-terminated to N = 24, fixed-iteration wherever the registers hold it.
+// Asked before a unit is compiled (a compile that cannot succeed costs every process ten seconds) and by the routing
+// (solver.hip: lean_ws_takes), so that such a solver's mpc_rollout keeps the quad kernel's fused loop.
+bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool knot_bounds) {
+    const int EX = nx * N, EU = nu * (N - 1);
+    if (2 * N * nx + 4 * N * nu + 50 > 490) return false;                          // (registers: the 512-register form only)
+    int sw = 0;
+    if (EX % 4 == 0)
+        for (int c = 4; c <= EX && c <= 44; c += 4)
+            if (EX % c == 0) sw = c;
+    const int plain = std::max(64 * 17, 64 * (EU | 1));
+    const int stage = sw ? (std::max(std::max(64 * ((sw / 4) % 2 ? sw : sw + 4), 64 * EU), plain) + 3) / 4 * 4 : plain;
+    const int q = (EX + 3) / 4, pvs = (q % 2 ? q : q + 1) * 4;
+    size_t bytes = (size_t)4 * stage * 4 + (live ? (size_t)256 * (pvs + (EU | 1)) * 4 : 0);
+    bytes += knot_bounds ? (size_t)2 * nu * (N - 1) * 4 : 4;
+    bytes += xb ? (size_t)2 * nx * N * 4 : 4;
+    bytes += shared ? (size_t)8 * (EX + EU + nx) : 24;
+    bytes += (size_t)8 * nx * nx + 256;                                             // T (Hessenberg form), the status fold's words
+    return bytes <= (size_t)160 * 1024;
+}
+
 const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, int verbose) {
     if (std::getenv("TINYMPC_HIP_NO_JIT")) return nullptr;
     if (nx < 1 || nu < 1 || N < 3 || lean_layout(nx, nu).padded > 32) return nullptr;
     if (((variant & LV_SPARSE) != 0) != (sp != 0) || (sp && (nx > 4 || nu > 4))) return nullptr;
     const bool one = (variant & LV_ONE) != 0, f64 = (variant & LV_F64) != 0, xb = (variant & LV_XB) != 0;
-    if (f64 && !one) return nullptr;
+    const bool ws = (variant & LV_WS) != 0;
+    if ((f64 && !one) || (f64 && ws)) return nullptr;
+    if (ws && !lean_ws_fits(nx, nu, N, (variant & LV_LIVE) != 0, xb, (variant & LV_SHARED) != 0, !(variant & LV_UBK))) return nullptr;
     const int regs = f64 ? (xb ? 4 : 2) * N * nx + 6 * N * nu + 50 : 2 * N * nx + (one ? 4 : 3) * N * nu + 50;
     if (regs > (f64 ? 450 : (one ? 490 : 250))) return nullptr;   // (fp64 state with a state bound at N = 20: 490 values, 463 of them spilled)
     std::ostringstream name, src;
     name << "lean_" << nx << "_" << nu << "_" << N << "_v" << variant;
     if (sp) name << "_sp" << std::hex << (unsigned long long)sp << std::dec;
     auto tf = [&](int bit) { return (variant & bit) ? "true" : "false"; };
-    src << "// specialised at the first solve by jit.cpp\n#include \"lean_entry.hip.h\"\nTMPC_DEFINE_LEAN_JIT_ENTRY_SP(\"lean<" << nx << "," << nu << "," << N
-        << (f64 ? ";f64" : "") << ">\", " << nx << ", " << nu << ", " << N << ", " << tf(LV_LIVE) << ", " << tf(LV_UBK) << ", " << tf(LV_ONE) << ", " << tf(LV_XB)
-        << ", " << ((variant & LV_SHARED) ? "tmpc::REF_SHARED" : "tmpc::REF_ZERO") << ", " << (f64 ? "double" : "float") << ", 0x" << std::hex
-        << (unsigned long long)sp << std::dec << "ull)\n";
+    // (LV_WS: the workspace-keeping form has a macro of its own, fp32 state only)
+    src << "// specialised at the first solve by jit.cpp\n#include \"lean_entry.hip.h\"\n" << (ws ? "TMPC_DEFINE_LEAN_JIT_ENTRY_WS" : "TMPC_DEFINE_LEAN_JIT_ENTRY_SP")
+        << "(\"lean<" << nx << "," << nu << "," << N << (f64 ? ";f64" : "") << ">\", " << nx << ", " << nu << ", " << N << ", " << tf(LV_LIVE) << ", " << tf(LV_UBK)
+        << ", " << tf(LV_ONE) << ", " << tf(LV_XB) << ", " << ((variant & LV_SHARED) ? "tmpc::REF_SHARED" : "tmpc::REF_ZERO") << ", ";
+    if (!ws) src << (f64 ? "double" : "float") << ", ";
+    src << "0x" << std::hex << (unsigned long long)sp << std::dec << "ull)\n";
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_units.find(name.str());
     if (it != g_units.end()) return static_cast<const LeanEntry *>(it->second);

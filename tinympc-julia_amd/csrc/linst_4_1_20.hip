@@ -1,5 +1,6 @@
 // lean kernel instantiation for nx=4 nu=1 N=20 (one lane per instance, one-shot solves without an active state bound), with
 // the sparse kernels of the cartpole model's (A, B) pattern (problems.py: cartpole, the benchmark's family) beside it
+// (the workspace-keeping kernels of both kinds come from linst_ws_4_1_20_*.hip and are only declared here)
 #include "lean_entry.hip.h"
 namespace tmpc {
 namespace {
@@ -11,5 +12,5 @@ constexpr double kCartpoleA[16] = {1.0, 0.01, 0.0, 0.0,
                                    0.0, 0.0, 0.458, 1.002};
 constexpr double kCartpoleB[4] = {0.0, 0.02, 0.0, 0.067};
 }  // namespace
-TMPC_DEFINE_LEAN_ENTRY_SP(4, 1, 20, lean_pattern_rm(4, 1, kCartpoleA, kCartpoleB))
+TMPC_DEFINE_LEAN_ENTRY_SP_WS(4, 1, 20, lean_pattern_rm(4, 1, kCartpoleA, kCartpoleB))
 }

@@ -51,11 +51,17 @@ struct LeanEntry {
                        // specialised variant's own (launch); 0: none
     hipError_t (*launch_sparse)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
                                 hipEvent_t ev1) = nullptr;
+    // the workspace-keeping kernels (admm_lean.hip.h, WS: warm starts, kept workspace, the chained closed loop), dense and of
+    // the pattern sp; null: the entry has none (a specialised LV_WS variant carries its one kernel in launch_ws)
+    hipError_t (*launch_ws)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
+                            hipEvent_t ev1) = nullptr;
+    hipError_t (*launch_sparse_ws)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
+                                   hipEvent_t ev1) = nullptr;
 };
 const LeanEntry *find_lean_kernel(int nx, int nu, int N);
 // ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel);
-// LV_SPARSE: on the model's own pattern sp
-enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_COUNT = 128 };
+// LV_SPARSE: on the model's own pattern sp; LV_WS: the workspace-keeping form (fp32 state only)
+enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_WS = 128, LV_COUNT = 256 };
 const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, int verbose);
 // the lean kernel's 512-register form (one wavefront per SIMD): at most one workgroup per CU, tolerance-terminated solves,
 // TINYMPC_HIP_LEAN_ONE (lean_entry.hip.h: launch_lean_v)
@@ -118,6 +124,7 @@ struct Switches {
          no_uni = false, no_os = false, lean_one = false,   // lean_one: TINYMPC_HIP_LEAN_ONE — the lean kernel's 512-register variant at any batch
          no_jit = false,                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
          lean_dense = false,                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
+         lean_ws = false,                                   // TINYMPC_HIP_LEAN_WS: warm / kept-workspace solves and mpc_rollout on the lean kernel
          event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
     int mfmac_debug = 0;    // timing probe builds only
 };
@@ -301,6 +308,7 @@ struct Solver {
     int solve_async(hipStream_t stream, int mpc_steps = 0);
     // one kernel launch over `n_slots` instances (idx: their ids, NULL = 0..n_slots-1) for at most `max_iter_pass`
     // iterations, the instances having done `iter_offset` already
+    bool lean_ws_takes(const int *idx) const;     // TINYMPC_HIP_LEAN_WS: warm / saving solves on the lean kernel (launch_pass)
     int launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n_slots, int iter_offset, int max_iter_pass,
                     bool cold, bool save);
     // tolerance-terminated solves of big batches in chunks of `chunk_iters` iterations: after each chunk the

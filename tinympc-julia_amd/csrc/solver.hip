@@ -350,6 +350,7 @@ Switches read_switches() {
     w.no_os = on("TINYMPC_HIP_NO_OS");
     w.lean_one = on("TINYMPC_HIP_LEAN_ONE");
     w.lean_dense = on("TINYMPC_HIP_LEAN_DENSE");
+    w.lean_ws = on("TINYMPC_HIP_LEAN_WS");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     return w;
@@ -1069,6 +1070,12 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
                            st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0 && st.max_iter > chunk_iters;
     if (chunkable) return solve_chunked(stream);
     if (mpc_steps > 0 && ke && ke->G == 16) return rollout_steps(stream, mpc_steps);
+    // TINYMPC_HIP_LEAN_WS: the closed loop as the same chain of workspace-carrying launches on the lean kernel (plant state in
+    // fp64 between them) instead of the quad kernel's in-kernel loop; per-step reference sequences stay an error outside mfmat
+    if (mpc_steps > 0 && sw.lean_ws && warm_start && ref_seq_steps == 0) {
+        if (packs_dirty && upload_packs()) return -1;   // (the lean entry and its pack are found there)
+        if (lean_ws_takes(nullptr)) return rollout_steps(stream, mpc_steps);
+    }
     return launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, !warm_start, warm_start);
 }
 
@@ -1116,6 +1123,21 @@ int Solver::solve_chunked(hipStream_t stream) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
+}
+
+// Whether the workspace-keeping lean kernels (admm_lean.hip.h, WS; TINYMPC_HIP_LEAN_WS) take this solver's warm / saving
+// solves: a lanes-per-instance entry, fp32 state, a family the lean pack holds, zero or shared references, the family's rho —
+// and a kernel: the one-lane-per-instance entry's built-in ones, or one variant specialised on request where the one-shot
+// solves of the shape get theirs that way (lean_jit, upload_packs; every quad variant keeps the workspace in the same layout)
+// (jit.cpp: registers and LDS of the variant this solver's settings ask for — a shape beyond them stays where it is, its
+// mpc_rollout on the quad kernel's fused loop)
+bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool knot_bounds);
+bool Solver::lean_ws_takes(const int *idx) const {
+    if (!(sw.lean_ws && ke && ke->G < 16 && precision == 0 && lean_ok && !idx && ref_mode != REF_PER_INSTANCE && !st.adaptive_rho)) return false;
+    if (le) return le->launch_ws != nullptr;
+    const bool xb = state_bounds_active || g_maybe_nonzero, shared = ref_mode == REF_SHARED;
+    const bool live = (st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0) || (xb && shared && lean_knot_bounds);
+    return lean_jit && lean_ws_fits(nx, nu, N, live, xb, shared, lean_knot_bounds);
 }
 
 int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n_slots, int iter_offset, int max_iter_pass,
@@ -1239,8 +1261,13 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     // one-shot solves (cold start, nothing of the workspace kept) of a one-lane-per-instance entry, zero or shared references,
     // fp64 recurrences: the lean kernel (same arithmetic, a third fewer instructions)
     const bool lean_f64 = precision == 2 && !ke && lean_jit;
-    const bool lean_call = (ke ? precision == 0 : lean_f64) && lean_ok && cold && !save && mpc_steps == 0 && !idx &&
+    // ... and, with TINYMPC_HIP_LEAN_WS, its workspace-keeping form for every other solve of that kind (lean_ws)
+    const bool lean_ws = !(cold && !save) && lean_ws_takes(idx);
+    const bool lean_call = (ke ? precision == 0 : lean_f64) && lean_ok && ((cold && !save) || lean_ws) && mpc_steps == 0 && !idx &&
                            ref_mode != REF_PER_INSTANCE && !st.adaptive_rho && max_iter_pass >= 1;
+    // the kernels without a state bound take the state dual for zero: a kept workspace whose g may hold something goes to the
+    // state-bounded form (whose clamps then clamp nothing) rather than dropping it
+    const bool lean_xb = state_bounds_active || (lean_ws && g_maybe_nonzero);
     const bool lean_live = st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0;
     const LeanEntry *lk = lean_call ? le : nullptr;
     // the sweeps: the sparse form where a kernel's (A, B) pattern covers the model's and costs less per knot than the dense
@@ -1250,26 +1277,31 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     uint64_t form_sp = 0;
     bool one = false;
     if (lean_call && le) {
-        one = lean_one_form(P.batch, lean_live, sw.lean_one);
-        const bool can = le->launch_sparse && !sw.lean_dense && ref_mode == REF_ZERO && !lean_knot_bounds;
-        form_sp = le->launch_sparse ? le->sp : 0;
-        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, state_bounds_active, can);
+        one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_ws;   // (the WS kernels: the 512-register form only)
+        const bool has_sparse = lean_ws ? le->launch_sparse_ws != nullptr : le->launch_sparse != nullptr;
+        const bool can = has_sparse && !sw.lean_dense && ref_mode == REF_ZERO && !lean_knot_bounds;
+        form_sp = has_sparse ? le->sp : 0;
+        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, lean_xb, can);
     }
     if (lean_call && !le && lean_jit) {
         // the one variant this launch needs (lean_entry.hip.h: launch_lean_v's choices), compiled on first use
-        one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_f64;
+        one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_f64 || lean_ws;
         if (2 * N * nx + 3 * N * nu + 50 > 250) one = true;   // (the 256-register form does not hold this horizon)
         form_sp = lean_sp;
-        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, state_bounds_active, !sw.lean_dense);
-        const int v = (lean_live ? LV_LIVE : 0) | (lean_knot_bounds ? 0 : LV_UBK) | (one ? LV_ONE : 0) | (state_bounds_active ? LV_XB : 0) |
-                      (ref_mode == REF_SHARED ? LV_SHARED : 0) | (lean_f64 ? LV_F64 : 0) | (form == LF_SPARSE ? LV_SPARSE : 0);
+        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, lean_xb, !sw.lean_dense);
+        // (the one WS calling pattern whose fixed-iteration kernel parks a register runs the tolerance-terminated kernel of the
+        // same flags, as the built-in launcher does: lean_entry.hip.h, launch_lean_v)
+        const bool live_v = lean_live || (lean_ws && lean_xb && ref_mode == REF_SHARED && lean_knot_bounds);
+        const int v = (live_v ? LV_LIVE : 0) | (lean_knot_bounds ? 0 : LV_UBK) | (one ? LV_ONE : 0) | (lean_xb ? LV_XB : 0) |
+                      (ref_mode == REF_SHARED ? LV_SHARED : 0) | (lean_f64 ? LV_F64 : 0) | (form == LF_SPARSE ? LV_SPARSE : 0) |
+                      (lean_ws ? LV_WS : 0);
         if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, form == LF_SPARSE ? lean_sp : 0, verbose), le_var_tried[v] = true;
         lk = le_var[v];
     }
     const bool lean = lk != nullptr;
     last_lean_form = lean ? form : LF_NONE;
     last_lean_cost[0] = lean && form_sp ? lean_cost_sparse(form_sp, nx, nu) : 0;
-    last_lean_cost[1] = !lean ? 0 : (one && !lean_live && !state_bounds_active) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
+    last_lean_cost[1] = !lean ? 0 : (one && !lean_live && !lean_xb) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
     if (lean && !le && (!ke || ke->G != 1)) P.bounds = reinterpret_cast<const float *>(d_lean + lean_layout(nx, nu).total);   // (upload_packs)
     P.lean = d_lean;
     P.ws64 = d_ws64;
@@ -1285,8 +1317,8 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     if (profiling && !attached) HIP_TRY(hipEventRecord(ev0, stream));
     if (lean) {
         hipEvent_t a0 = attached ? ev0 : nullptr, a1 = attached ? ev1 : nullptr;
-        if (form == LF_SPARSE && le) HIP_TRY(le->launch_sparse(P, lean_live, lean_knot_bounds, state_bounds_active, stream, a0, a1));
-        else HIP_TRY(lk->launch(P, lean_live, lean_knot_bounds, state_bounds_active, stream, a0, a1));
+        if (form == LF_SPARSE && le) HIP_TRY((lean_ws ? le->launch_sparse_ws : le->launch_sparse)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
+        else HIP_TRY((lean_ws ? lk->launch_ws : lk->launch)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
     } else
     HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
                : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
