@@ -266,7 +266,11 @@ double tinympc_kernel_elapsed_mean_ms(tinympc_solver *s, int last_n);
  * kernels (families whose duals lose digits to fp32 rounding miss 1e-5 there); it is the slowest path of the library —
  * except cold one-shot solves of cartpole-class shapes ((4,1) to N = 30, (3,2), (2,x)), which are launched on the headline
  * kernel's fp64-state variant, compiled on request (csrc/jit.cpp; tinympc_last_launch_name: "lean<...;f64>"): the same
- * digits at that kernel's speed.
+ * digits at that kernel's speed.  With TINYMPC_HIP_STREAM_F64=1 in the environment when the solver is created (off by
+ * default), every other precision-2 solve of a shape that has the stream kernel's fp64-state form — (4,1), (6,3), (12,4);
+ * any horizon, the affine term, cones, linear rows, cold or kept workspace; not adaptive rho, not chunked solves — runs
+ * on that form ("stream4<NX,NU;f64>"): the same digits and iteration counts, 9 to 24 times faster than the generic kernel
+ * on the benchmark shapes (profiles/r09_stream_f64_time.txt).
  * Switching to or from precision 2 restarts the workspace cold.
  * precision = 1 is a request to save time and does NOT meet the 1e-5 parity target on every instance (3 of the 65 536
  * benchmark cartpole instances miss it, worst 1.6e-5).  Where a shape has a matrix-core kernel that kernel is faster than the

@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "admm_generic.hip.h"   // Ws64, the type-generic gmin / gmax / gsqrt / gfma / gupmax
 #include "admm_params.h"
 #include "admm_quad.hip.h"
 
@@ -105,6 +106,31 @@ __device__ __forceinline__ void store_rows(float __attribute__((address_space(1)
     }
 }
 
+// ... and R consecutive doubles (the fp64-state form): 16 bytes where rows pair up, 8 for the odd one (8-byte aligned)
+typedef double sg_d2 __attribute__((ext_vector_type(2)));
+typedef sg_d2 sg_d2u __attribute__((aligned(8)));
+template <int R, int O = 0, int RT_>
+__device__ __forceinline__ void load_rows(const double __attribute__((address_space(1))) * p, double (&dst)[RT_]) {
+    if constexpr (R >= 2) {
+        const sg_d2 v = *(const sg_d2u __attribute__((address_space(1))) *)(p + O);
+        dst[O] = v.x, dst[O + 1] = v.y;
+        load_rows<R - 2, O + 2>(p, dst);
+    } else if constexpr (R == 1) {
+        dst[O] = p[O];
+    }
+}
+template <int R, int O = 0, int RT_>
+__device__ __forceinline__ void store_rows(double __attribute__((address_space(1))) * p, const double (&src)[RT_]) {
+    if constexpr (R >= 2) {
+        sg_d2 v;
+        v.x = src[O], v.y = src[O + 1];
+        *(sg_d2u __attribute__((address_space(1))) *)(p + O) = v;
+        store_rows<R - 2, O + 2>(p, src);
+    } else if constexpr (R == 1) {
+        p[O] = src[O];
+    }
+}
+
 // Coefficient rows of one lane role in the LDS image (CoefLds's role-interleaved 16-byte chunks), any offset
 template <class RT, int G>
 struct CoefRole {
@@ -128,8 +154,8 @@ struct CoefCol {
     __device__ __forceinline__ CoefCol operator+(int off) const { return CoefCol{base + off * stride, stride, lane}; }
 };
 
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
+template <int G, class T>
+__device__ __forceinline__ T group_sum(T v) {
     if constexpr (G >= 2) v += dpp_quad<0xB1>(v);
     if constexpr (G == 4) v += dpp_quad<0x4E>(v);
     return v;
@@ -148,6 +174,15 @@ __device__ __forceinline__ T group_max_t(T v) {
     }
     return v;
 }
+// max over the group of a state-typed value: the quad kernel's DPP form, for either width
+template <int G>
+__device__ __forceinline__ float group_max_s(float m) { return group_max<G>(m); }
+template <int G>
+__device__ __forceinline__ double group_max_s(double m) {
+    if constexpr (G >= 2) m = fmax(m, dpp_quad<0xB1>(m));
+    if constexpr (G == 4) m = fmax(m, dpp_quad<0x4E>(m));
+    return m;
+}
 template <class T>
 __device__ __forceinline__ void upmax_abs(T &m, T v) {
     v = v < (T)0 ? -v : v;
@@ -155,20 +190,20 @@ __device__ __forceinline__ void upmax_abs(T &m, T v) {
 }
 
 // cone c restricted to this lane's R local rows: bit m of head / axis set when local row m belongs to it
-template <int G, int R>
-__device__ __forceinline__ void project_soc_group(float (&blk)[R], unsigned head, unsigned axis, float mu) {
-    float a2 = 0.f, ax = 0.f;
+template <int G, int R, class T>
+__device__ __forceinline__ void project_soc_group(T (&blk)[R], unsigned head, unsigned axis, T mu) {
+    T a2 = (T)0, ax = (T)0;
 #pragma unroll
     for (int m = 0; m < R; ++m) {
-        if ((head >> m) & 1u) a2 = fmaf(blk[m], blk[m], a2);
+        if ((head >> m) & 1u) a2 = gfma(blk[m], blk[m], a2);
         if ((axis >> m) & 1u) ax = blk[m];
     }
     a2 = group_sum<G>(a2);
     ax = group_sum<G>(ax);  // exactly one lane contributes
-    const float an = sqrtf(a2), u0 = ax * mu;
+    const T an = gsqrt(a2), u0 = ax * mu;
     const bool zero = an <= -u0, keep = !zero && an <= u0;
-    const float sc = zero ? 0.f : (keep ? 1.f : 0.5f * (1.f + u0 / an));
-    const float ax_new = zero ? 0.f : (keep ? ax : sc * (an / mu));
+    const T sc = zero ? (T)0 : (keep ? (T)1 : (T)0.5 * ((T)1 + u0 / an));
+    const T ax_new = zero ? (T)0 : (keep ? ax : sc * (an / mu));
 #pragma unroll
     for (int m = 0; m < R; ++m) {
         if ((head >> m) & 1u) blk[m] *= sc;
@@ -178,21 +213,28 @@ __device__ __forceinline__ void project_soc_group(float (&blk)[R], unsigned head
 
 // z <- projection onto {a_k . z <= b_k}, one row after the other; a lane holds its R local entries of each row
 // (rows + k * stride), the dot product is summed over the group, so the branch is uniform within it
-template <int G, int R>
-__device__ __forceinline__ void project_halfspaces_group(float (&z)[R], const float *rows, int stride, int m,
+template <int G, int R, class T>
+__device__ __forceinline__ void project_halfspaces_group(T (&z)[R], const float *rows, int stride, int m,
                                                          const float *b, const float *n2) {
     for (int k = 0; k < m; ++k) {
         const float *a = rows + k * stride;
-        float dot = 0.f;
+        T dot = (T)0;
 #pragma unroll
-        for (int j = 0; j < R; ++j) dot = fmaf(a[j], z[j], dot);
+        for (int j = 0; j < R; ++j) dot = gfma((T)a[j], z[j], dot);
         dot = group_sum<G>(dot);
-        if (dot > b[k]) {
-            const float t = (dot - b[k]) / n2[k];
+        if (dot > (T)b[k]) {
+            const T t = (dot - (T)b[k]) / (T)n2[k];
 #pragma unroll
-            for (int j = 0; j < R; ++j) z[j] -= t * a[j];
+            for (int j = 0; j < R; ++j) z[j] -= t * (T)a[j];
         }
     }
+}
+
+// a workspace array in the state's type: the fp32 array, or its place in the fp64 block (Ws64)
+template <class ST>
+__device__ __forceinline__ ST *ws_sel(float *f32, double *f64) {
+    if constexpr (sizeof(ST) == 8) return f64;
+    else return f32;
 }
 
 // wavefronts per SIMD the register allocation is held to, and knots of prefetch, per group size (MI355X, rocket
@@ -200,6 +242,10 @@ __device__ __forceinline__ void project_halfspaces_group(float (&z)[R], const fl
 template <int G>
 struct StreamTune {
     static constexpr int WAVES = G == 4 ? 3 : (G == 2 ? 2 : 1);
+    // fp64 state: the knot buffers take twice the registers.  Two wavefronts (256 registers) hold every form but the
+    // workspace-keeping ones with cones / linear rows compiled in, whose backward buffer carries w and g of every set:
+    // (12, 4) spills 18 / 91 registers there, so those forms are held to one wavefront (the unified 512-register file)
+    static constexpr int waves64(int ext, bool os) { return (ext > 0 && !os) ? 1 : 2; }
     static constexpr int DEPTH = G == 4 ? 1 : (G == 2 ? 2 : 3);
 };
 #ifndef TMPC_STREAM_DEPTH
@@ -208,14 +254,26 @@ struct StreamTune {
 #ifndef TMPC_STREAM_WAVES
 #define TMPC_STREAM_WAVES(G) StreamTune<G>::WAVES
 #endif
+#ifndef TMPC_STREAM_WAVES64
+#define TMPC_STREAM_WAVES64(G, EXT, OS) StreamTune<G>::waves64(EXT, OS)
+#endif
 
 // ADP: adaptive rho (admm.cpp:147-174 with rho_benchmark.cpp:44-213).  One family for the batch (its rows in LDS), but
 // rho, Kinf and Pinf are every instance's own: the rows built from them (Kinf, Kinf^T, Pinf^T) are read from the lane's
 // column of a scratch matrix that the kernel fills from the solver's adaptive state at entry and re-writes, together
 // with that state, whenever it adapts — every 5th iteration, from norms gathered during that iteration's forward sweep.
-template <int NX, int NU, int G, class RT, int EXT, bool HET, bool OS, bool ADP = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES(G)))) void admm_streamg_kernel(const AdmmParams P) {
+//
+// ST: the type of everything the iteration stores and streams — the scratch arrays, the knot buffers, slacks, duals, the
+// residual maxima and the workspace kept between solves.  float: what precision 0 / 1 carry.  double (precision 2, with
+// RT = double; one family, no adaptive rho): the reference's arithmetic end to end, as the generic kernel's fp64-state form
+// computes it — same values, same order within a row; only the mat-vec sums are ordered by lane — with the workspace in the
+// fp64 block P.ws64 (Ws64) and the tolerances compared in fp64.  Inputs, the LDS image and the outputs are the same fp32 arrays.
+template <int NX, int NU, int G, class RT, int EXT, bool HET, bool OS, bool ADP = false, class ST = float>
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, OS) : TMPC_STREAM_WAVES(G)))) void admm_streamg_kernel(const AdmmParams P) {
     static_assert(!ADP || (!HET && EXT == 0), "adaptive rho: one family, box sets only");
+    static_assert(sizeof(ST) == 4 || (sizeof(RT) == 8 && !HET && !ADP), "fp64 state: fp64 recurrences, one family, fixed rho");
+    constexpr bool WIDE = sizeof(ST) == 8;
     using PK = StreamPackG<NX, NU, G>;
     using S = typename PK::S;
     constexpr int T = 256, D = TMPC_STREAM_DEPTH(G), RX = S::RX, RU = S::RU, NXP = S::NXP, NUP = S::NUP, NXL = S::NXL,
@@ -250,7 +308,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
     const float *lb = s_bnd + q * PK::BW;
 
     float cQD[RX], cRD[RU];
-    float rho = P.rho;
+    ST rho = WIDE ? (ST)P.rho_family : (ST)P.rho;
     if constexpr (HET) {  // per instance: het_aux = [Qd (nx) | Rd (nu) | rho][batch]
 #pragma unroll
         for (int m = 0; m < RX; ++m) cQD[m] = (q * RX + m < NX) ? P.het_aux[(long)(q * RX + m) * B + bb] : 0.f;
@@ -285,7 +343,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
         const double *ad = P.adapt + b;
         if (active) {
             rho_d = ad[0];
-            rho = (float)rho_d;
+            rho = (ST)(float)rho_d;
             RT *mine = adp_cols + L;
 #pragma unroll
             for (int m = 0; m < RU; ++m)
@@ -367,27 +425,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
         const int row = q * RX + m;
         if (row < NX) okx |= 1u << m;
         const int rc = XFULL ? (q < NXL ? q : NXL - 1) * RX : (row < NX ? row : NX - 1);
-        lxo[m] = (unsigned)((bb * NX + rc) * 4);
+        lxo[m] = (unsigned)((bb * NX + rc) * (long)sizeof(ST));
     }
 #pragma unroll
     for (int m = 0; m < RU; ++m) {
         const int row = q * RU + m;
         if (row < NU) oku |= 1u << m;
         const int rc = UFULL ? (q < NUL ? q : NUL - 1) * RU : (row < NU ? row : NU - 1);
-        luo[m] = (unsigned)((bb * NU + rc) * 4);
+        luo[m] = (unsigned)((bb * NU + rc) * (long)sizeof(ST));
     }
-    float *const Sg = P.scratch, *const Sw = Sg + SXN, *const Sv = Sw + SXN;
-    float *const Sy = Sv + SXN, *const Szw = Sy + SUN, *const Sz = Szw + SUN, *const Sd = Sz + SUN;
-    float *const Sgc = Sd + SUN, *const Swc = Sgc + SXN, *const Svc = Swc + SXN;
-    float *const Syc = Svc + SXN, *const Szwc = Syc + SUN, *const Szc = Szwc + SUN;
-    float *const Sgl = Szc + SUN, *const Swl = Sgl + SXN, *const Svl = Swl + SXN;
-    float *const Syl = Svl + SXN, *const Szwl = Syl + SUN, *const Szl = Szwl + SUN;
-    float *const Ss = Sv, *const Ssu = Sz;  // OS: the fused arrays live where v and z would
+    ST *const Sg = reinterpret_cast<ST *>(P.scratch), *const Sw = Sg + SXN, *const Sv = Sw + SXN;
+    ST *const Sy = Sv + SXN, *const Szw = Sy + SUN, *const Sz = Szw + SUN, *const Sd = Sz + SUN;
+    ST *const Sgc = Sd + SUN, *const Swc = Sgc + SXN, *const Svc = Swc + SXN;
+    ST *const Syc = Svc + SXN, *const Szwc = Syc + SUN, *const Szc = Szwc + SUN;
+    ST *const Sgl = Szc + SUN, *const Swl = Sgl + SXN, *const Svl = Swl + SXN;
+    ST *const Syl = Svl + SXN, *const Szwl = Syl + SUN, *const Szl = Szwl + SUN;
+    ST *const Ss = Sv, *const Ssu = Sz;  // OS: the fused arrays live where v and z would
 #define SXP(arr, k, m) lane_elem(sgpr_ptr(arr + ((long)(k)*BNX + (XFULL ? (m) : 0))), lxo[XFULL ? 0 : (m)])
 #define SUP(arr, k, m) lane_elem(sgpr_ptr(arr + ((long)(k)*BNU + (UFULL ? (m) : 0))), luo[UFULL ? 0 : (m)])
 #define OKX(m) (ALLX || (XFULL ? xl : (((okx >> (m)) & 1u) != 0u)))
 #define OKU(m) (ALLU || (UFULL ? ul : (((oku >> (m)) & 1u) != 0u)))
-    auto ldx = [&](float *arr, int k, float (&dst)[RX]) {
+    auto ldx = [&](ST *arr, int k, ST (&dst)[RX]) {
         if constexpr (XFULL) {
             load_rows<RX>(SXP(arr, k, 0), dst);
         } else {
@@ -395,7 +453,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
             for (int m = 0; m < RX; ++m) dst[m] = *SXP(arr, k, m);
         }
     };
-    auto ldu = [&](float *arr, int k, float (&dst)[RU]) {
+    auto ldu = [&](ST *arr, int k, ST (&dst)[RU]) {
         if constexpr (UFULL) {
             load_rows<RU>(SUP(arr, k, 0), dst);
         } else {
@@ -404,7 +462,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
         }
     };
     // stores of one array's rows; the caller has already excluded lanes that own no row (XFULL / UFULL shapes)
-    auto stx = [&](float *arr, int k, const float (&src)[RX]) {
+    auto stx = [&](ST *arr, int k, const ST (&src)[RX]) {
         if constexpr (XFULL) {
             store_rows<RX>(SXP(arr, k, 0), src);
         } else {
@@ -413,7 +471,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                 if (OKX(m)) *SXP(arr, k, m) = src[m];
         }
     };
-    auto stu = [&](float *arr, int k, const float (&src)[RU]) {
+    auto stu = [&](ST *arr, int k, const ST (&src)[RU]) {
         if constexpr (UFULL) {
             store_rows<RU>(SUP(arr, k, 0), src);
         } else {
@@ -422,8 +480,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                 if (OKU(m)) *SUP(arr, k, m) = src[m];
         }
     };
-    auto mkx = [&](float v, int m) __attribute__((always_inline)) { return OKX(m) ? v : 0.f; };
-    auto mku = [&](float v, int m) __attribute__((always_inline)) { return OKU(m) ? v : 0.f; };
+    auto mkx = [&](ST v, int m) __attribute__((always_inline)) { return OKX(m) ? v : (ST)0; };
+    auto mku = [&](ST v, int m) __attribute__((always_inline)) { return OKU(m) ? v : (ST)0; };
     const bool x_owner = ALLX || !XFULL || xl, u_owner = ALLU || !UFULL || ul;
     // One-shot solve without a finite state bound: vnew = x + g is never clamped, so the state dual stays at its
     // cold-start value, zero — it is neither streamed nor computed (bit-identical results).  Plain kernels only: with
@@ -434,24 +492,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
 #pragma unroll
     for (int m = 0; m < RX; ++m) x0[m] = (active && q * RX + m < NX) ? (RT)P.x0[b * NX + q * RX + m] : (RT)0;
     const bool warm = active && !P.cold_start;
+    // the workspace kept between solves: the fp32 arrays, or (fp64 state) the fp64 block, both instance-major
+    const Ws64 w64(P.ws64, B, EX, EU);
+#define WSA(f) ws_sel<ST>(P.f, w64.f)
     if (active) {
         for (int k = 0; k < N; ++k)
 #pragma unroll
             for (int m = 0; m < RX; ++m) {
                 const int row = q * RX + m;
                 if (row >= NX) continue;
-                *SXP(Sg, k, m) = warm ? P.sg[b * EX + k * NX + row] : 0.f;
+                *SXP(Sg, k, m) = warm ? WSA(sg)[b * EX + k * NX + row] : 0.f;
                 *SXP(Sw, k, m) = 0.f;
-                if constexpr (!OS) *SXP(Sv, k, m) = warm ? P.sv[b * EX + k * NX + row] : 0.f;
+                if constexpr (!OS) *SXP(Sv, k, m) = warm ? WSA(sv)[b * EX + k * NX + row] : 0.f;
                 if (soc_x) {
-                    *SXP(Sgc, k, m) = warm ? P.sgc[b * EX + k * NX + row] : 0.f;
+                    *SXP(Sgc, k, m) = warm ? WSA(sgc)[b * EX + k * NX + row] : 0.f;
                     *SXP(Swc, k, m) = 0.f;
-                    if constexpr (!OS) *SXP(Svc, k, m) = warm ? P.svc[b * EX + k * NX + row] : 0.f;
+                    if constexpr (!OS) *SXP(Svc, k, m) = warm ? WSA(svc)[b * EX + k * NX + row] : 0.f;
                 }
                 if (lin_x) {
-                    *SXP(Sgl, k, m) = warm ? P.sgl[b * EX + k * NX + row] : 0.f;
+                    *SXP(Sgl, k, m) = warm ? WSA(sgl)[b * EX + k * NX + row] : 0.f;
                     *SXP(Swl, k, m) = 0.f;
-                    if constexpr (!OS) *SXP(Svl, k, m) = warm ? P.svl[b * EX + k * NX + row] : 0.f;
+                    if constexpr (!OS) *SXP(Svl, k, m) = warm ? WSA(svl)[b * EX + k * NX + row] : 0.f;
                 }
             }
         for (int k = 0; k < N - 1; ++k)
@@ -459,19 +520,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
             for (int m = 0; m < RU; ++m) {
                 const int row = q * RU + m;
                 if (row >= NU) continue;
-                *SUP(Sy, k, m) = warm ? P.sy[b * EU + k * NU + row] : 0.f;
-                *SUP(Sd, k, m) = warm ? P.sd[b * EU + k * NU + row] : 0.f;
+                *SUP(Sy, k, m) = warm ? WSA(sy)[b * EU + k * NU + row] : 0.f;
+                *SUP(Sd, k, m) = warm ? WSA(sd)[b * EU + k * NU + row] : 0.f;
                 *SUP(Szw, k, m) = 0.f;
-                if constexpr (!OS) *SUP(Sz, k, m) = warm ? P.sz[b * EU + k * NU + row] : 0.f;
+                if constexpr (!OS) *SUP(Sz, k, m) = warm ? WSA(sz)[b * EU + k * NU + row] : 0.f;
                 if (soc_u) {
-                    *SUP(Syc, k, m) = warm ? P.syc[b * EU + k * NU + row] : 0.f;
+                    *SUP(Syc, k, m) = warm ? WSA(syc)[b * EU + k * NU + row] : 0.f;
                     *SUP(Szwc, k, m) = 0.f;
-                    if constexpr (!OS) *SUP(Szc, k, m) = warm ? P.szc[b * EU + k * NU + row] : 0.f;
+                    if constexpr (!OS) *SUP(Szc, k, m) = warm ? WSA(szc)[b * EU + k * NU + row] : 0.f;
                 }
                 if (lin_u) {
-                    *SUP(Syl, k, m) = warm ? P.syl[b * EU + k * NU + row] : 0.f;
+                    *SUP(Syl, k, m) = warm ? WSA(syl)[b * EU + k * NU + row] : 0.f;
                     *SUP(Szwl, k, m) = 0.f;
-                    if constexpr (!OS) *SUP(Szl, k, m) = warm ? P.szl[b * EU + k * NU + row] : 0.f;
+                    if constexpr (!OS) *SUP(Szl, k, m) = warm ? WSA(szl)[b * EU + k * NU + row] : 0.f;
                 }
             }
     }
@@ -495,18 +556,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
         res3 = P.res[b * 4 + 3];
     }
     const int ct = P.check_termination;
-    const bool can_converge = P.abs_pri_tol > 0.f && P.abs_dua_tol > 0.f;
+    const bool can_converge = WIDE ? (P.abs_pri_tol64 > 0.0 && P.abs_dua_tol64 > 0.0) : (P.abs_pri_tol > 0.f && P.abs_dua_tol > 0.f);
     const int last_check_it = ct > 0 ? (P.max_iter / ct) * ct : 0;
     // where the previous iteration's vnew / znew are found (dual residual, admm.cpp:93-96)
-    float *const Svold = OS ? Sw : Sv, *const Svcold = OS ? Swc : Svc, *const Szold = OS ? Szw : Sz,
+    ST *const Svold = OS ? Sw : Sv, *const Svcold = OS ? Swc : Svc, *const Szold = OS ? Szw : Sz,
                  *const Szcold = OS ? Szwc : Szc, *const Svlold = OS ? Swl : Svl, *const Szlold = OS ? Szwl : Szl;
 
     // what one knot of the forward / backward sweep reads from the scratch block, D knots ahead of its use
     struct FwdBuf {
-        float g[RX], v[RX], gc[RX], vc[RX], gl[RX], vl[RX], d[RU], y[RU], z[RU], yc[RU], zc[RU], yl[RU], zl[RU];
+        ST g[RX], v[RX], gc[RX], vc[RX], gl[RX], vl[RX], d[RU], y[RU], z[RU], yc[RU], zc[RU], yl[RU], zl[RU];
     };
     struct BwdBuf {  // OS: the fused arrays in w / zw; else all of them
-        float w[RX], g[RX], wc[RX], gc[RX], wl[RX], gl[RX], zw[RU], y[RU], zwc[RU], yc[RU], zwl[RU], yl[RU];
+        ST w[RX], g[RX], wc[RX], gc[RX], wl[RX], gl[RX], zw[RU], y[RU], zwc[RU], yc[RU], zwl[RU], yl[RU];
     };
 
     for (int i = 0; i < P.max_iter; ++i) {
@@ -522,13 +583,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
             RT x[RX];
 #pragma unroll
             for (int m = 0; m < RX; ++m) x[m] = x0[m];
-            float pri_x = 0.f, dua_x = 0.f, pri_u = 0.f, dua_u = 0.f;
+            ST pri_x = (ST)0, dua_x = (ST)0, pri_u = (ST)0, dua_u = (ST)0;
             // adaptive rho: the iterations that adapt (admm.cpp:147) gather the norms of rho_benchmark.cpp:44-213 on the
             // way — constraint rows [u_k; A x_k + B u_k (+ f) - x_{k+1}] against [znew_k; vnew_{k+1}], cost rows
             // P x + q + A'y with P = blkdiag(Q~, R~, .., Pinf), q = [Q~ x; R~ u] (zero reference), y = [y_k; g_{k+1}] —
             // each knot contributing the rows of knot k - 1 that needed its new dual g_k.
             const bool adapt_now = ADP && i > 0 && i % 5 == 0;
-            const float rho_lin = rho;   // the linear cost of this iteration is formed before the adaptation (admm.cpp:139 vs :147)
+            const ST rho_lin = rho;   // the linear cost of this iteration is formed before the adaptation (admm.cpp:139 vs :147)
             RT a_pri = 0, a_axm = 0, a_zm = 0, a_dres = 0, a_pxm = 0, a_atym = 0, a_qm = 0;
             RT a_xp[RX];
             float a_gp[RX], a_up[RU], a_yp[RU];              // knot k - 1: x, new g, u, new y
@@ -541,10 +602,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
             for (int j = 0; j < D; ++j) {
 #pragma unroll
                 for (int m = 0; m < RX; ++m)
-                    fb[j].g[m] = fb[j].v[m] = fb[j].gc[m] = fb[j].vc[m] = fb[j].gl[m] = fb[j].vl[m] = 0.f;
+                    fb[j].g[m] = fb[j].v[m] = fb[j].gc[m] = fb[j].vc[m] = fb[j].gl[m] = fb[j].vl[m] = (ST)0;
 #pragma unroll
                 for (int m = 0; m < RU; ++m)
-                    fb[j].d[m] = fb[j].y[m] = fb[j].z[m] = fb[j].yc[m] = fb[j].zc[m] = fb[j].yl[m] = fb[j].zl[m] = 0.f;
+                    fb[j].d[m] = fb[j].y[m] = fb[j].z[m] = fb[j].yc[m] = fb[j].zc[m] = fb[j].yl[m] = fb[j].zl[m] = (ST)0;
             }
             auto fetch_x = [&](int k_, FwdBuf &f) __attribute__((always_inline)) {
                 const int k = knot_sgpr(k_);
@@ -578,15 +639,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                 const int k = knot_sgpr(k_);
                 const bool pf = k + D < N;  // this knot's buffer is refilled for knot k + D once consumed
                 const float *bk = lb + k * G * PK::BW;
-                float xf[RX], vn[RX], gn[RX], wc[RX], gcn[RX], wl[RX], gln[RX], sx[RX];
+                ST xf[RX], vn[RX], gn[RX], wc[RX], gcn[RX], wl[RX], gln[RX], sx[RX];
 #pragma unroll
                 for (int m = 0; m < RX; ++m) {
-                    const float g_c = nog ? 0.f : mkx(f.g[m], m), v_c = mkx(f.v[m], m);
-                    xf[m] = (float)x[m];
-                    vn[m] = fminf(bk[RX + m], fmaxf(bk[m], xf[m] + g_c));
+                    const ST g_c = nog ? (ST)0 : mkx(f.g[m], m), v_c = mkx(f.v[m], m);
+                    xf[m] = (ST)x[m];
+                    vn[m] = gmin((ST)bk[RX + m], gmax((ST)bk[m], xf[m] + g_c));
                     gn[m] = (g_c + xf[m]) - vn[m];
-                    pri_x = fmaxf(pri_x, fabsf(xf[m] - vn[m]));
-                    dua_x = fmaxf(dua_x, fabsf(v_c - vn[m]));
+                    gupmax(pri_x, xf[m] - vn[m]);
+                    gupmax(dua_x, v_c - vn[m]);
                     sx[m] = vn[m] - gn[m];
                 }
                 if constexpr (EXT) {
@@ -595,13 +656,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                         for (int m = 0; m < RX; ++m) wc[m] = xf[m] + mkx(f.gc[m], m);
                         for (int c = 0; c < ncx; ++c) {
                             const uint4 mk = cm[c * G];
-                            project_soc_group<G, RX>(wc, mk.x, mk.y, P.cx[c]);
+                            project_soc_group<G, RX>(wc, mk.x, mk.y, (ST)P.cx[c]);
                         }
 #pragma unroll
                         for (int m = 0; m < RX; ++m) {
                             gcn[m] = (mkx(f.gc[m], m) + xf[m]) - wc[m];
-                            pri_x = fmaxf(pri_x, fabsf(xf[m] - wc[m]));
-                            dua_x = fmaxf(dua_x, fabsf(mkx(f.vc[m], m) - wc[m]));
+                            gupmax(pri_x, xf[m] - wc[m]);
+                            gupmax(dua_x, mkx(f.vc[m], m) - wc[m]);
                             sx[m] += wc[m] - gcn[m];
                         }
                     }
@@ -614,8 +675,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
 #pragma unroll
                         for (int m = 0; m < RX; ++m) {
                             gln[m] = (mkx(f.gl[m], m) + xf[m]) - wl[m];
-                            pri_x = fmaxf(pri_x, fabsf(xf[m] - wl[m]));
-                            dua_x = fmaxf(dua_x, fabsf(mkx(f.vl[m], m) - wl[m]));
+                            gupmax(pri_x, xf[m] - wl[m]);
+                            gupmax(dua_x, mkx(f.vl[m], m) - wl[m]);
                             sx[m] += wl[m] - gln[m];
                         }
                     }
@@ -690,7 +751,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                 if (pf) fetch_x(k + D, f);
                 if (k < N - 1) {
                     RT u[RU], xn[RX];
-                    float uf[RU], zn[RU], yn[RU], zc2[RU], ycn[RU], zl2[RU], yln[RU], su[RU];
+                    ST uf[RU], zn[RU], yn[RU], zc2[RU], ycn[RU], zl2[RU], yln[RU], su[RU];
 #pragma unroll
                     for (int m = 0; m < RU; ++m) u[m] = -(RT)mku(f.d[m], m);
 #pragma unroll
@@ -702,12 +763,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     asm volatile("" ::: "memory");
 #pragma unroll
                     for (int m = 0; m < RU; ++m) {
-                        const float y_c = mku(f.y[m], m);
-                        uf[m] = (float)u[m];
-                        zn[m] = fminf(bk[2 * RX + RU + m], fmaxf(bk[2 * RX + m], uf[m] + y_c));
+                        const ST y_c = mku(f.y[m], m);
+                        uf[m] = (ST)u[m];
+                        zn[m] = gmin((ST)bk[2 * RX + RU + m], gmax((ST)bk[2 * RX + m], uf[m] + y_c));
                         yn[m] = (y_c + uf[m]) - zn[m];
-                        pri_u = fmaxf(pri_u, fabsf(uf[m] - zn[m]));
-                        dua_u = fmaxf(dua_u, fabsf(mku(f.z[m], m) - zn[m]));
+                        gupmax(pri_u, uf[m] - zn[m]);
+                        gupmax(dua_u, mku(f.z[m], m) - zn[m]);
                         su[m] = zn[m] - yn[m];
                     }
                     if constexpr (EXT) {
@@ -716,13 +777,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                             for (int m = 0; m < RU; ++m) zc2[m] = uf[m] + mku(f.yc[m], m);
                             for (int c = 0; c < ncu; ++c) {
                                 const uint4 mk = cm[c * G];
-                                project_soc_group<G, RU>(zc2, mk.z, mk.w, P.cu[c]);
+                                project_soc_group<G, RU>(zc2, mk.z, mk.w, (ST)P.cu[c]);
                             }
 #pragma unroll
                             for (int m = 0; m < RU; ++m) {
                                 ycn[m] = (mku(f.yc[m], m) + uf[m]) - zc2[m];
-                                pri_u = fmaxf(pri_u, fabsf(uf[m] - zc2[m]));
-                                dua_u = fmaxf(dua_u, fabsf(mku(f.zc[m], m) - zc2[m]));
+                                gupmax(pri_u, uf[m] - zc2[m]);
+                                gupmax(dua_u, mku(f.zc[m], m) - zc2[m]);
                                 su[m] += zc2[m] - ycn[m];
                             }
                         }
@@ -736,8 +797,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
 #pragma unroll
                             for (int m = 0; m < RU; ++m) {
                                 yln[m] = (mku(f.yl[m], m) + uf[m]) - zl2[m];
-                                pri_u = fmaxf(pri_u, fabsf(uf[m] - zl2[m]));
-                                dua_u = fmaxf(dua_u, fabsf(mku(f.zl[m], m) - zl2[m]));
+                                gupmax(pri_u, uf[m] - zl2[m]);
+                                gupmax(dua_u, mku(f.zl[m], m) - zl2[m]);
                                 su[m] += zl2[m] - yln[m];
                             }
                         }
@@ -841,16 +902,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     }
                     if (q == 0) ad[0] = (double)nrho;
                     rho_d = (double)nrho;
-                    rho = (float)nrho;
+                    rho = (ST)(float)nrho;
                 }
             }
             if (need_res) {
-                res0 = group_max<G>(pri_x);
-                res1 = group_max<G>(dua_x) * rho;
-                res2 = group_max<G>(pri_u);
-                res3 = group_max<G>(dua_u) * rho;
-                if (res0 < P.abs_pri_tol && res2 < P.abs_pri_tol && res1 < P.abs_dua_tol && res3 < P.abs_dua_tol)
-                    conv = 1;
+                if constexpr (WIDE) {
+                    // fp64 state compares what the reference compares: fp64 residuals against the fp64 tolerances (admm.cpp:99-103)
+                    const ST r0 = group_max_s<G>(pri_x), r1 = group_max_s<G>(dua_x) * rho, r2 = group_max_s<G>(pri_u),
+                             r3 = group_max_s<G>(dua_u) * rho;
+                    res0 = (float)r0, res1 = (float)r1, res2 = (float)r2, res3 = (float)r3;
+                    if (r0 < P.abs_pri_tol64 && r2 < P.abs_pri_tol64 && r1 < P.abs_dua_tol64 && r3 < P.abs_dua_tol64) conv = 1;
+                } else {
+                    res0 = group_max<G>(pri_x);
+                    res1 = group_max<G>(dua_x) * rho;
+                    res2 = group_max<G>(pri_u);
+                    res3 = group_max<G>(dua_u) * rho;
+                    if (res0 < P.abs_pri_tol && res2 < P.abs_pri_tol && res1 < P.abs_dua_tol && res3 < P.abs_dua_tol)
+                        conv = 1;
+                }
             }
             if (!conv) {
                 // ================= fused backward sweep (admm.cpp:75-83, :196-197, :13-20) =================
@@ -891,7 +960,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     }
                 };
                 // consume the state-shaped part of a buffer: returns rho-less (vnew - g [+ cone set]) per row
-                auto take_x = [&](int k, BwdBuf &f, float (&sx)[RX]) {
+                auto take_x = [&](int k, BwdBuf &f, ST (&sx)[RX]) {
                     if constexpr (OS) {
 #pragma unroll
                         for (int m = 0; m < RX; ++m) sx[m] = mkx(f.w[m], m);
@@ -909,7 +978,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                         }
                     }
                 };
-                auto take_u = [&](int k, BwdBuf &f, float (&su)[RU]) {
+                auto take_u = [&](int k, BwdBuf &f, ST (&su)[RU]) {
                     if constexpr (OS) {
 #pragma unroll
                         for (int m = 0; m < RU; ++m) su[m] = mku(f.zw[m], m);
@@ -947,7 +1016,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                         for (int m = 0; m < RX; ++m) xrl[m] = (RT)ref_x(N - 1, m);
                         quad_matvec<G, RX, NXL, RX, NXP>(acc, cPT, xrl);
                     }
-                    float sx[RX];
+                    ST sx[RX];
                     take_x(N - 1, bterm, sx);
 #pragma unroll
                     for (int m = 0; m < RX; ++m) p[m] = -acc[m] - (RT)(rho_lin * sx[m]);
@@ -957,19 +1026,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     const int t = knot_sgpr(t_);
                     const int k = N - 2 - t;
                     RT r[RU], qk[RX];
-                    float sx[RX], su[RU];
+                    ST sx[RX], su[RU];
                     take_x(k, f, sx);
                     take_u(k, f, su);
 #pragma unroll
-                    for (int m = 0; m < RU; ++m) r[m] = (RT)(-(ref_u(k, m) * cRD[m]) - rho_lin * su[m]);
+                    for (int m = 0; m < RU; ++m) r[m] = (RT)(-((ST)ref_u(k, m) * (ST)cRD[m]) - rho_lin * su[m]);
 #pragma unroll
-                    for (int m = 0; m < RX; ++m) qk[m] = (RT)(-(ref_x(k, m) * cQD[m]) - rho_lin * sx[m]);
+                    for (int m = 0; m < RX; ++m) qk[m] = (RT)(-((ST)ref_x(k, m) * (ST)cQD[m]) - rho_lin * sx[m]);
                     if (t + D < N - 1) {
                         fetchb_x(k - D, f);
                         fetchb_u(k - D, f);
                     }
                     RT tt[RU], dn[RU], ap[RX];
-                    float dnf[RU];
+                    ST dnf[RU];
 #pragma unroll
                     for (int m = 0; m < RU; ++m) {
                         tt[m] = r[m] + (EXT ? (RT)cBPF[m] : (RT)0);
@@ -980,7 +1049,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     asm volatile("" ::: "memory");
                     quad_matvec<G, RU, NUL, RU, NUP>(dn, cQI, tt);  // d = Quu_inv (...)
 #pragma unroll
-                    for (int m = 0; m < RU; ++m) dnf[m] = (float)dn[m];
+                    for (int m = 0; m < RU; ++m) dnf[m] = (ST)dn[m];
                     if (u_owner) stu(Sd, k, dnf);
 #pragma unroll
                     for (int m = 0; m < RX; ++m) ap[m] = qk[m] + (EXT ? (RT)cAPF[m] : (RT)0);
@@ -1005,11 +1074,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
         for (int k = 0; k < N; ++k)
 #pragma unroll
             for (int m = 0; m < RX; ++m)
-                if (q * RX + m < NX) P.xout[b * EX + k * NX + q * RX + m] = *SXP(Sw, k, m);
+                if (q * RX + m < NX) P.xout[b * EX + k * NX + q * RX + m] = (float)*SXP(Sw, k, m);
         for (int k = 0; k < N - 1; ++k)
 #pragma unroll
             for (int m = 0; m < RU; ++m)
-                if (q * RU + m < NU) P.uout[b * EU + k * NU + q * RU + m] = *SUP(Szw, k, m);
+                if (q * RU + m < NU) P.uout[b * EU + k * NU + q * RU + m] = (float)*SUP(Szw, k, m);
         if (q == 0) {
             P.iter[b] = P.iter_offset + it;
             P.solved[b] = conv;
@@ -1025,15 +1094,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     for (int m = 0; m < RX; ++m) {
                         const int row = q * RX + m;
                         if (row < NX) {
-                            P.sg[b * EX + k * NX + row] = *SXP(Sg, k, m);
-                            P.sv[b * EX + k * NX + row] = *SXP(Sv, k, m);
+                            WSA(sg)[b * EX + k * NX + row] = *SXP(Sg, k, m);
+                            WSA(sv)[b * EX + k * NX + row] = *SXP(Sv, k, m);
                             if (soc_x) {
-                                P.sgc[b * EX + k * NX + row] = *SXP(Sgc, k, m);
-                                P.svc[b * EX + k * NX + row] = *SXP(Svc, k, m);
+                                WSA(sgc)[b * EX + k * NX + row] = *SXP(Sgc, k, m);
+                                WSA(svc)[b * EX + k * NX + row] = *SXP(Svc, k, m);
                             }
                             if (lin_x) {
-                                P.sgl[b * EX + k * NX + row] = *SXP(Sgl, k, m);
-                                P.svl[b * EX + k * NX + row] = *SXP(Svl, k, m);
+                                WSA(sgl)[b * EX + k * NX + row] = *SXP(Sgl, k, m);
+                                WSA(svl)[b * EX + k * NX + row] = *SXP(Svl, k, m);
                             }
                         }
                     }
@@ -1042,22 +1111,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM
                     for (int m = 0; m < RU; ++m) {
                         const int row = q * RU + m;
                         if (row < NU) {
-                            P.sy[b * EU + k * NU + row] = *SUP(Sy, k, m);
-                            P.sz[b * EU + k * NU + row] = *SUP(Sz, k, m);
-                            P.sd[b * EU + k * NU + row] = *SUP(Sd, k, m);
+                            WSA(sy)[b * EU + k * NU + row] = *SUP(Sy, k, m);
+                            WSA(sz)[b * EU + k * NU + row] = *SUP(Sz, k, m);
+                            WSA(sd)[b * EU + k * NU + row] = *SUP(Sd, k, m);
                             if (soc_u) {
-                                P.syc[b * EU + k * NU + row] = *SUP(Syc, k, m);
-                                P.szc[b * EU + k * NU + row] = *SUP(Szc, k, m);
+                                WSA(syc)[b * EU + k * NU + row] = *SUP(Syc, k, m);
+                                WSA(szc)[b * EU + k * NU + row] = *SUP(Szc, k, m);
                             }
                             if (lin_u) {
-                                P.syl[b * EU + k * NU + row] = *SUP(Syl, k, m);
-                                P.szl[b * EU + k * NU + row] = *SUP(Szl, k, m);
+                                WSA(syl)[b * EU + k * NU + row] = *SUP(Syl, k, m);
+                                WSA(szl)[b * EU + k * NU + row] = *SUP(Szl, k, m);
                             }
                         }
                     }
             }
         }
     }
+#undef WSA
 #undef SXP
 #undef SUP
 #undef OKX

@@ -3,5 +3,5 @@
 namespace tmpc {
 TMPC_DEFINE_STREAMG_ENTRY(3, 2, 4)
 TMPC_DEFINE_STREAMG_ENTRY(3, 3, 4)
-TMPC_DEFINE_STREAMG_ENTRY(4, 1, 4)
+TMPC_DEFINE_STREAMG_ENTRY_F64(4, 1, 4)
 }

@@ -3,5 +3,5 @@
 namespace tmpc {
 TMPC_DEFINE_STREAMG_ENTRY(6, 1, 4)
 TMPC_DEFINE_STREAMG_ENTRY(6, 2, 4)
-TMPC_DEFINE_STREAMG_ENTRY(6, 3, 4)
+TMPC_DEFINE_STREAMG_ENTRY_F64(6, 3, 4)
 }

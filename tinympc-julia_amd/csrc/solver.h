@@ -91,6 +91,10 @@ struct StreamEntry {
     size_t (*lds_bytes)(int N, int precision);
     size_t (*scratch_floats)(int N, int sets);  // per instance; sets: 1 box, 2 + cones, 3 + linear
     hipError_t (*launch)(const AdmmParams &, int precision, int ext, bool het, hipStream_t);  // ext: 0 | 1 fdyn, cones | 2 + linear
+    // the fp64-state form (precision 2: scratch, knot buffers, duals and the kept workspace in doubles; one family, fixed
+    // rho) and the name it reports, "stream4<NX,NU;f64>" — both null where the form is not built (sinst_f64_*.hip)
+    hipError_t (*launch_f64)(const AdmmParams &, int ext, hipStream_t) = nullptr;
+    const char *name_f64 = nullptr;
 };
 const StreamEntry *find_stream_kernel(int nx, int nu);
 // One (nx, nu) instantiation of the LDS-resident matrix-core kernel with a run-time horizon (admm_mfmac.hip.h):
@@ -125,6 +129,7 @@ struct Switches {
          no_jit = false,                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
          lean_dense = false,                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
          lean_ws = false,                                   // TINYMPC_HIP_LEAN_WS: warm / kept-workspace solves and mpc_rollout on the lean kernel
+         stream_f64 = false,                                // TINYMPC_HIP_STREAM_F64: precision 2 on the stream kernel's fp64-state form where it is built
          event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
     int mfmac_debug = 0;    // timing probe builds only
 };
@@ -254,7 +259,7 @@ struct Solver {
     static constexpr int EV_RING = 256;  // event pairs around the most recent launches (profiling mode)
     std::vector<hipEvent_t> ev_ring;     // [2 * EV_RING], created on first use
     long launches = 0;                   // launches recorded since profiling was switched on
-    int precision = 0;  // 0: fp64 recurrences, fp32 state (default), 1: all fp32, 2: all fp64 (generic kernel)
+    int precision = 0;  // 0: fp64 recurrences, fp32 state (default), 1: all fp32, 2: all fp64 (lean / stream / generic kernel's fp64-state form)
 
     int ex() const { return nx * N; }
     int eu() const { return nu * (N - 1); }
@@ -283,6 +288,7 @@ struct Solver {
     const KernelEntry *route_quad(bool rollout) const;
     const KernelEntry *route_mfma(bool rollout, const KernelEntry *quad) const;
     const StreamEntry *route_stream() const;
+    const StreamEntry *route_stream_f64() const;   // precision 2, TINYMPC_HIP_STREAM_F64
     const ConeEntry *route_cone(bool rollout, bool have_quad, bool have_stream) const;
     const ConeEntry *route_trans(bool rollout, const ConeEntry *oneshot) const;
     std::vector<long> routing_key(bool rollout) const;

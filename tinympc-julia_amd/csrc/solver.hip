@@ -351,6 +351,7 @@ Switches read_switches() {
     w.lean_one = on("TINYMPC_HIP_LEAN_ONE");
     w.lean_dense = on("TINYMPC_HIP_LEAN_DENSE");
     w.lean_ws = on("TINYMPC_HIP_LEAN_WS");
+    w.stream_f64 = on("TINYMPC_HIP_STREAM_F64");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     return w;
@@ -413,6 +414,18 @@ const StreamEntry *Solver::route_stream() const {
     const StreamEntry *s2 = find_stream_kernel(nx, nu);
     if (s2 && 16.0 * batch * std::max(nx, nu) >= 4.0e9) s2 = nullptr;   // 32-bit lane byte offsets into one knot's rows
     if (s2 && s2->lds_bytes(N, precision) > 150 * 1024) s2 = nullptr;   // LDS image of coefficients + bounds
+    return s2;
+}
+
+// precision 2 with TINYMPC_HIP_STREAM_F64: the stream kernel's fp64-state form where the shape has one — any horizon, the
+// affine term, cones, linear rows, cold or kept workspace.  One family, fixed rho, the whole batch in one launch (no
+// chunks): everything else stays on the generic kernel's fp64-state form.
+const StreamEntry *Solver::route_stream_f64() const {
+    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0) return nullptr;
+    const StreamEntry *s2 = find_stream_kernel(nx, nu);
+    if (!s2 || !s2->launch_f64) return nullptr;
+    if (32.0 * batch * std::max(nx, nu) >= 4.0e9) return nullptr;   // 32-bit lane byte offsets, 8-byte elements
+    if (s2->lds_bytes(N, 2) > 150 * 1024) return nullptr;
     return s2;
 }
 
@@ -483,7 +496,7 @@ int Solver::select_kernel(bool rollout) {
         set_error("adaptive_rho is not available on a per-instance-family solver");
         return -1;
     }
-    if (precision == 2) {   // fp64 end to end: the generic kernel's double-state form, whatever the shape
+    if (precision == 2) {   // fp64 end to end: the stream kernel's fp64-state form (route_stream_f64), else the generic kernel's, whatever the shape
         if (hetero || rollout) {
             set_error(hetero ? "precision 2 is not available on a per-instance-family solver" : "precision 2 has no fused closed loop (step it from the host)");
             return -1;
@@ -492,10 +505,11 @@ int Solver::select_kernel(bool rollout) {
             set_error("problem shape exceeds the generic kernel limits (nx <= 64, nu <= 32)");
             return -1;
         }
-        if (ke || se || ce) packs_dirty = true;
-        ke = nullptr, se = nullptr, ce = nullptr;
+        const StreamEntry *s2 = route_stream_f64();
+        if (ke || ce || s2 != se) packs_dirty = true;
+        ke = nullptr, se = s2, ce = nullptr;
         rollout_quad = false;
-        kernel_name = "generic<f64>";
+        kernel_name = se ? se->name_f64 : "generic<f64>";
         routed_key = std::move(key);
         routed = true;
         return 0;
@@ -665,7 +679,8 @@ int Solver::upload_packs() {
     lean_jit = !le && ke && lean_enabled && !sw.no_jit && !no_specialise && (ke->G == 1 || (ke->jit && ke->G < 16 && batch >= 20480));
     // precision 2 (the generic kernel's fp64-state form, one lane per instance like this one): one-shot solves of a shape the lean
     // kernel holds run on ITS fp64-state form, specialised on request — the reference's digits at the headline kernel's speed
-    if (precision == 2 && !ke && !se && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise) lean_jit = true;
+    // (`se` at precision 2 is the stream kernel's fp64-state form: it takes what the lean kernel leaves)
+    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise) lean_jit = true;
     std::fill(le_var_tried, le_var_tried + LV_COUNT, false);
     lean_ok = false;
     lean_sp = lean_pattern(A, B);
@@ -982,7 +997,7 @@ int Solver::ensure_extension_buffers() {
             ws64_cap = w;
         }
     }
-    if (se) need = std::max(need, Bn * se->scratch_floats(N, (int)sets));
+    if (se) need = std::max(need, Bn * se->scratch_floats(N, (int)sets) * (precision == 2 ? 2 : 1));   // (fp64 state: doubles)
     if (ce) need = ce->scratch_floats(*this);
     if (scratch_cap < need) {
         if (dev_alloc(d_scratch, need)) return -1;
@@ -1260,7 +1275,9 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     const bool carry_g = state_bounds_active || (ke && ke->G == 16 && g_maybe_nonzero);
     // one-shot solves (cold start, nothing of the workspace kept) of a one-lane-per-instance entry, zero or shared references,
     // fp64 recurrences: the lean kernel (same arithmetic, a third fewer instructions)
-    const bool lean_f64 = precision == 2 && !ke && lean_jit;
+    // (behind the stream kernel's fp64-state form the lean kernel is asked launch by launch: constraints added since the packs
+    // were built go to the stream kernel's EXT forms)
+    const bool lean_f64 = precision == 2 && !ke && lean_jit && !(se && extensions_active());
     // ... and, with TINYMPC_HIP_LEAN_WS, its workspace-keeping form for every other solve of that kind (lean_ws)
     const bool lean_ws = !(cold && !save) && lean_ws_takes(idx);
     const bool lean_call = (ke ? precision == 0 : lean_f64) && lean_ok && ((cold && !save) || lean_ws) && mpc_steps == 0 && !idx &&
@@ -1322,7 +1339,8 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     } else
     HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
                : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
-                     : (se ? se->launch(P, precision, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), hetero, stream)
+                     : (se ? (precision == 2 ? se->launch_f64(P, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), stream)
+                                             : se->launch(P, precision, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), hetero, stream))
                            : launch_generic(P, precision, stream))));
     if (profiling) {
         if (!attached) HIP_TRY(hipEventRecord(ev1, stream));

@@ -81,7 +81,7 @@ void fill_streamg_coef(const Solver &sv, std::vector<unsigned char> &out) {
 
 template <int NX, int NU, int G>
 void build_streamg_coef(const Solver &sv, std::vector<unsigned char> &out) {
-    if (sv.precision == 0)
+    if (sv.precision != 1)   // (precision 2, the fp64-state form: fp64 rows like precision 0)
         fill_streamg_coef<NX, NU, G, double>(sv, out);
     else
         fill_streamg_coef<NX, NU, G, float>(sv, out);
@@ -121,12 +121,12 @@ void build_streamg_bounds(const Solver &sv, std::vector<float> &out) {
 template <int NX, int NU, int G>
 size_t streamg_lds_bytes(int N, int precision) {
     using PK = StreamPackG<NX, NU, G>;
-    const size_t rt = precision == 0 ? 8 : 4;
+    const size_t rt = precision != 1 ? 8 : 4;
     return rt * G * PK::CP + 4 * ((size_t)N * G * PK::BW + G * PK::DW);
 }
 
 // floats of scratch per instance: 3 state-shaped and 3 input-shaped arrays per constraint set (box | + cones |
-// + linear inequalities), + d
+// + linear inequalities), + d (the fp64-state form: as many doubles)
 template <int NX, int NU>
 size_t streamg_scratch_floats(int N, int sets) {
     return (size_t)NX * N * (3 * sets) + (size_t)NU * (N - 1) * (3 * sets + 1);
@@ -181,6 +181,48 @@ hipError_t launch_streamg(const AdmmParams &P, int precision, int ext, bool het,
 #undef TMPC_LAUNCH
     return hipGetLastError();
 }
+
+// The fp64-state form (ST = double): RT = double, one family, fixed rho; EXT x OS, six kernels per (nx, nu).
+template <int NX, int NU, int G>
+hipError_t launch_streamg_f64(const AdmmParams &P, int ext, hipStream_t stream) {
+    const int grid = (P.batch + 256 / G - 1) / (256 / G);
+    const size_t lds = streamg_lds_bytes<NX, NU, G>(P.N, 2);
+    const bool oneshot = P.cold_start && !P.save_state;
+#define TMPC_LAUNCH(EXT_, OS_)                                                                                          \
+    do {                                                                                                                \
+        if (lds > 48 * 1024)                                                                                            \
+            (void)hipFuncSetAttribute((const void *)admm_streamg_kernel<NX, NU, G, double, EXT_, false, OS_, false, double>, \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
+        hipLaunchKernelGGL((admm_streamg_kernel<NX, NU, G, double, EXT_, false, OS_, false, double>), dim3(grid), dim3(256), \
+                           lds, stream, P);                                                                             \
+    } while (0)
+#define TMPC_LAUNCH_OS(EXT_)                                                   \
+    do {                                                                       \
+        if (oneshot) TMPC_LAUNCH(EXT_, true); else TMPC_LAUNCH(EXT_, false);   \
+    } while (0)
+    if (ext == 2) TMPC_LAUNCH_OS(2);
+    else if (ext == 1) TMPC_LAUNCH_OS(1);
+    else TMPC_LAUNCH_OS(0);
+#undef TMPC_LAUNCH_OS
+#undef TMPC_LAUNCH
+    return hipGetLastError();
+}
+
+// the fp64-state launcher of a shape, in a translation unit of its own (sinst_f64_*.hip) ...
+#define TMPC_DEFINE_STREAMG_F64(NX, NU, GG)                                                                   \
+    hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &P, int ext, hipStream_t stream) {        \
+        return launch_streamg_f64<NX, NU, GG>(P, ext, stream);                                                \
+    }
+// ... and the entry of a shape that has one: TMPC_DEFINE_STREAMG_ENTRY plus that launcher and its reported name
+#define TMPC_DEFINE_STREAMG_ENTRY_F64(NX, NU, GG)                                                                   \
+    hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &, int, hipStream_t);                          \
+    const StreamEntry *stream##GG##_entry_##NX##_##NU() {                                                          \
+        static const StreamEntry e = {NX, NU, GG, "stream" #GG "<" #NX "," #NU ">", &build_streamg_coef<NX, NU, GG>, \
+                                      &build_streamg_bounds<NX, NU, GG>, &streamg_lds_bytes<NX, NU, GG>,           \
+                                      &streamg_scratch_floats<NX, NU>, &launch_streamg<NX, NU, GG>,                \
+                                      &launch_stream##GG##_f64_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";f64>"}; \
+        return &e;                                                                                                 \
+    }
 
 #define TMPC_DEFINE_STREAMG_ENTRY(NX, NU, GG)                                                                       \
     const StreamEntry *stream##GG##_entry_##NX##_##NU() {                                                          \

@@ -819,7 +819,10 @@ class BatchSolver:
         return float(self.lib.tinympc_kernel_elapsed_mean_ms(self.h, int(last_n)))
 
     def set_precision(self, precision):
-        """0: fp64 recurrences, fp32 state (default); 1: all fp32; 2: all fp64 like the reference (generic kernel, slow)"""
+        """0: fp64 recurrences, fp32 state (default); 1: all fp32; 2: all fp64 like the reference — on the generic kernel
+        (slow), except cold one-shot solves of the lean kernel's shapes (its fp64-state form, specialised on request) and, with
+        TINYMPC_HIP_STREAM_F64=1 set when the solver is created, every fixed-rho unchunked solve of (4,1), (6,3), (12,4) shapes
+        on the stream kernel's fp64-state form ("stream4<NX,NU;f64>")"""
         self._chk(self.lib.tinympc_set_precision(self.h, int(precision)), "set_precision")
 
     def reload_switches(self):
