@@ -241,7 +241,14 @@ int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter);
  * x_ref_seq is nx x (N*steps), u_ref_seq nu x ((N-1)*steps), column-major, step after step (what `steps` calls of
  * set_x_ref / set_u_ref would have passed).  The plant step of such a loop includes the affine term,
  * x0 = A x0 + B u0 + f (:123).  Step 0's references become the solver's own shared references and stay installed when
- * the sequence is dropped (by a later set_x_ref / set_u_ref, which replaces them, or by steps = 0, which does not).  Needs the transposed-sets kernel (mfmat) for the shape. */
+ * the sequence is dropped (by a later shared set_x_ref / set_u_ref, which replaces them, or by steps = 0, which does not).
+ * Supported wherever mpc_rollout is: inside the launch on the transposed-sets kernel (mfmat) and on the lanes-per-instance
+ * kernels at horizons up to 20 (quad: the step's references are re-staged in LDS before the step's first iteration), and
+ * launch by launch on the chained loops (mfma, and the lean kernel's behind TINYMPC_HIP_LEAN_WS), whose launches read their
+ * step's slice of the sequence in place.  tinympc_mpc_rollout fails, naming the condition, with fewer sequence steps than
+ * loop steps, with per-instance references (set after the sequence, or through tinympc_set_ref_mode(2)), with adaptive rho,
+ * at precision 2, on a quad entry with a horizon above 20, and on shapes that have no closed loop at all (stream / generic
+ * kernels); a sharded solver takes no sequence. */
 int tinympc_set_ref_sequence(tinympc_solver *s, const double *x_ref_seq, int x_rows, int x_cols, const double *u_ref_seq,
                              int u_rows, int u_cols, int steps);
 /* Tolerance-terminated solves of big batches: with chunk_iters > 0 (rounded up to a multiple of check_termination)

@@ -11,6 +11,10 @@ enum RefMode : int {
     REF_PER_INSTANCE = 2,  // [B][N][nx] / [B][N-1][nu]
 };
 
+// Longest horizon at which the lanes-per-instance (quad) kernels' in-kernel closed loop takes per-step references
+// (admm_quad.hip.h: REF_STEP; solver.hip refuses a reference sequence on a longer quad entry)
+enum { QUAD_REF_SEQ_MAX_N = 20 };
+
 // Slots of the per-solve device status block (uint32 each).
 //   [0..3] max over instances of (pri_x, dua_x, pri_u, dua_u), float bits (non-negative
 //          floats order like unsigned ints, so atomicMax on the bits is a float max)

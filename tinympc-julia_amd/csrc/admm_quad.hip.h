@@ -533,6 +533,9 @@ __device__ __forceinline__ T group_max_q(T v) {
     return v;
 }
 
+// workgroups (of four wavefronts) whose LDS a CU holds side by side: at most eight, one wavefront of each per SIMD
+constexpr int quad_lds_workgroups(size_t bytes) { return bytes * 8 <= 160 * 1024 ? 8 : (int)(160 * 1024 / bytes); }
+
 // OS ("one shot"): cold start and no workspace kept (the benchmark configs).  vnew / znew then overwrite
 // v / z in place — the separate copies only exist to reproduce what the reference leaves in its
 // workspace after a converged exit (admm.cpp:181-197) — which removes E_x + E_u floats of state per
@@ -573,13 +576,32 @@ __global__ __launch_bounds__(256) void admm_quad_kernel(const AdmmParams P) {
     // shape asks for it (QuadShape::LOOPV bit 2: rocket N=50 with fp64 recurrences 5.88 -> 5.54 ms)
     constexpr bool FOLD = G == 1 || ((S::LOOPV & 4) != 0 && sizeof(RT) == 8);
 
+    // Shared references of a closed loop that moves them every step (P.xref_seq): the wavefronts of a workgroup reach a step
+    // at different times (tolerance-terminated instances leave the iteration loop at different iterations), so each wavefront
+    // keeps its OWN image of the pack and re-stages it behind a wavefront-scope fence — where that costs neither a workgroup
+    // per CU nor a register: the three extra images must not lower the number of workgroups a CU's LDS holds; the lanes must
+    // already address the image through a register (G > 1: the lane's role offset — with one lane per instance the address
+    // is a constant, and a per-wavefront one took 6 more registers in the iteration loop: quad<4,1,20,g1> with a state
+    // bound sits at 510 of 512); and the kernel must not already keep trajectories or coefficient rows in LDS because its
+    // registers do not hold them (those kernels spill at the 512-register limit).  Elsewhere the iteration loop stays
+    // exactly as it is and the one image is re-staged between two workgroup barriers: every wavefront runs every step, so
+    // the whole workgroup reaches them.  One-shot and adaptive-rho kernels run no such loop and keep the one image.
+    constexpr int NW = T / 64;
+    constexpr size_t LDS_REST = sizeof(float) * ((CO_STORE ? 4 * wave_stage_floats(S::NU * (S::N - 1)) : 1) + S::BOUNDS_LEN + STATE_LEN) +
+                                sizeof(RT) * (COEF_LDS ? G * S::CP : 1);
+    // The kernels that can meet P.xref_seq: horizons up to QUAD_REF_SEQ_MAX_N.  The longer instantiations (quadrotor N = 30,
+    // cartpole N = 30, rocket N = 50) spill at the 512-register limit, and any code added to them moves their register
+    // allocation; they are compiled exactly as without the feature, and the solver refuses a sequence on them (launch_pass).
+    constexpr bool REF_STEP = REFS == REF_SHARED && !OS && !ADP && N <= QUAD_REF_SEQ_MAX_N;
+    constexpr bool REF_WAVE = REF_STEP && G > 1 && !COEF_LDS && PL.lds_floats == 0 &&
+                              quad_lds_workgroups(LDS_REST + sizeof(float) * NW * S::REFS_LEN) ==
+                                  quad_lds_workgroups(LDS_REST + sizeof(float) * S::REFS_LEN);
+    constexpr int REF_IMAGES = REF_WAVE ? NW : 1;
     __shared__ float s_bnd[S::BOUNDS_LEN];
-    __shared__ float s_ref[REFS == REF_SHARED ? S::REFS_LEN : 1];
+    __shared__ float s_ref[REFS == REF_SHARED ? REF_IMAGES * S::REFS_LEN : 1];
     __shared__ RT s_coef[COEF_LDS ? G * S::CP : 1];
     __shared__ __align__(16) float s_state[STATE_LEN];
-    static_assert(sizeof(float) * (S::BOUNDS_LEN + (REFS == REF_SHARED ? S::REFS_LEN : 1) + STATE_LEN) +
-                          sizeof(RT) * (COEF_LDS ? G * S::CP : 1) <=
-                      160 * 1024,
+    static_assert(LDS_REST + sizeof(float) * (REFS == REF_SHARED ? REF_IMAGES * S::REFS_LEN : 1) <= 160 * 1024,
                   "workgroup LDS budget exceeded");
 
     const int tid = threadIdx.x;
@@ -587,20 +609,43 @@ __global__ __launch_bounds__(256) void admm_quad_kernel(const AdmmParams P) {
     for (int i = tid; i < S::BOUNDS_LEN; i += T) s_bnd[i] = P.bounds[i];
     if constexpr (COEF_LDS)  // role-major in HBM -> role-interleaved 16-byte chunks in LDS
         for (int i = tid; i < G * S::CP; i += T) s_coef[CoefLds<RT, G>::slot(i % S::CP, i / S::CP)] = gcoef[i];
-    if constexpr (REFS == REF_SHARED) {
-        // pack [N][G][xref[RX] uref[RU]] from knot-major xref [N][nx], uref [N-1][nu]
-        for (int i = tid; i < S::REFS_LEN; i += T) {
+    // pack [N][G][xref[RX] uref[RU]] from knot-major xref [N][nx], uref [N-1][nu]; elements first, first + stride, ...
+    auto stage_refs = [&](float *img, const float *__restrict__ xref, const float *__restrict__ uref, int first, int stride) {
+        for (int i = first; i < S::REFS_LEN; i += stride) {
             const int k = i / (G * S::RW), rem = i % (G * S::RW);
             const int qq = rem / S::RW, j = rem % S::RW;
             float val = 0.f;
             if (j < RX) {
                 const int row = qq * RX + j;
-                if (row < NX) val = P.xref[k * NX + row];
+                if (row < NX) val = xref[k * NX + row];
             } else {
                 const int row = UREP ? (j - RX) : qq * RU + (j - RX);
-                if (row < NU && k < N - 1) val = P.uref[k * NU + row];
+                if (row < NU && k < N - 1) val = uref[k * NU + row];
             }
-            s_ref[i] = val;
+            img[i] = val;
+        }
+    };
+    if constexpr (REFS == REF_SHARED) {
+        if constexpr (REF_WAVE) {
+            stage_refs(s_ref + (tid >> 6) * S::REFS_LEN, P.xref, P.uref, tid & 63, 64);   // this wavefront's image
+        } else if constexpr (REF_STEP) {
+            stage_refs(s_ref, P.xref, P.uref, tid, T);
+        } else {
+            // the kernels outside REF_STEP keep this loop as they always had it, not the call above: they are at the register
+            // limit, and the same pack staged through the lambda's arguments moved the allocation of quad<12,4,30,g4>
+            for (int i = tid; i < S::REFS_LEN; i += T) {
+                const int k = i / (G * S::RW), rem = i % (G * S::RW);
+                const int qq = rem / S::RW, j = rem % S::RW;
+                float val = 0.f;
+                if (j < RX) {
+                    const int row = qq * RX + j;
+                    if (row < NX) val = P.xref[k * NX + row];
+                } else {
+                    const int row = UREP ? (j - RX) : qq * RU + (j - RX);
+                    if (row < NU && k < N - 1) val = P.uref[k * NU + row];
+                }
+                s_ref[i] = val;
+            }
         }
     }
     __syncthreads();
@@ -610,7 +655,7 @@ __global__ __launch_bounds__(256) void admm_quad_kernel(const AdmmParams P) {
     const bool active = slot < P.batch;
     const long b = (active && P.idx) ? P.idx[slot] : slot;  // instance this lane group works on
     const float *lb = s_bnd + q * S::BW;
-    const float *lr = s_ref + q * S::RW;
+    const float *lr = s_ref + (REF_WAVE ? (tid >> 6) * S::REFS_LEN : 0) + q * S::RW;
     const float *ld = s_bnd + N * G * S::BW + q * S::DW;  // diag(Q)+rho, diag(R)+rho
 
     // ---- per-lane coefficient rows: VGPRs, LDS (big shapes) or scalar loads (G = 1) ----
@@ -1050,6 +1095,29 @@ __global__ __launch_bounds__(256) void admm_quad_kernel(const AdmmParams P) {
         it = 0;
         conv = 0;
         ct_count = ct;
+    }
+    if constexpr (REF_STEP) {
+        // this step's shared references (set_x_ref / set_u_ref between two solves of the caller's loop,
+        // rocket_landing_constraints.jl:107-115); step 0 runs on what the prologue staged.  Wave-uniform, and the same at every
+        // wavefront of the launch: P.xref_seq is a kernel argument, and every wavefront runs n_steps steps.
+        if (P.xref_seq && step > 0) {
+            const float *xs = P.xref_seq + (size_t)step * EX, *us = P.uref_seq + (size_t)step * EU;
+            // (the image's address and the lane come from an opaque copy of tid, formed here: hoisted out of the step loop
+            // they would occupy registers through every iteration of a kernel that has none to spare)
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            if constexpr (REF_WAVE) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // the previous step's reads of the image are done
+                __builtin_amdgcn_wave_barrier();
+                stage_refs(s_ref + (t >> 6) * S::REFS_LEN, xs, us, t & 63, 64);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            } else {
+                __syncthreads();                                          // every wavefront has left step - 1
+                stage_refs(s_ref, xs, us, t, T);
+                __syncthreads();
+            }
+        }
     }
     auto backward_body = [&](const auto cAT, const auto cBT, const auto cKT, const auto cQI, const auto cPT) {
             // ================= fused backward sweep =================

@@ -325,6 +325,8 @@ struct Solver {
     int rollout_steps(hipStream_t stream, int mpc_steps);
     double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B] column-major fp64; [B][nx] plant state
     const double *x0d_launch = nullptr;           // handed to the next launch_pass
+    const float *xref_launch = nullptr, *uref_launch = nullptr;   // ... and its shared references, where not the solver's own (a step of a reference sequence)
+    int check_ref_sequence(int mpc_steps) const;
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};
     int *d_count = nullptr;

@@ -452,7 +452,7 @@ const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stre
 // loop) of a shape that has it, with the affine term / at most one cone per side (box-only problems where the entry says so)
 const ConeEntry *Solver::route_trans(bool rollout, const ConeEntry *oneshot) const {
     if (sw.no_mfmat || sw.no_mfma || sw.group) return nullptr;
-    if (strict_fp32() || hetero || st.adaptive_rho || (refs_per_instance() && ref_seq_steps > 0) || st.max_iter < 1 || (double)batch * ex() >= 2.0e9)
+    if (strict_fp32() || hetero || st.adaptive_rho || (rollout && refs_per_instance() && ref_seq_steps > 0) || st.max_iter < 1 || (double)batch * ex() >= 2.0e9)
         return nullptr;
     const ConeEntry *ct = find_trans_kernel(nx, nu, N);
     if (ct && (lin_active() || (ct->supports && !ct->supports(*this)))) ct = nullptr;
@@ -766,7 +766,9 @@ int Solver::set_ref(bool is_x, const double *ref, int cols) {
         h.clear();
     }
     (is_x ? xref_kind : uref_kind) = kind;
-    ref_seq_steps = 0;  // (a closed loop's per-step references go with the references they replaced)
+    // a closed loop's per-step references go with the shared references they replaced; per-instance references replace
+    // nothing the sequence installed, and the next mpc_rollout says that the two do not go together
+    if (kind != 2) ref_seq_steps = 0;
     refs_dirty = true;
     refs_device_owned = false;
     return 0;
@@ -1077,18 +1079,43 @@ __global__ void residual_max_kernel(const float *res, long batch, uint32_t *gsta
     }
 }
 
+// A closed loop with per-step shared references (set_ref_sequence): what no route offers, each named
+int Solver::check_ref_sequence(int mpc_steps) const {
+    if (mpc_steps <= 0 || ref_seq_steps <= 0) return 0;
+    if (ref_seq_steps < mpc_steps) {
+        set_error("mpc_rollout: the reference sequence holds " + std::to_string(ref_seq_steps) + " steps, the loop asks for " +
+                  std::to_string(mpc_steps) + " (one reference set per step)");
+        return -1;
+    }
+    if (refs_per_instance()) {
+        set_error("mpc_rollout: a reference sequence is shared by the batch and cannot be combined with per-instance references "
+                  "(set_ref_sequence with steps = 0 drops the sequence)");
+        return -1;
+    }
+    if (st.adaptive_rho) {
+        set_error("mpc_rollout: a reference sequence is not available with adaptive rho");
+        return -1;
+    }
+    if (precision == 2) {
+        set_error("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
+        return -1;
+    }
+    return 0;
+}
+
 int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     HIP_TRY(hipSetDevice(device));
     layout_final = true;
+    if (check_ref_sequence(mpc_steps)) return -1;
     if (select_kernel(mpc_steps > 0) || ensure_extension_buffers()) return -1;
     const bool chunkable = chunk_iters > 0 && mpc_steps == 0 && !hetero && (ke || se || (ce && ce->ws)) && st.check_termination > 0 &&
                            st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0 && st.max_iter > chunk_iters;
     if (chunkable) return solve_chunked(stream);
     if (mpc_steps > 0 && ke && ke->G == 16) return rollout_steps(stream, mpc_steps);
     // TINYMPC_HIP_LEAN_WS: the closed loop as the same chain of workspace-carrying launches on the lean kernel (plant state in
-    // fp64 between them) instead of the quad kernel's in-kernel loop; per-step reference sequences stay an error outside mfmat
-    if (mpc_steps > 0 && sw.lean_ws && warm_start && ref_seq_steps == 0) {
-        if (packs_dirty && upload_packs()) return -1;   // (the lean entry and its pack are found there)
+    // fp64 between them) instead of the quad kernel's in-kernel loop; with a reference sequence each launch gets its step's
+    if (mpc_steps > 0 && sw.lean_ws && warm_start) {
+        if ((packs_dirty && upload_packs()) || upload_refs()) return -1;   // (the lean entry and its pack are found there; the reference mode here)
         if (lean_ws_takes(nullptr)) return rollout_steps(stream, mpc_steps);
     }
     return launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, !warm_start, warm_start);
@@ -1181,8 +1208,8 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     P.bounds = d_bounds;
     P.x0 = d_x0;
     P.x0d = x0d_launch;
-    P.xref = d_xref;
-    P.uref = d_uref;
+    P.xref = xref_launch ? xref_launch : d_xref;
+    P.uref = uref_launch ? uref_launch : d_uref;
     P.xout = d_xout;
     P.uout = d_uout;
     P.iter = d_iter;
@@ -1251,9 +1278,20 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     // the quad and stream kernels keep the status block clean themselves (fold_status); the generic kernel
     // accumulates straight into it
     P.bounds_stride = (ce && ce->bounds_vary(*this)) ? 1 : 0;
+    // per-step references of a loop that runs inside the launch: mfmat's and the quad kernel's (the chain, rollout_steps,
+    // hands every launch its step's slice as P.xref / P.uref instead and arrives here with mpc_steps = 0)
     if (mpc_steps > 0 && ref_seq_steps > 0) {
-        if (!(ce && ce->ws) || ref_seq_steps < mpc_steps || ref_mode != REF_SHARED) {
-            set_error("mpc_rollout: per-step references need the transposed-sets kernel (mfmat) and one reference set per step");
+        if (!(ce && ce->ws) && !ke) {
+            set_error("mpc_rollout: per-step references need a kernel with a closed loop (mfmat, quad) or the chain of launches (mfma, lean)");
+            return -1;
+        }
+        if (ref_seq_steps < mpc_steps || ref_mode != REF_SHARED) {
+            set_error("mpc_rollout: per-step references need one shared reference set per step");
+            return -1;
+        }
+        if (ke && ke->N > QUAD_REF_SEQ_MAX_N) {
+            set_error("mpc_rollout: the lanes-per-instance kernels take a reference sequence at horizons up to " +
+                      std::to_string((int)QUAD_REF_SEQ_MAX_N) + " (this entry: " + ke->name + "); step the loop from the host");
             return -1;
         }
         P.xref_seq = d_xref_seq;
@@ -1412,10 +1450,15 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     }
     const long n0 = (long)Bn * nx;
     plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+    // with a reference sequence every launch reads its step's slice of the sequence as its shared references (step 0's are the
+    // solver's own, which stay installed: nothing is copied, and the stream is not synchronised between steps)
+    const size_t EX = (size_t)ex(), EU = (size_t)eu();
     for (int step = 0; step < mpc_steps; ++step) {
         x0d_launch = d_x0d;
+        if (ref_seq_steps > 0 && step > 0) xref_launch = d_xref_seq + step * EX, uref_launch = d_uref_seq + step * EU;
         const int rc = launch_pass(stream, 0, nullptr, batch, 0, st.max_iter, false, true);
         x0d_launch = nullptr;
+        xref_launch = uref_launch = nullptr;
         if (rc) return -1;
         plant_step_kernel<<<(unsigned)((Bn + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
                                                                         d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,

@@ -365,7 +365,8 @@ def get_status(solver):
 
 
 def set_ref_sequence(solver, x_ref_seq, u_ref_seq):
-    """shared references of every step of the next closed loops, (nx, N, steps) / (nu, N-1, steps)"""
+    """shared references of every step of the next closed loops, (nx, N, steps) / (nu, N-1, steps).  Supported wherever
+    mpc_rollout is (see BatchSolver.set_ref_sequence); not on a sharded solver"""
     _need_setup(solver)
     xs = np.asfortranarray(np.asarray(x_ref_seq, dtype=np.float64))
     us = np.asfortranarray(np.asarray(u_ref_seq, dtype=np.float64))
@@ -778,7 +779,13 @@ class BatchSolver:
 
     def set_ref_sequence(self, x_ref_seq, u_ref_seq):
         """shared references of every step of the next closed loops: x_ref_seq (nx, N, steps), u_ref_seq (nu, N-1, steps)
-        (rocket_landing_constraints.jl:107-115 shifts them step by step); None, None drops the sequence"""
+        (rocket_landing_constraints.jl:107-115 shifts them step by step); None, None drops the sequence.
+        Step 0's references become the solver's own shared references and stay installed after the loop.
+        Supported wherever mpc_rollout is: inside the launch on the transposed-sets kernel (mfmat) and on the lanes-per-instance
+        kernels at horizons up to 20 (quad), launch by launch on the chained loops (mfma; the lean kernel's with TINYMPC_HIP_LEAN_WS=1).  mpc_rollout
+        raises TinyMPCError, naming the condition, with fewer sequence steps than loop steps, with per-instance references
+        (set after the sequence — a later SHARED set_x_ref / set_u_ref drops the sequence instead), with adaptive rho, at
+        precision 2, on a quad entry with a horizon above 20, and on shapes without a closed loop (stream / generic kernels)"""
         if x_ref_seq is None:
             self._chk(self.lib.tinympc_set_ref_sequence(self.h, None, 0, 0, None, 0, 0, 0), "set_ref_sequence")
             return
