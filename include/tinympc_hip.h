@@ -233,7 +233,12 @@ int tinympc_unpin_host(tinympc_solver *s, void *ptr);
  * Afterwards x0 holds the plant state after the last step and get_states/get_controls/get_status
  * describe the last solve.  Logs, instance-major: x [batch][steps][nx] (plant state after each
  * step), u [batch][steps][nu] (control applied), iter [batch][steps] (ADMM iterations of the step,
- * negated when the step hit max_iter).  Any log pointer may be NULL. */
+ * negated when the step hit max_iter).  Any log pointer may be NULL.
+ * Environment switches, read when the solver is created (both off by default): TINYMPC_HIP_LEAN_WS=1 runs the loop of a
+ * cartpole-class shape with at least 20 480 instances on the headline (lean) kernel, as a stream-ordered chain of `steps`
+ * workspace-carrying launches and plant updates; TINYMPC_HIP_LEAN_LOOP=1 beside it (no effect alone) as ONE launch of that
+ * kernel's in-kernel loop, every instance's workspace kept on chip between the steps — except with a reference sequence
+ * (below), which keeps the chain.  Results, logs and workspace are those of the chain. */
 int tinympc_mpc_rollout(tinympc_solver *s, int steps, void *hip_stream);
 int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter);
 /* Shared references of EVERY step of the next closed loops — the caller pattern of

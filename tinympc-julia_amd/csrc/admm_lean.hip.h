@@ -100,12 +100,34 @@ __device__ __forceinline__ double lean_abs(double a) { return fabs(a); }
 // through the staging with the ballot of its converging lanes as the mask — in the steady state of a warm-started loop every
 // lane of a wavefront converges at the same check — and its lanes idle on as in the one-shot form; nothing of them is
 // stored again.  Without XB the form assumes the workspace's g is zero and leaves it alone (the host picks XB otherwise).
+// MPC (WS, LIVE, ONE; routed to with TINYMPC_HIP_LEAN_LOOP beside TINYMPC_HIP_LEAN_WS): the closed loop of P.mpc_steps warm
+// solves in one launch — what the chain of WS launches and plant_step_kernel (solver.hip) computes, step by step, with the
+// workspace kept on chip between the steps.  The instances of a wavefront do not leave a step together (their iteration
+// counts differ; at a sparse check converged and max_iter exits mix), so every lane keeps the workspace of ITS OWN exit while
+// the rest of its wavefront iterates on:
+//   * v, z: the lane's row of the parked slack.  The parking writes are masked by `!conv`, so a converged lane's row stays
+//     what it was at its exit (the previous iteration's v, z); a lane that leaves at max_iter writes its vnew, znew there;
+//   * y, d (and g): to the workspace arrays through the masked staged stores — a converged lane's at its convergence, ahead
+//     of the backward pass that would overwrite the d it leaves; the others' at the end of the step — 2 nu (N-1) floats per
+//     instance and step where a chained launch moves the whole workspace and the solution both ways;
+//   * the control it applies, znew_0 as a float, captured at the exit.
+// A step then starts from the rows and the arrays: every value crosses the workspace's own format (fp32), as in the chain.
+// The arrays are re-read by the wavefront that wrote them: s_waitcnt vmcnt(0) behind the stores, an agent-scope acquire
+// ahead of the loads (the L1 may hold the lines of the previous read).  Nothing between the steps is wider than a
+// wavefront: no workgroup barrier (wavefronts of a workgroup reach their steps at different times, ragged workgroups have
+// wavefronts without an active lane).  The plant step x0 <- A x0 + B u0 is plant_step_kernel's arithmetic (fp64, the model's
+// own A and B from the pack's sparse block, A terms by column, then B terms), the log its layout.  The last step is the WS
+// form's solve unchanged: solution, status, residuals, the workspace when P.save_state; behind it the last plant step leaves
+// the plant state in P.x0_out and, in fp64, in P.x0d, where it came from.  The kept workspace is always loaded (the host
+// sends no cold start here).
 constexpr int lean_park_stride(int EX) { return (((EX + 3) / 4) % 2 ? (EX + 3) / 4 : (EX + 3) / 4 + 1) * 4; }   // an odd number of float4
-template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB = false, int REFS = REF_ZERO, class ST = float, uint64_t SP = 0, bool WS = false>
+template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB = false, int REFS = REF_ZERO, class ST = float, uint64_t SP = 0, bool WS = false,
+          bool MPC = false>
 __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const AdmmParams P) {
     constexpr bool F64 = std::is_same<ST, double>::value;
     static_assert(!F64 || ONE, "fp64 state: the 512-register form");
     static_assert(!WS || !F64, "kept workspace: fp32 state (the fp64 workspace has another format)");
+    static_assert(!MPC || (WS && LIVE && ONE), "in-kernel closed loop: the tolerance-terminated workspace-keeping form");
     static_assert(REFS == REF_ZERO || REFS == REF_SHARED, "lean kernel: zero or shared references");
 #ifdef TMPC_LEAN_CLOCK_PROBE
     const unsigned long long probe_entry = __builtin_amdgcn_s_memrealtime();
@@ -251,7 +273,19 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     for (int k = 0; k < N - 1; ++k)
 #pragma unroll
         for (int a = 0; a < NU; ++a) Y[k][a] = (ST)0, Z[k][a] = (ST)0, D[k][a] = (DT)0;
-    if constexpr (WS) {
+    if constexpr (MPC) {
+        // the kept v, z into the lanes' rows: every step, the first included, then starts from the rows and the arrays
+        // (lanes without an instance get zeros)
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
+        int td = tid;
+        asm volatile("" : "+v"(td));
+        const int ln = td & 63;
+        const long w0 = (long)blockIdx.x * 256 + (td & ~63);
+        float *so = s_stage[td >> 6];
+        load_wave_x<EX>(so, P.sv + w0 * EX, ln, mask, [&](auto ee, float val) { s_pv[td * PVS + decltype(ee)::value] = val; });
+        load_wave_u<EU>(so, P.sz + w0 * EU, ln, mask, [&](auto ee, float val) { s_pz[td * PZS + decltype(ee)::value] = val; });
+    }
+    if constexpr (WS && !MPC) {
         if (!P.cold_start) {                                                    // go on from the kept workspace (admm.cpp:111-115)
             const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
             int td = tid;                                                       // (opaque, as at the stores: nothing of the
@@ -324,7 +358,13 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             const ST gn = t - vn;                                               // g = g + x - vnew
             // PARK: the previous v, kept for a converged exit (element by element here: gathered into a float4 of its own the
             // four values cost this form 12 parked registers; the compiler merges a knot's four writes — tests/test_lean_ws_asm.py)
-            if constexpr (RES && PARK) s_pv[tid * PVS + k * NX + m] = (float)(QT[k][m] + G[k][m]);
+            if constexpr (RES && PARK) {
+                if constexpr (MPC) {                                            // (a converged lane's row stays its exit's)
+                    if (!conv) s_pv[tid * PVS + k * NX + m] = (float)(QT[k][m] + G[k][m]);
+                } else {
+                    s_pv[tid * PVS + k * NX + m] = (float)(QT[k][m] + G[k][m]);
+                }
+            }
             if constexpr (RES) {
                 pri_xf = lean_max(pri_xf, lean_abs(xf - vn));
                 dua_xf = lean_max(dua_xf, lean_abs((QT[k][m] + G[k][m]) - vn)); // v = the previous vnew = q~ + g
@@ -381,11 +421,18 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                     }
 #pragma unroll
                     for (int m = 0; m < NX; ++m) {
-                        v0p[m] = warm0 ? P.sv[bb * EX + m] : 0.f;
+                        if constexpr (MPC) v0p[m] = s_pv[td * PVS + m];      // (the lane's row: the v_0 of its last exit)
+                        else v0p[m] = warm0 ? P.sv[bb * EX + m] : 0.f;
                         dua_x = fmax(dua_x, fabs((double)v0p[m] - x0v[m]));
                     }
                 }
-                if constexpr (PARK) park_v(0, v0p);
+                if constexpr (PARK) {
+                    if constexpr (MPC) {
+                        if (!conv) park_v(0, v0p);
+                    } else {
+                        park_v(0, v0p);
+                    }
+                }
             }
             if constexpr (!WS && !XB)
                 if (first_iter) {   // cold start: the previous state slack is the zero workspace at knot 0 too, where vnew is x0 (admm.cpp:94)
@@ -505,7 +552,13 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 if constexpr (RES) {
                     pri_u = lean_max(pri_u, lean_abs(uf - zn));                 // (:95)
                     dua_u = lean_max(dua_u, lean_abs(Z[k][a] - zn));            // (:96), times rho at the check
-                    if constexpr (PARK) s_pz[tid * PZS + k * NU + a] = (float)Z[k][a];
+                    if constexpr (PARK) {
+                        if constexpr (MPC) {
+                            if (!conv) s_pz[tid * PZS + k * NU + a] = (float)Z[k][a];
+                        } else {
+                            s_pz[tid * PZS + k * NU + a] = (float)Z[k][a];
+                        }
+                    }
                 }
                 Z[k][a] = zn;
             }
@@ -513,7 +566,11 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 float pv[NX];
 #pragma unroll
                 for (int m = 0; m < NX; ++m) pv[m] = (float)X[k + 1][m];
-                park_v(k + 1, pv);
+                if constexpr (MPC) {
+                    if (!conv) park_v(k + 1, pv);
+                } else {
+                    park_v(k + 1, pv);
+                }
             }
 #pragma unroll
             for (int m = 0; m < NX; ++m) {
@@ -702,6 +759,106 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // loop-carried register and lets the compiler hoist their common parts above the branch, live across everything).
     const bool can_converge = P.abs_pri_tol > 0.f && P.abs_dua_tol > 0.f;
     const int max_iter = P.max_iter;
+    // MPC, a step before the last: y, d (and g) of the lanes in `mask` to the workspace arrays, through the staging
+    auto store_step = [&](unsigned long long mask) {
+        int td = tid;
+        asm volatile("" : "+v"(td));
+        const int ln = td & 63;
+        float *so = s_stage[td >> 6];
+        const long w0 = (long)blockIdx.x * 256 + (td & ~63);
+        auto single = [&](float *uo, auto &&gu) {
+            if constexpr (SW != 0) {
+                if (mask == ~0ull) store_wave_u_wide<EU>(so, uo, ln, gu);
+                else store_wave_u<EU, false>(so, uo, ln, mask, gu);
+            } else {
+                store_wave_u<EU, false>(so, uo, ln, mask, gu);
+            }
+        };
+        auto gety = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)Y[e / NU][e % NU]; };
+        auto getd = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)D[e / NU][e % NU]; };
+        if constexpr (XB) {
+            auto getg = [&](auto ee) { constexpr int e = decltype(ee)::value; return (float)G[e / NX][e % NX]; };
+            if constexpr (SW != 0) store_wave_wide<EX, EU, SW>(so, P.sg + w0 * EX, P.sy + w0 * EU, ln, mask, getg, gety);
+            else store_wave_coalesced<EX, EU>(so, P.sg + w0 * EX, P.sy + w0 * EU, ln, mask, getg, gety);
+        } else {
+            single(P.sy + w0 * EU, gety);
+        }
+        single(P.sd + w0 * EU, getd);
+    };
+    // MPC: the plant step behind a solve and its log (plant_step_kernel, solver.hip: the same operations in the same order);
+    // u0: the control the lane's exit left
+    float u0c[MPC ? NU : 1];
+    auto plant = [&](int step, bool final_step) {
+        const double *ab = P.lean + L::O_S;                                     // the model's own A [nx][nx], B [nx][nu], row-major
+        double xn[NX];
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < NX; ++j) acc = fma(ab[L::O_M + r * NX + j], X[0][j], acc);
+#pragma unroll
+            for (int a = 0; a < NU; ++a) acc = fma(ab[L::O_B + r * NU + a], (double)u0c[a], acc);
+            xn[r] = acc;
+        }
+        int td = tid;
+        asm volatile("" : "+v"(td));
+        const long bb = (long)blockIdx.x * 256 + td;
+        if (bb < P.batch) {
+            const long so = bb * P.mpc_steps + step;
+#pragma unroll
+            for (int r = 0; r < NX; ++r) P.mpc_x[so * NX + r] = (float)xn[r];
+#pragma unroll
+            for (int a = 0; a < NU; ++a) P.mpc_u[so * NU + a] = u0c[a];
+            P.mpc_iter[so] = conv ? P.iter_offset + it : -(P.iter_offset + it);
+            if (final_step) {
+#pragma unroll
+                for (int r = 0; r < NX; ++r) P.x0_out[bb * NX + r] = (float)xn[r];
+                // (the caller's fp64 plant state, read at entry: the loop's launch owns it, as plant_step_kernel does in the chain)
+                if (double *xd = const_cast<double *>(P.x0d)) {
+#pragma unroll
+                    for (int r = 0; r < NX; ++r) xd[bb * NX + r] = xn[r];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < NX; ++r) X[0][r] = xn[r];
+    };
+    int step = 0;
+#ifdef TMPC_LEAN_CLOCK_PROBE
+    // MPC: core clocks of a step's phases, summed over the steps — the reload, the iteration loop, of which the stores at
+    // convergence, and the step's end (rows, y / d store, plant step, log, the wait for the stores)
+    unsigned long long probe_ph[4] = {0, 0, 0, 0}, probe_a = 0, probe_c = 0;
+#endif
+    do {   // (MPC: the steps of the closed loop; otherwise once)
+#ifdef TMPC_LEAN_CLOCK_PROBE
+    probe_a = __builtin_amdgcn_s_memtime();
+#endif
+    if constexpr (MPC) {
+        // the step's start: v, z from the lane's row, y, d (g) from the arrays this wavefront wrote in the step before
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        int td = tid;
+        asm volatile("" : "+v"(td));
+        const int ln = td & 63;
+        const long w0 = (long)blockIdx.x * 256 + (td & ~63);
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(w0 + ln < P.batch);
+        float *so = s_stage[td >> 6];
+        const float *rv = s_pv + td * PVS, *rz = s_pz + td * PZS;
+        if constexpr (XB) {
+            load_wave_x<EX>(so, P.sg + w0 * EX, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; G[e / NX][e % NX] = val; });
+            sfor<0, EX>([&](auto ee) { constexpr int e = decltype(ee)::value; QT[e / NX][e % NX] = rv[e] - G[e / NX][e % NX]; });
+        } else {
+            sfor<NX, EX>([&](auto ee) { constexpr int e = decltype(ee)::value; X[e / NX][e % NX] = (double)rv[e]; });
+        }
+        sfor<0, EU>([&](auto ee) { constexpr int e = decltype(ee)::value; Z[e / NU][e % NU] = rz[e]; });
+        load_wave_u<EU>(so, P.sy + w0 * EU, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; Y[e / NU][e % NU] = val; });
+        load_wave_u<EU>(so, P.sd + w0 * EU, ln, mask, [&](auto ee, float val) { constexpr int e = decltype(ee)::value; D[e / NU][e % NU] = (DT)val; });
+        it = 0, conv = 0;
+        res0 = 0, res1 = 0, res2 = 0, res3 = 0;
+    }
+    const bool last_step = !MPC || step + 1 >= P.mpc_steps;
+#ifdef TMPC_LEAN_CLOCK_PROBE
+    probe_ph[0] += __builtin_amdgcn_s_memtime() - probe_a, probe_a = __builtin_amdgcn_s_memtime();
+#endif
     int i = 0;
     while (i < max_iter) {
         int next_res = max_iter;                                                // 0-based index of the next iteration with residuals
@@ -730,6 +887,22 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             const bool now = active && !conv && res0 < ptol && res2 < ptol && res1 < dtol && res3 < dtol;
             if constexpr (WS) {                                                 // returns before v = vnew and the backward pass (:181-193)
                 const unsigned long long cm = __builtin_amdgcn_ballot_w64(now);
+                if constexpr (MPC) {
+#ifdef TMPC_LEAN_CLOCK_PROBE
+                    probe_c = __builtin_amdgcn_s_memtime();
+#endif
+                    if (cm) {
+                        if (last_step) store_ws(cm, now, std::true_type{});
+                        else store_step(cm);                                    // (ahead of the backward pass below: the d of its exit)
+                    }
+#ifdef TMPC_LEAN_CLOCK_PROBE
+                    probe_ph[2] += __builtin_amdgcn_s_memtime() - probe_c;
+#endif
+                    if (now) {
+#pragma unroll
+                        for (int a = 0; a < NU; ++a) u0c[a] = (float)Z[0][a];
+                    }
+                } else
                 if (cm) store_ws(cm, now, std::true_type{});
                 if (now) conv = 1;
             } else
@@ -744,6 +917,39 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         // (WS: a saving solve leaves that d in the workspace, admm.cpp:195-205)
         if (!(ONE && !XB) || WS || i < max_iter) backward();
     }
+    if constexpr (MPC) {
+#ifdef TMPC_LEAN_CLOCK_PROBE
+        probe_ph[1] += __builtin_amdgcn_s_memtime() - probe_a, probe_a = __builtin_amdgcn_s_memtime();
+#endif
+#pragma unroll
+        for (int a = 0; a < NU; ++a)
+            if (!conv) u0c[a] = (float)Z[0][a];
+        if (last_step) break;                                                   // (the last step's exit at max_iter: the final store below)
+        // the lanes that leave at max_iter: vnew, znew into their rows, y, d (g) — the d of the backward pass behind the last
+        // iteration — to the arrays (admm.cpp:195-205)
+        const bool mine = active && !conv;
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
+        if (mask) {
+            if (mine) {
+                int td = tid;
+                asm volatile("" : "+v"(td));
+                float *rv = s_pv + td * PVS, *rz = s_pz + td * PZS;
+                sfor<0, EX>([&](auto ee) {
+                    constexpr int e = decltype(ee)::value;
+                    rv[e] = vnew_at(std::integral_constant<int, e / NX>{}, std::integral_constant<int, e % NX>{});
+                });
+                sfor<0, EU>([&](auto ee) { constexpr int e = decltype(ee)::value; rz[e] = (float)Z[e / NU][e % NU]; });
+            }
+            store_step(mask);
+        }
+        plant(step, false);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                        // this step's stores, before the next step re-reads them
+#ifdef TMPC_LEAN_CLOCK_PROBE
+        probe_ph[3] += __builtin_amdgcn_s_memtime() - probe_a;
+#endif
+        ++step;
+    }
+    } while (MPC);
     // ---- global status block: wavefront max of the residuals, count of unsolved instances; behind the final store, or
     // (TMPC_LEAN_FOLD_FIRST) ahead of it ----
     auto fold = [&]() {
@@ -795,6 +1001,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             }
         }
     }
+    if constexpr (MPC) plant(step, true);                                       // ... and the plant step behind the last solve
 #ifdef TMPC_LEAN_CLOCK_PROBE
     if (active) P.iter[b] = (int)(__builtin_amdgcn_s_memrealtime() & 0xFFFFFFull);     // stores issued
     __builtin_amdgcn_s_waitcnt(0);
@@ -807,6 +1014,10 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #endif
     }
 #ifdef TMPC_LEAN_CLOCK_PROBE
+    if constexpr (MPC) {
+        if (active)
+            for (int q = 0; q < 4; ++q) P.res[b * 4 + q] = (float)probe_ph[q];  // (the last step's end is the final store: not in [3])
+    } else
     if (active) {
         P.res[b * 4 + 0] = (float)(probe_t1 - probe_t0);                                // core clocks of the iteration loop
         P.res[b * 4 + 1] = (float)(probe_r1 - probe_r0);                                // ... in 100 MHz ticks

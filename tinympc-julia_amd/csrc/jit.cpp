@@ -268,6 +268,8 @@ const ConeEntry *jit_trans_for(const Solver &sv, int verbose) {
 // nu (N-1) | 1) floats.  Cartpole-class (4,1): tolerance-terminated to N = 24, fixed-iteration wherever the registers hold it.
 // Asked before a unit is compiled (a compile that cannot succeed costs every process ten seconds) and by the routing
 // (solver.hip: lean_ws_takes), so that such a solver's mpc_rollout keeps the quad kernel's fused loop.
+// (The in-kernel closed loop, LV_MPC, adds nothing to this: between its steps v and z stay in the parked rows the
+// tolerance-terminated form has anyway — `live` is then true whatever the tolerances — and y, d, g go through the staging.)
 bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool knot_bounds) {
     const int EX = nx * N, EU = nu * (N - 1);
     if (2 * N * nx + 4 * N * nu + 50 > 490) return false;                          // (registers: the 512-register form only)
@@ -291,8 +293,9 @@ const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, i
     if (nx < 1 || nu < 1 || N < 3 || lean_layout(nx, nu).padded > 32) return nullptr;
     if (((variant & LV_SPARSE) != 0) != (sp != 0) || (sp && (nx > 4 || nu > 4))) return nullptr;
     const bool one = (variant & LV_ONE) != 0, f64 = (variant & LV_F64) != 0, xb = (variant & LV_XB) != 0;
-    const bool ws = (variant & LV_WS) != 0;
+    const bool ws = (variant & LV_WS) != 0, mpc = (variant & LV_MPC) != 0;
     if ((f64 && !one) || (f64 && ws)) return nullptr;
+    if (mpc && !(ws && one && (variant & LV_LIVE))) return nullptr;   // (the loop: the tolerance-terminated workspace-keeping form only)
     if (ws && !lean_ws_fits(nx, nu, N, (variant & LV_LIVE) != 0, xb, (variant & LV_SHARED) != 0, !(variant & LV_UBK))) return nullptr;
     const int regs = f64 ? (xb ? 4 : 2) * N * nx + 6 * N * nu + 50 : 2 * N * nx + (one ? 4 : 3) * N * nu + 50;
     if (regs > (f64 ? 450 : (one ? 490 : 250))) return nullptr;   // (fp64 state with a state bound at N = 20: 490 values, 463 of them spilled)
@@ -300,8 +303,9 @@ const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, i
     name << "lean_" << nx << "_" << nu << "_" << N << "_v" << variant;
     if (sp) name << "_sp" << std::hex << (unsigned long long)sp << std::dec;
     auto tf = [&](int bit) { return (variant & bit) ? "true" : "false"; };
-    // (LV_WS: the workspace-keeping form has a macro of its own, fp32 state only)
-    src << "// specialised at the first solve by jit.cpp\n#include \"lean_entry.hip.h\"\n" << (ws ? "TMPC_DEFINE_LEAN_JIT_ENTRY_WS" : "TMPC_DEFINE_LEAN_JIT_ENTRY_SP")
+    // (LV_WS: the workspace-keeping form has a macro of its own, fp32 state only; LV_MPC: its in-kernel closed loop likewise)
+    src << "// specialised at the first solve by jit.cpp\n#include \"lean_entry.hip.h\"\n"
+        << (mpc ? "TMPC_DEFINE_LEAN_JIT_ENTRY_MPC" : (ws ? "TMPC_DEFINE_LEAN_JIT_ENTRY_WS" : "TMPC_DEFINE_LEAN_JIT_ENTRY_SP"))
         << "(\"lean<" << nx << "," << nu << "," << N << (f64 ? ";f64" : "") << ">\", " << nx << ", " << nu << ", " << N << ", " << tf(LV_LIVE) << ", " << tf(LV_UBK)
         << ", " << tf(LV_ONE) << ", " << tf(LV_XB) << ", " << ((variant & LV_SHARED) ? "tmpc::REF_SHARED" : "tmpc::REF_ZERO") << ", ";
     if (!ws) src << (f64 ? "double" : "float") << ", ";

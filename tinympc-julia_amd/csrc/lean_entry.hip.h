@@ -83,9 +83,9 @@ hipError_t launch_lean_sparse(const AdmmParams &P, bool live, bool knot_bounds, 
 // the reference accepts any (nx, nu, N) at run time (tiny_api.cpp:21-71).  A whole entry is 24 kernels and 45-90 s of compiler;
 // one variant — the (LIVE, UBK, ONE, XB, REFS) the launch in hand needs — is a few seconds, so a unit carries exactly one.
 // (ST = double: the fp64-state form, precision 2 — only ever built this way; SP: the model's exact pattern, the sparse sweeps)
-template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB, int REFS, class ST, uint64_t SP = 0, bool WS = false>
+template <int NX, int NU, int N, bool LIVE, bool UBK, bool ONE, bool XB, int REFS, class ST, uint64_t SP = 0, bool WS = false, bool MPC = false>
 hipError_t launch_lean_exact(const AdmmParams &P, bool, bool, bool, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
-    lean_dispatch(admm_lean_kernel<NX, NU, N, LIVE, UBK, ONE, XB, REFS, ST, SP, WS>, (P.batch + 255) / 256, stream, ev0, ev1, P);
+    lean_dispatch(admm_lean_kernel<NX, NU, N, LIVE, UBK, ONE, XB, REFS, ST, SP, WS, MPC>, (P.batch + 255) / 256, stream, ev0, ev1, P);
     return hipGetLastError();
 }
 // ... its workspace-keeping form (LV_WS): the one variant is the entry's launch_ws
@@ -94,6 +94,16 @@ hipError_t launch_lean_exact(const AdmmParams &P, bool, bool, bool, hipStream_t 
     const LeanEntry *lean_jit_entry() {                                                                                  \
         static const LeanEntry e = {NX, NU, NN, NAME, nullptr, SP, nullptr,                                              \
                                     &launch_lean_exact<NX, NU, NN, LIVE, UBK, ONE, XB, REFS, float, SP, true>};          \
+        return &e;                                                                                                       \
+    }                                                                                                                    \
+    }                                                                                                                    \
+    extern "C" const void *tmpc_jit_entry() { return tmpc::lean_jit_entry(); }
+// ... and the in-kernel closed loop (LV_MPC): the one variant is the entry's launch_mpc
+#define TMPC_DEFINE_LEAN_JIT_ENTRY_MPC(NAME, NX, NU, NN, LIVE, UBK, ONE, XB, REFS, SP)                                   \
+    namespace tmpc {                                                                                                     \
+    const LeanEntry *lean_jit_entry() {                                                                                  \
+        static const LeanEntry e = {NX, NU, NN, NAME, nullptr, SP, nullptr, nullptr, nullptr,                            \
+                                    &launch_lean_exact<NX, NU, NN, LIVE, UBK, ONE, XB, REFS, float, SP, true, true>};    \
         return &e;                                                                                                       \
     }                                                                                                                    \
     }                                                                                                                    \
@@ -156,6 +166,62 @@ hipError_t launch_lean_exact(const AdmmParams &P, bool, bool, bool, hipStream_t 
         static const LeanEntry e = {NX, NU, NN, "lean<" #NX "," #NU "," #NN ">", &launch_lean<NX, NU, NN>, (SP),   \
                                     &launch_lean_sparse<NX, NU, NN, (SP)>, &lean_ws_##NX##_##NU##_##NN,            \
                                     &lean_ws_##NX##_##NU##_##NN##_sparse};                                          \
+        return &e;                                                                                                 \
+    }
+
+// The in-kernel closed loop (admm_lean.hip.h, MPC) of a built-in entry, in translation units of their own like the WS kernels
+// (linst_mpc_*.hip): the tolerance-terminated kernels only — they do the fixed-iteration arithmetic when no tolerance is
+// positive, so a fixed-iteration rollout runs them too (as launch_lean_v does for one WS pattern) — by (XB, REFS) and the
+// kind of input bounds; the sparse ones by XB.
+template <int NX, int NU, int N, bool XB, int REFS>
+hipError_t launch_lean_mpc_v(const AdmmParams &P, bool knot_bounds, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    const int grid = (P.batch + 255) / 256;
+    if (knot_bounds) lean_dispatch(admm_lean_kernel<NX, NU, N, true, false, true, XB, REFS, float, 0, true, true>, grid, stream, ev0, ev1, P);
+    else lean_dispatch(admm_lean_kernel<NX, NU, N, true, true, true, XB, REFS, float, 0, true, true>, grid, stream, ev0, ev1, P);
+    return hipGetLastError();
+}
+template <int NX, int NU, int N, uint64_t SP>
+hipError_t launch_lean_mpc_sparse(const AdmmParams &P, bool, bool knot_bounds, bool state_bounds, hipStream_t stream, hipEvent_t ev0,
+                                  hipEvent_t ev1) {
+    if (P.ref_mode != REF_ZERO || knot_bounds) return hipErrorInvalidValue;
+    const int grid = (P.batch + 255) / 256;
+    if (state_bounds) lean_dispatch(admm_lean_kernel<NX, NU, N, true, true, true, true, REF_ZERO, float, SP, true, true>, grid, stream, ev0, ev1, P);
+    else lean_dispatch(admm_lean_kernel<NX, NU, N, true, true, true, false, REF_ZERO, float, SP, true, true>, grid, stream, ev0, ev1, P);
+    return hipGetLastError();
+}
+#define TMPC_LEAN_MPC_ARGS const AdmmParams &P, bool knot_bounds, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1
+#define TMPC_DECLARE_LEAN_MPC_PARTS(NX, NU, NN)                                                                         \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_z(TMPC_LEAN_MPC_ARGS);                                                    \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_zx(TMPC_LEAN_MPC_ARGS);                                                   \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_s(TMPC_LEAN_MPC_ARGS);                                                    \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_sx(TMPC_LEAN_MPC_ARGS);                                                   \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_sparse(const AdmmParams &, bool, bool, bool, hipStream_t, hipEvent_t, hipEvent_t); \
+    inline hipError_t lean_mpc_##NX##_##NU##_##NN(const AdmmParams &P, bool, bool knot_bounds, bool state_bounds,       \
+                                                  hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {                 \
+        if (P.ref_mode == REF_SHARED)                                                                                   \
+            return state_bounds ? lean_mpc_##NX##_##NU##_##NN##_sx(P, knot_bounds, stream, ev0, ev1)                    \
+                                : lean_mpc_##NX##_##NU##_##NN##_s(P, knot_bounds, stream, ev0, ev1);                    \
+        return state_bounds ? lean_mpc_##NX##_##NU##_##NN##_zx(P, knot_bounds, stream, ev0, ev1)                        \
+                            : lean_mpc_##NX##_##NU##_##NN##_z(P, knot_bounds, stream, ev0, ev1);                        \
+    }
+#define TMPC_DEFINE_LEAN_MPC_PART(NX, NU, NN, TAG, XB, REFS)                                                            \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_##TAG(TMPC_LEAN_MPC_ARGS) {                                                \
+        return launch_lean_mpc_v<NX, NU, NN, XB, REFS>(P, knot_bounds, stream, ev0, ev1);                               \
+    }
+#define TMPC_DEFINE_LEAN_MPC_SPARSE(NX, NU, NN, SP)                                                                     \
+    hipError_t lean_mpc_##NX##_##NU##_##NN##_sparse(const AdmmParams &P, bool live, bool knot_bounds, bool state_bounds, \
+                                                    hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {               \
+        return launch_lean_mpc_sparse<NX, NU, NN, (SP)>(P, live, knot_bounds, state_bounds, stream, ev0, ev1);          \
+    }
+// an entry with the sparse kernels, the workspace-keeping kernels and the in-kernel closed loop of both kinds
+#define TMPC_DEFINE_LEAN_ENTRY_SP_WS_MPC(NX, NU, NN, SP)                                                           \
+    TMPC_DECLARE_LEAN_WS_PARTS(NX, NU, NN)                                                                         \
+    TMPC_DECLARE_LEAN_MPC_PARTS(NX, NU, NN)                                                                        \
+    const LeanEntry *lean_entry_##NX##_##NU##_##NN() {                                                             \
+        static const LeanEntry e = {NX, NU, NN, "lean<" #NX "," #NU "," #NN ">", &launch_lean<NX, NU, NN>, (SP),   \
+                                    &launch_lean_sparse<NX, NU, NN, (SP)>, &lean_ws_##NX##_##NU##_##NN,            \
+                                    &lean_ws_##NX##_##NU##_##NN##_sparse, &lean_mpc_##NX##_##NU##_##NN,             \
+                                    &lean_mpc_##NX##_##NU##_##NN##_sparse};                                         \
         return &e;                                                                                                 \
     }
 

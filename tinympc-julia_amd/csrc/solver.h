@@ -57,11 +57,18 @@ struct LeanEntry {
                             hipEvent_t ev1) = nullptr;
     hipError_t (*launch_sparse_ws)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
                                    hipEvent_t ev1) = nullptr;
+    // the in-kernel closed loop (admm_lean.hip.h, MPC: P.mpc_steps warm solves and plant steps in one launch), dense and of
+    // the pattern sp; null: the entry has none (a specialised LV_MPC variant carries its one kernel in launch_mpc)
+    hipError_t (*launch_mpc)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
+                             hipEvent_t ev1) = nullptr;
+    hipError_t (*launch_sparse_mpc)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
+                                    hipEvent_t ev1) = nullptr;
 };
 const LeanEntry *find_lean_kernel(int nx, int nu, int N);
 // ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel);
-// LV_SPARSE: on the model's own pattern sp; LV_WS: the workspace-keeping form (fp32 state only)
-enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_WS = 128, LV_COUNT = 256 };
+// LV_SPARSE: on the model's own pattern sp; LV_WS: the workspace-keeping form (fp32 state only); LV_MPC: its in-kernel closed
+// loop (with LV_WS, LV_LIVE and LV_ONE)
+enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_WS = 128, LV_MPC = 256, LV_COUNT = 512 };
 const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, int verbose);
 // the lean kernel's 512-register form (one wavefront per SIMD): at most one workgroup per CU, tolerance-terminated solves,
 // TINYMPC_HIP_LEAN_ONE (lean_entry.hip.h: launch_lean_v)
@@ -129,6 +136,7 @@ struct Switches {
          no_jit = false,                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
          lean_dense = false,                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
          lean_ws = false,                                   // TINYMPC_HIP_LEAN_WS: warm / kept-workspace solves and mpc_rollout on the lean kernel
+         lean_loop = false,                                 // TINYMPC_HIP_LEAN_LOOP: with lean_ws, mpc_rollout as one launch of the lean kernel's in-kernel loop
          stream_f64 = false,                                // TINYMPC_HIP_STREAM_F64: precision 2 on the stream kernel's fp64-state form where it is built
          event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
     int mfmac_debug = 0;    // timing probe builds only
@@ -323,6 +331,11 @@ struct Solver {
     // closed loop on the matrix-core kernel: per step one WS launch and a plant-update kernel, stream-ordered, the plant
     // state kept in fp64 on the device between steps (what the quad kernel's fused loop keeps in registers)
     int rollout_steps(hipStream_t stream, int mpc_steps);
+    // TINYMPC_HIP_LEAN_LOOP: the same loop as ONE launch of the lean kernel's in-kernel loop (1: no loop kernel for this
+    // calling pattern, nothing launched)
+    int rollout_lean_loop(hipStream_t stream, int mpc_steps);
+    bool lean_loop_launch = false;                // handed to the next launch_pass: the lean kernel's loop form, or nothing
+    int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout (-1: none has run)
     double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B] column-major fp64; [B][nx] plant state
     const double *x0d_launch = nullptr;           // handed to the next launch_pass
     const float *xref_launch = nullptr, *uref_launch = nullptr;   // ... and its shared references, where not the solver's own (a step of a reference sequence)

@@ -351,6 +351,7 @@ Switches read_switches() {
     w.lean_one = on("TINYMPC_HIP_LEAN_ONE");
     w.lean_dense = on("TINYMPC_HIP_LEAN_DENSE");
     w.lean_ws = on("TINYMPC_HIP_LEAN_WS");
+    w.lean_loop = on("TINYMPC_HIP_LEAN_LOOP");
     w.stream_f64 = on("TINYMPC_HIP_STREAM_F64");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
@@ -1116,9 +1117,23 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     // fp64 between them) instead of the quad kernel's in-kernel loop; with a reference sequence each launch gets its step's
     if (mpc_steps > 0 && sw.lean_ws && warm_start) {
         if ((packs_dirty && upload_packs()) || upload_refs()) return -1;   // (the lean entry and its pack are found there; the reference mode here)
-        if (lean_ws_takes(nullptr)) return rollout_steps(stream, mpc_steps);
+        if (lean_ws_takes(nullptr)) {
+            // ... and with TINYMPC_HIP_LEAN_LOOP beside it, the whole loop as ONE launch of the lean kernel's in-kernel loop
+            // (admm_lean.hip.h, MPC).  What keeps the chain, each by name: per-step references (the kernel stages the shared
+            // references once per launch), and a calling pattern without a loop kernel — the entry has none for it, or its
+            // specialisation was refused or failed (rollout_lean_loop returns 1)
+            const bool ref_sequence = ref_seq_steps > 0;
+            if (sw.lean_loop && !ref_sequence) {
+                const int rc = rollout_lean_loop(stream, mpc_steps);
+                const bool no_loop_kernel = rc == 1;
+                if (!no_loop_kernel) return rc;
+            }
+            return rollout_steps(stream, mpc_steps);
+        }
     }
-    return launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, !warm_start, warm_start);
+    const int rc = launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, !warm_start, warm_start);
+    if (rc == 0 && mpc_steps > 0) last_rollout_launches = 1;              // (an in-kernel loop: quad, mfmat)
+    return rc;
 }
 
 // Chunks of (a multiple of check_termination) iterations; between chunks the unconverged instances are gathered
@@ -1318,7 +1333,10 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     const bool lean_f64 = precision == 2 && !ke && lean_jit && !(se && extensions_active());
     // ... and, with TINYMPC_HIP_LEAN_WS, its workspace-keeping form for every other solve of that kind (lean_ws)
     const bool lean_ws = !(cold && !save) && lean_ws_takes(idx);
-    const bool lean_call = (ke ? precision == 0 : lean_f64) && lean_ok && ((cold && !save) || lean_ws) && mpc_steps == 0 && !idx &&
+    // ... and, with TINYMPC_HIP_LEAN_LOOP, that form's in-kernel closed loop (rollout_lean_loop: the only launch with mpc_steps
+    // that comes here for the lean kernel)
+    const bool lean_loop = lean_loop_launch && lean_ws && mpc_steps > 0;
+    const bool lean_call = (ke ? precision == 0 : lean_f64) && lean_ok && ((cold && !save) || lean_ws) && (mpc_steps == 0 || lean_loop) && !idx &&
                            ref_mode != REF_PER_INSTANCE && !st.adaptive_rho && max_iter_pass >= 1;
     // the kernels without a state bound take the state dual for zero: a kept workspace whose g may hold something goes to the
     // state-bounded form (whose clamps then clamp nothing) rather than dropping it
@@ -1333,30 +1351,34 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     bool one = false;
     if (lean_call && le) {
         one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_ws;   // (the WS kernels: the 512-register form only)
-        const bool has_sparse = lean_ws ? le->launch_sparse_ws != nullptr : le->launch_sparse != nullptr;
+        const bool has_sparse = lean_loop ? le->launch_sparse_mpc != nullptr : (lean_ws ? le->launch_sparse_ws != nullptr : le->launch_sparse != nullptr);
         const bool can = has_sparse && !sw.lean_dense && ref_mode == REF_ZERO && !lean_knot_bounds;
         form_sp = has_sparse ? le->sp : 0;
-        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, lean_xb, can);
+        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live || lean_loop, lean_xb, can);   // (the loop kernels are tolerance-terminated ones)
     }
     if (lean_call && !le && lean_jit) {
         // the one variant this launch needs (lean_entry.hip.h: launch_lean_v's choices), compiled on first use
         one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_f64 || lean_ws;
         if (2 * N * nx + 3 * N * nu + 50 > 250) one = true;   // (the 256-register form does not hold this horizon)
         form_sp = lean_sp;
-        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live, lean_xb, !sw.lean_dense);
+        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live || lean_loop, lean_xb, !sw.lean_dense);
         // (the one WS calling pattern whose fixed-iteration kernel parks a register runs the tolerance-terminated kernel of the
         // same flags, as the built-in launcher does: lean_entry.hip.h, launch_lean_v)
-        const bool live_v = lean_live || (lean_ws && lean_xb && ref_mode == REF_SHARED && lean_knot_bounds);
+        // (... and so does every in-kernel loop: its kernels are the tolerance-terminated ones)
+        const bool live_v = lean_live || (lean_ws && lean_xb && ref_mode == REF_SHARED && lean_knot_bounds) || lean_loop;
         const int v = (live_v ? LV_LIVE : 0) | (lean_knot_bounds ? 0 : LV_UBK) | (one ? LV_ONE : 0) | (lean_xb ? LV_XB : 0) |
                       (ref_mode == REF_SHARED ? LV_SHARED : 0) | (lean_f64 ? LV_F64 : 0) | (form == LF_SPARSE ? LV_SPARSE : 0) |
-                      (lean_ws ? LV_WS : 0);
+                      (lean_ws ? LV_WS : 0) | (lean_loop ? LV_MPC : 0);
         if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, form == LF_SPARSE ? lean_sp : 0, verbose), le_var_tried[v] = true;
         lk = le_var[v];
+    }
+    if (lean_loop_launch) {   // the loop kernel of this calling pattern, or nothing: the caller falls back to the chain
+        if (!lk || !(form == LF_SPARSE && le ? le->launch_sparse_mpc : lk->launch_mpc)) return 1;
     }
     const bool lean = lk != nullptr;
     last_lean_form = lean ? form : LF_NONE;
     last_lean_cost[0] = lean && form_sp ? lean_cost_sparse(form_sp, nx, nu) : 0;
-    last_lean_cost[1] = !lean ? 0 : (one && !lean_live && !lean_xb) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
+    last_lean_cost[1] = !lean ? 0 : (one && !lean_live && !lean_loop && !lean_xb) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
     if (lean && !le && (!ke || ke->G != 1)) P.bounds = reinterpret_cast<const float *>(d_lean + lean_layout(nx, nu).total);   // (upload_packs)
     P.lean = d_lean;
     P.ws64 = d_ws64;
@@ -1372,7 +1394,8 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     if (profiling && !attached) HIP_TRY(hipEventRecord(ev0, stream));
     if (lean) {
         hipEvent_t a0 = attached ? ev0 : nullptr, a1 = attached ? ev1 : nullptr;
-        if (form == LF_SPARSE && le) HIP_TRY((lean_ws ? le->launch_sparse_ws : le->launch_sparse)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
+        if (lean_loop) HIP_TRY((form == LF_SPARSE && le ? le->launch_sparse_mpc : lk->launch_mpc)(P, true, lean_knot_bounds, lean_xb, stream, a0, a1));
+        else if (form == LF_SPARSE && le) HIP_TRY((lean_ws ? le->launch_sparse_ws : le->launch_sparse)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
         else HIP_TRY((lean_ws ? lk->launch_ws : lk->launch)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
     } else
     HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
@@ -1466,11 +1489,29 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     }
     HIP_TRY(hipGetLastError());
     mpc_steps_last = mpc_steps;
+    last_rollout_launches = mpc_steps;
     if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ev_done, stream));
     ev_wait = ev_done;
     ev_done_pending = true;
     return 0;
+}
+
+// The closed loop as one launch of the lean kernel's in-kernel loop: log buffers as every fused loop has them (launch_pass),
+// the fp64 plant state set up as rollout_steps does (x0d <- x0) and handed to the launch, which leaves x0 and x0d as the
+// chain leaves them.  1: no loop kernel for this solver's calling pattern (no solve was launched; the chain takes the loop).
+int Solver::rollout_lean_loop(hipStream_t stream, int mpc_steps) {
+    if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
+    const long n0 = (long)batch * nx;
+    plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+    HIP_TRY(hipGetLastError());
+    lean_loop_launch = true;
+    x0d_launch = d_x0d;
+    const int rc = launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, false, true);
+    lean_loop_launch = false;
+    x0d_launch = nullptr;
+    if (rc == 0) last_rollout_launches = 1;
+    return rc;
 }
 
 int Solver::solve_status() {
@@ -1668,3 +1709,7 @@ extern "C" int tmpc_lean_last_form(tinympc_solver *s, unsigned long long *patter
     if (form) *form = s->s.last_lean_form;
     return 0;
 }
+
+// (test hook like the one above) the number of solve-kernel launches the solver's last mpc_rollout took: `steps` for the
+// chains of launches, 1 for any in-kernel loop, -1 before any rollout
+extern "C" int tmpc_last_rollout_launches(tinympc_solver *s) { return s ? s->s.last_rollout_launches : -1; }

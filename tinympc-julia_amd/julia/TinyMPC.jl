@@ -217,7 +217,8 @@ end
 # what the loop of examples/rocket_landing_constraints.jl:107-115 passes to set_x_ref / set_u_ref step by step.
 # Supported wherever mpc_rollout is: inside the launch on the transposed-sets kernel (rocket shapes) and on the lanes-per-instance
 # kernels at horizons up to 20 (cartpole shapes; quadrotor N = 20 with TINYMPC_HIP_MFMA_ONESHOT_ONLY=1), launch by launch on the chained loops
-# (quadrotor shapes on the matrix-core kernel; the lean kernel's with TINYMPC_HIP_LEAN_WS=1).  mpc_rollout fails, naming the
+# (quadrotor shapes on the matrix-core kernel; the lean kernel's with TINYMPC_HIP_LEAN_WS=1 — with a sequence also when
+# TINYMPC_HIP_LEAN_LOOP=1 asks for that kernel's in-kernel loop, which takes constant references only).  mpc_rollout fails, naming the
 # condition, with fewer sequence steps than loop steps, per-instance references, adaptive rho, precision 2, a lanes-per-instance
 # entry with a horizon above 20, shapes without a
 # closed loop (stream / generic kernels); a sharded solver (set_gpus > 1) takes no sequence.

@@ -799,6 +799,8 @@ class BatchSolver:
 
     def mpc_rollout(self, steps, stream=None):
         """`steps` fused closed-loop MPC steps in one launch (plant = the family's own A, B).
+        (TINYMPC_HIP_LEAN_WS=1 when the solver is created: cartpole-class shapes on the lean kernel, as a chain of `steps`
+        launches; with TINYMPC_HIP_LEAN_LOOP=1 beside it as one launch of its in-kernel loop — the same results.)
         Returns dict(status, x=(nx, steps, B), u=(nu, steps, B), iter=(steps, B), solved=(steps, B))."""
         st = int(self.lib.tinympc_mpc_rollout(self.h, int(steps), c_vp(stream or 0)))
         if st < 0:
