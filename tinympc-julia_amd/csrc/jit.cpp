@@ -255,19 +255,13 @@ const ConeEntry *jit_trans_for(const Solver &sv, int verbose) {
     return e;
 }
 
-// One variant of the lean kernel (admm_lean.hip.h, the headline's) for a shape without a built-in lean instantiation, compiled at
-// the first launch that needs it.  variant bits: LV_LIVE tolerance-terminated, LV_UBK the input bounds do not depend on the
-// knot, LV_ONE the 512-register form, LV_XB a finite state bound, LV_SHARED shared references, LV_F64 slack / dual state in
-// fp64 (precision 2: the reference's arithmetic end to end at this kernel's speed), LV_SPARSE the sweeps on the model's own
-// (A, B) pattern sp (admm_params.h: lean_pattern_rm) — it joins the unit's name.  The kernel holds one lane's
-// whole solve in registers and its coefficients in scalar registers: 32 coefficient doubles and ~490 registers at most —
-// cartpole-class systems ((4,1) to N = 36, (3,2), (2,x)); anything else: nullptr, the quad / stream kernels as before.
 // Whether a workspace-keeping variant (LV_WS) of the shape fits a workgroup's 160 KiB of LDS — what admm_lean.hip.h declares:
 // the four wavefronts' staging (wide_stage_width / wave_stage_floats_wide, admm_quad.hip.h), the per-knot bounds and reference
 // terms, and, tolerance-terminated, every lane's parked previous slack: 256 x (nx N padded to an odd number of float4 +
 // nu (N-1) | 1) floats.  Cartpole-class (4,1): tolerance-terminated to N = 24, fixed-iteration wherever the registers hold it.
-// Asked before a unit is compiled (a compile that cannot succeed costs every process ten seconds) and by the routing
-// (solver.hip: lean_ws_takes), so that such a solver's mpc_rollout keeps the quad kernel's fused loop.
+// The one LDS rule: lean_plan (kernels.hip) asks it, with the flags the variant will carry, before anything is compiled (a
+// compile that cannot succeed costs every process ten seconds), so that a solver beyond it keeps its quad kernel, fused
+// closed loop included.
 // (The in-kernel closed loop, LV_MPC, adds nothing to this: between its steps v and z stay in the parked rows the
 // tolerance-terminated form has anyway — `live` is then true whatever the tolerances — and y, d, g go through the staging.)
 bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool knot_bounds) {
@@ -288,28 +282,24 @@ bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool k
     return bytes <= (size_t)160 * 1024;
 }
 
+// One variant of the lean kernel (admm_lean.hip.h, the headline's) for a shape without a built-in lean instantiation, compiled at
+// the first launch that needs it: the LV_* bits lean_plan decided (solver.h), LV_SPARSE on the model's own (A, B) pattern sp
+// (admm_params.h: lean_pattern_rm) — it joins the unit's name.  The kernel holds one lane's whole solve in registers and
+// its coefficients in scalar registers: 32 coefficient doubles and ~490 registers at most — cartpole-class systems ((4,1) to
+// N = 36, (3,2), (2,x)); anything else: nullptr, the quad / stream kernels as before.
 const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, int verbose) {
     if (std::getenv("TINYMPC_HIP_NO_JIT")) return nullptr;
     if (nx < 1 || nu < 1 || N < 3 || lean_layout(nx, nu).padded > 32) return nullptr;
     if (((variant & LV_SPARSE) != 0) != (sp != 0) || (sp && (nx > 4 || nu > 4))) return nullptr;
     const bool one = (variant & LV_ONE) != 0, f64 = (variant & LV_F64) != 0, xb = (variant & LV_XB) != 0;
-    const bool ws = (variant & LV_WS) != 0, mpc = (variant & LV_MPC) != 0;
-    if ((f64 && !one) || (f64 && ws)) return nullptr;
-    if (mpc && !(ws && one && (variant & LV_LIVE))) return nullptr;   // (the loop: the tolerance-terminated workspace-keeping form only)
-    if (ws && !lean_ws_fits(nx, nu, N, (variant & LV_LIVE) != 0, xb, (variant & LV_SHARED) != 0, !(variant & LV_UBK))) return nullptr;
     const int regs = f64 ? (xb ? 4 : 2) * N * nx + 6 * N * nu + 50 : 2 * N * nx + (one ? 4 : 3) * N * nu + 50;
     if (regs > (f64 ? 450 : (one ? 490 : 250))) return nullptr;   // (fp64 state with a state bound at N = 20: 490 values, 463 of them spilled)
     std::ostringstream name, src;
     name << "lean_" << nx << "_" << nu << "_" << N << "_v" << variant;
     if (sp) name << "_sp" << std::hex << (unsigned long long)sp << std::dec;
-    auto tf = [&](int bit) { return (variant & bit) ? "true" : "false"; };
-    // (LV_WS: the workspace-keeping form has a macro of its own, fp32 state only; LV_MPC: its in-kernel closed loop likewise)
-    src << "// specialised at the first solve by jit.cpp\n#include \"lean_entry.hip.h\"\n"
-        << (mpc ? "TMPC_DEFINE_LEAN_JIT_ENTRY_MPC" : (ws ? "TMPC_DEFINE_LEAN_JIT_ENTRY_WS" : "TMPC_DEFINE_LEAN_JIT_ENTRY_SP"))
-        << "(\"lean<" << nx << "," << nu << "," << N << (f64 ? ";f64" : "") << ">\", " << nx << ", " << nu << ", " << N << ", " << tf(LV_LIVE) << ", " << tf(LV_UBK)
-        << ", " << tf(LV_ONE) << ", " << tf(LV_XB) << ", " << ((variant & LV_SHARED) ? "tmpc::REF_SHARED" : "tmpc::REF_ZERO") << ", ";
-    if (!ws) src << (f64 ? "double" : "float") << ", ";
-    src << "0x" << std::hex << (unsigned long long)sp << std::dec << "ull)\n";
+    src << "// specialised at the first solve by jit.cpp\n#include \"lean_entry.hip.h\"\nTMPC_DEFINE_LEAN_JIT_VARIANT(\"lean<" << nx << "," << nu
+        << "," << N << (f64 ? ";f64" : "") << ">\", " << nx << ", " << nu << ", " << N << ", " << variant << ", " << (f64 ? "double" : "float") << ", 0x"
+        << std::hex << (unsigned long long)sp << std::dec << "ull)\n";
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_units.find(name.str());
     if (it != g_units.end()) return static_cast<const LeanEntry *>(it->second);

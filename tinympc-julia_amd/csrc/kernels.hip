@@ -115,6 +115,83 @@ bool build_lean_pack(const Solver &sv, std::vector<double> &out) {
     return true;
 }
 
+// The one-lane-per-instance bound pack — [knot][x_min x_max u_min u_max], then diag(Q) + rho, diag(R) + rho (quad_entry.hip.h:
+// build_quad_bounds with G = 1) — behind the coefficient doubles of `out`, for a solver whose selected entry keeps its bounds
+// in another layout (four lanes per instance, the stream kernel's): launch_pass points P.bounds there
+void append_lean_bounds(const Solver &sv, std::vector<double> &out) {
+    constexpr float kInf = std::numeric_limits<float>::infinity();
+    const int nx = sv.nx, nu = sv.nu, N = sv.N, BW = 2 * nx + 2 * nu;
+    std::vector<float> lb((size_t)N * BW + nx + nu + 1, 0.f);
+    for (int k = 0; k < N; ++k) {
+        float *p = lb.data() + (size_t)k * BW;
+        for (int r = 0; r < nx; ++r) {
+            p[r] = sv.st.en_state_bound ? (float)sv.x_min[r + (size_t)k * nx] : -kInf;
+            p[nx + r] = sv.st.en_state_bound ? (float)sv.x_max[r + (size_t)k * nx] : kInf;
+        }
+        for (int a = 0; a < nu; ++a) {
+            const bool on = sv.st.en_input_bound && k < N - 1;
+            p[2 * nx + a] = on ? (float)sv.u_min[a + (size_t)k * nu] : -kInf;
+            p[2 * nx + nu + a] = on ? (float)sv.u_max[a + (size_t)k * nu] : kInf;
+        }
+    }
+    for (int r = 0; r < nx; ++r) lb[(size_t)N * BW + r] = (float)sv.cache.Qd[r];
+    for (int a = 0; a < nu; ++a) lb[(size_t)N * BW + nx + a] = (float)sv.cache.Rd[a];
+    const size_t at = out.size();
+    out.resize(at + (lb.size() + 1) / 2, 0.0);
+    std::memcpy(out.data() + at, lb.data(), lb.size() * sizeof(float));
+}
+
+// The lean kernel takes the launches of a one-lane-per-instance quad entry (fp64 recurrences, fp32 state), or — precision 2, no
+// quad entry — of a shape it holds in its fp64-state form, when the family's pack qualifies, the references are zero or shared,
+// rho is the family's, every slot is an instance and there is an iteration to run:
+//   one-shot solves (cold start, nothing of the workspace kept): always;
+//   every other solve: TINYMPC_HIP_LEAN_WS, on the workspace-keeping form (fp32 state only), where the entry has it or a
+//     specialised variant fits the LDS (lean_ws_fits) — a shape beyond it stays on its quad kernel, fused closed loop included;
+//   mpc_steps in one launch: TINYMPC_HIP_LEAN_LOOP beside it and the caller asking for the loop (in.loop), which in turn
+//     gets the loop kernel or nothing.
+// The variant then follows, every normalisation once:
+//   XB    a finite state bound, or a kept workspace whose state dual may hold something (the kernels without a state bound
+//         take g for zero; the state-bounded form's clamps then clamp nothing);
+//   LIVE  positive tolerances; every in-kernel loop; the WS pattern XB + shared references + per-knot input bounds, whose
+//         fixed-iteration kernel is not built (lean_entry.hip.h);
+//   ONE   the 512-register form: at most one workgroup per CU (= one wavefront per SIMD); every LIVE, WS and fp64-state
+//         kernel; TINYMPC_HIP_LEAN_ONE; a specialised shape the 256-register form does not hold.  (Fixed-iteration solves of
+//         batch 131 072 in the 256- / 512-register form: 0.46 / 0.69 against 0.47 / 0.61 ms — scripts/lean_time.py "big")
+//   SPARSE where a kernel's (A, B) pattern covers the model's and costs less per knot than the dense form it replaces
+//         (lean_pick_form; TINYMPC_HIP_LEAN_DENSE: never).  The built-in sparse kernels take zero references and uniform
+//         input bounds; a specialised variant carries the model's own pattern, any calling pattern.
+LeanPlan lean_plan(const LeanPlanIn &in) {
+    LeanPlan p;
+    const int nx = in.nx, nu = in.nu, N = in.N;
+    const bool f64 = in.precision == 2 && in.quad_G == 0 && in.lean_jit && !in.stream_ext;
+    if (!(in.quad_G ? in.precision == 0 : f64) || !in.lean_ok || !(in.builtin || in.lean_jit)) return p;
+    if (in.indexed || in.ref_mode == REF_PER_INSTANCE || in.adaptive_rho || in.iters < 1) return p;
+    const bool ws = !(in.cold && !in.save);
+    if (ws && !(in.sw_ws && in.quad_G > 0 && in.quad_G < 16 && in.precision == 0 && (!in.builtin || (in.kinds & LK_WS)))) return p;
+    const bool mpc = in.loop && in.sw_loop && ws && in.mpc_steps > 0;
+    if ((in.loop || in.mpc_steps > 0) && !mpc) return p;
+    const bool xb = in.state_bounds || (ws && in.g_maybe_nonzero), shared = in.ref_mode == REF_SHARED;
+    const bool live = in.live || mpc || (ws && xb && shared && in.knot_bounds);
+    const bool one = live || ws || f64 || in.sw_one || (in.slots + 255) / 256 <= in.cus ||
+                     (!in.builtin && 2 * N * nx + 3 * N * nu + 50 > 250);
+    if (ws && !in.builtin && !lean_ws_fits(nx, nu, N, live, xb, shared, in.knot_bounds)) return p;
+    bool sparse_allowed = !in.sw_dense;
+    p.sp = in.model_sp;
+    if (in.builtin) {
+        const bool has = (in.kinds & (mpc ? LK_SPARSE_MPC : (ws ? LK_SPARSE_WS : LK_SPARSE))) != 0;
+        p.sp = has ? in.builtin_sp : 0;
+        sparse_allowed = sparse_allowed && has && in.ref_mode == REF_ZERO && !in.knot_bounds;
+    }
+    p.form = lean_pick_form(nx, nu, p.sp, in.model_sp, one, live, xb, sparse_allowed);
+    if (mpc && in.builtin && !(in.kinds & (p.form == LF_SPARSE ? LK_SPARSE_MPC : LK_MPC))) return LeanPlan();
+    p.take = true;
+    p.variant = (live ? LV_LIVE : 0) | (in.knot_bounds ? 0 : LV_UBK) | (one ? LV_ONE : 0) | (xb ? LV_XB : 0) | (shared ? LV_SHARED : 0) |
+                (f64 ? LV_F64 : 0) | (p.form == LF_SPARSE ? LV_SPARSE : 0) | (ws ? LV_WS : 0) | (mpc ? LV_MPC : 0);
+    p.cost_sparse = p.sp ? lean_cost_sparse(p.sp, nx, nu) : 0;
+    p.cost_dense = (one && !live && !xb) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
+    return p;
+}
+
 uint64_t lean_pattern(const Mat &A, const Mat &B) {
     const int nx = A.r, nu = B.c;
     if (nx < 1 || nu < 1 || nx > 4 || nu > 4) return 0;
@@ -128,7 +205,7 @@ uint64_t lean_pattern(const Mat &A, const Mat &B) {
 
 }  // namespace tmpc
 
-// (test hooks, not part of the public boundary include/tinympc_hip.h: the lean kernel's sparse-form routing, Solver::launch_pass)
+// (test hooks, not part of the public boundary include/tinympc_hip.h: the lean kernel's routing, lean_plan)
 // the pattern of row-major A [nx][nx], B [nx][nu]; the per-knot fp64 costs {sparse of sp, Hessenberg, dense}; the coverage
 // rule; the form a launch would take; the pattern of the built-in entry of a shape (0: none, or no sparse kernels)
 extern "C" unsigned long long tmpc_lean_pattern(int nx, int nu, const double *A, const double *B) {
@@ -145,7 +222,28 @@ extern "C" int tmpc_lean_pick_form(int nx, int nu, unsigned long long built, uns
 }
 extern "C" unsigned long long tmpc_lean_builtin_pattern(int nx, int nu, int N) {
     const tmpc::LeanEntry *e = tmpc::find_lean_kernel(nx, nu, N);
-    return (e && e->launch_sparse) ? e->sp : 0;
+    return (e && (e->kinds & tmpc::LK_SPARSE)) ? e->sp : 0;
+}
+// lean_plan on LeanPlanIn's fields in their order, the two patterns apart; out: take, variant, form, the two costs
+extern "C" int tmpc_lean_plan(const int *in, int n_in, unsigned long long builtin_sp, unsigned long long model_sp, int *out5,
+                              unsigned long long *weighed) {
+    if (!in || n_in != 28 || !out5) return -1;
+    tmpc::LeanPlanIn q;
+    int i = 0;
+    q.nx = in[i++], q.nu = in[i++], q.N = in[i++];
+    q.builtin = in[i++] != 0, q.kinds = in[i++], q.builtin_sp = builtin_sp;
+    q.lean_jit = in[i++] != 0, q.lean_ok = in[i++] != 0, q.model_sp = model_sp, q.knot_bounds = in[i++] != 0;
+    q.quad_G = in[i++], q.precision = in[i++];
+    q.sw_one = in[i++] != 0, q.sw_dense = in[i++] != 0, q.sw_ws = in[i++] != 0, q.sw_loop = in[i++] != 0;
+    q.slots = in[i++], q.iters = in[i++], q.mpc_steps = in[i++];
+    q.cold = in[i++] != 0, q.save = in[i++] != 0, q.indexed = in[i++] != 0, q.adaptive_rho = in[i++] != 0;
+    q.ref_mode = in[i++];
+    q.loop = in[i++] != 0, q.state_bounds = in[i++] != 0, q.g_maybe_nonzero = in[i++] != 0, q.live = in[i++] != 0, q.stream_ext = in[i++] != 0;
+    q.cus = in[i++];
+    const tmpc::LeanPlan p = tmpc::lean_plan(q);
+    out5[0] = p.take ? 1 : 0, out5[1] = p.variant, out5[2] = p.form, out5[3] = p.cost_sparse, out5[4] = p.cost_dense;
+    if (weighed) *weighed = p.sp;
+    return 0;
 }
 
 namespace tmpc {

@@ -40,40 +40,33 @@ const KernelEntry *find_quad_kernel(int nx, int nu, int N, int group = -1);
 const KernelEntry *select_quad_kernel(int nx, int nu, int N, int batch);
 // the matrix-core kernel of the shape, for one-shot solves (nullptr: not instantiated)
 const KernelEntry *find_mfma_kernel(int nx, int nu, int N);
-// One instantiation of the lean kernel (admm_lean.hip.h): the one-lane-per-instance quad entry's one-shot solves (cold start,
-// workspace not kept) with zero or shared references and fp64 recurrences run there — the benchmark's calling pattern.
+// One entry of the lean kernel (admm_lean.hip.h): the one-lane-per-instance quad entry's solves with zero or shared
+// references and fp64 recurrences run there — the benchmark's calling pattern.  Which of its instantiations
+// admm_lean_kernel<LIVE, UBK, ONE, XB, REFS, ST, SP, WS, MPC> a launch runs is the variant, a set of LV_* bits that lean_plan
+// (below) decides and nothing else: LV_LIVE tolerance-terminated, LV_UBK the input bounds do not depend on the knot, LV_ONE the
+// 512-register form (one wavefront per SIMD), LV_XB the state-bounded form, LV_SHARED shared references, LV_F64 slack / dual
+// state in fp64 (precision 2), LV_SPARSE the sweeps on the pattern sp, LV_WS the workspace-keeping form (warm starts, kept
+// workspace, the chained closed loop), LV_MPC its in-kernel closed loop (P.mpc_steps warm solves and plant steps in one launch).
+enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_WS = 128, LV_MPC = 256, LV_COUNT = 512 };
+// the kinds of kernel a built-in entry carries beside its dense one-shot ones
+enum { LK_SPARSE = 1, LK_WS = 2, LK_SPARSE_WS = 4, LK_MPC = 8, LK_SPARSE_MPC = 16, LK_ALL = 31 };
+using LeanLaunch = hipError_t (*)(const AdmmParams &, int variant, hipStream_t, hipEvent_t ev0, hipEvent_t ev1);
 struct LeanEntry {
     int nx, nu, N;
     const char *name;
-    // ev0 / ev1: timing events carried by the kernel's own dispatch packet (its start and its end); null: none
-    hipError_t (*launch)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0, hipEvent_t ev1);
-    uint64_t sp = 0;   // the (A, B) pattern of the sparse kernels (admm_params.h: lean_pattern_rm): launch_sparse's, or a
-                       // specialised variant's own (launch); 0: none
-    hipError_t (*launch_sparse)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
-                                hipEvent_t ev1) = nullptr;
-    // the workspace-keeping kernels (admm_lean.hip.h, WS: warm starts, kept workspace, the chained closed loop), dense and of
-    // the pattern sp; null: the entry has none (a specialised LV_WS variant carries its one kernel in launch_ws)
-    hipError_t (*launch_ws)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
-                            hipEvent_t ev1) = nullptr;
-    hipError_t (*launch_sparse_ws)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
-                                   hipEvent_t ev1) = nullptr;
-    // the in-kernel closed loop (admm_lean.hip.h, MPC: P.mpc_steps warm solves and plant steps in one launch), dense and of
-    // the pattern sp; null: the entry has none (a specialised LV_MPC variant carries its one kernel in launch_mpc)
-    hipError_t (*launch_mpc)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
-                             hipEvent_t ev1) = nullptr;
-    hipError_t (*launch_sparse_mpc)(const AdmmParams &, bool live, bool knot_bounds, bool state_bounds, hipStream_t, hipEvent_t ev0,
-                                    hipEvent_t ev1) = nullptr;
+    uint64_t sp;   // the (A, B) pattern of its sparse kernels (admm_params.h: lean_pattern_rm), 0: none
+    int kinds;     // LK_*; a specialised unit: 0 (it carries the one variant it was compiled for)
+    // runs the kernel of `variant`; hipErrorNotSupported: the entry has no such kernel (lean_plan sends none).  ev0 / ev1:
+    // timing events carried by the kernel's own dispatch packet (its start and its end); null: none
+    LeanLaunch launch;
 };
 const LeanEntry *find_lean_kernel(int nx, int nu, int N);
 // ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel);
-// LV_SPARSE: on the model's own pattern sp; LV_WS: the workspace-keeping form (fp32 state only); LV_MPC: its in-kernel closed
-// loop (with LV_WS, LV_LIVE and LV_ONE)
-enum { LV_LIVE = 1, LV_UBK = 2, LV_ONE = 4, LV_XB = 8, LV_SHARED = 16, LV_F64 = 32, LV_SPARSE = 64, LV_WS = 128, LV_MPC = 256, LV_COUNT = 512 };
+// sp: the model's own pattern with LV_SPARSE, else 0
 const LeanEntry *jit_lean_for(int nx, int nu, int N, int variant, uint64_t sp, int verbose);
-// the lean kernel's 512-register form (one wavefront per SIMD): at most one workgroup per CU, tolerance-terminated solves,
-// TINYMPC_HIP_LEAN_ONE (lean_entry.hip.h: launch_lean_v)
+// whether a workspace-keeping variant of the shape fits a workgroup's LDS (jit.cpp: the one rule)
+bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool knot_bounds);
 int device_cu_count();   // CU count of the current device (cached per device: a sharded handle launches on several)
-inline bool lean_one_form(int batch, bool live, bool force) { return (batch + 255) / 256 <= device_cu_count() || live || force; }
 // The sweeps a lean launch runs: the dense plain form, controller-Hessenberg (fixed iterations, no state bound, 512 registers)
 // or the sparse form of a pattern.  A kernel built for pattern `built` takes a model of pattern `model` when it covers it and
 // costs fewer fp64 instructions per knot than the form it replaces.
@@ -84,10 +77,46 @@ inline int lean_pick_form(int nx, int nu, uint64_t built, uint64_t model, bool o
     if (sparse_allowed && lean_pattern_covers(built, model) && lean_cost_sparse(built, nx, nu) < dense) return LF_SPARSE;
     return hb ? LF_HB : LF_PLAIN;
 }
+// THE routing of the lean kernel: whether a launch runs there and as which variant — the one place that decides it
+// (kernels.hip).  Scalars in, scalars out; nothing is allocated and nothing asked of the device (cus comes in).
+struct LeanPlanIn {
+    int nx = 0, nu = 0, N = 0;
+    // what the solver holds
+    bool builtin = false;            // a built-in entry of the shape, with
+    int kinds = 0;                   // ... these kinds of kernel (LK_*) and
+    uint64_t builtin_sp = 0;         // ... this pattern; otherwise
+    bool lean_jit = false;           // ... single variants are specialised at the launches that need them
+    bool lean_ok = false;            // the family qualifies (build_lean_pack)
+    uint64_t model_sp = 0;           // the model's pattern (lean_pattern)
+    bool knot_bounds = false;        // the input bounds depend on the knot
+    int quad_G = 0;                  // lanes per instance of the selected quad entry, 0: none is selected
+    int precision = 0;
+    bool sw_one = false, sw_dense = false, sw_ws = false, sw_loop = false;   // TINYMPC_HIP_LEAN_ONE / _DENSE / _WS / _LOOP
+    // the launch
+    int slots = 0, iters = 0, mpc_steps = 0;
+    bool cold = false, save = false, indexed = false, adaptive_rho = false;
+    int ref_mode = REF_ZERO;
+    bool loop = false;               // the in-kernel closed loop or nothing (rollout_lean_loop)
+    bool state_bounds = false;       // some enabled state bound is finite
+    bool g_maybe_nonzero = false;    // the kept workspace's state dual may hold something
+    bool live = false;               // both tolerances positive
+    bool stream_ext = false;         // the stream entry is selected and extensions are active (precision 2: they go there)
+    int cus = 256;
+};
+struct LeanPlan {
+    bool take = false;
+    int variant = 0;                 // LV_*
+    int form = LF_NONE;              // LF_*
+    uint64_t sp = 0;                 // the pattern weighed against the model's: the built-in sparse kernels' or the model's own
+    int cost_sparse = 0, cost_dense = 0;   // per-knot fp64 costs: of sp, and of the dense form it replaces (tmpc_lean_last_form)
+};
+LeanPlan lean_plan(const LeanPlanIn &);
 // the (A, B) pattern of a solver's model (0: nx or nu above 4)
 uint64_t lean_pattern(const Mat &A, const Mat &B);
 // the lean kernel's fp64 pack (lean_layout); false when the family does not qualify (cache.AmBKt is not (A - B Kinf)')
 bool build_lean_pack(const Solver &, std::vector<double> &);
+// ... and the one-lane-per-instance bound pack appended to it, for a solver whose selected entry keeps another layout
+void append_lean_bounds(const Solver &, std::vector<double> &);
 // One (nx, nu) instantiation of the run-time-horizon stream kernel (admm_streamg.hip.h).
 struct StreamEntry {
     int nx, nu;
@@ -218,8 +247,8 @@ struct Solver {
     const StreamEntry *se = nullptr;  // run-time-horizon stream kernel, or
     const ConeEntry *ce = nullptr;    // LDS-resident matrix-core kernel (one-shot solves), or (all null) the generic kernel
     std::string kernel_name;
-    // the lean kernel of the shape (admm_lean.hip.h): takes the one-lane-per-instance quad entry's one-shot solves without an
-    // active state bound (launch_pass decides per launch); its pack, and whether the family qualifies (build_lean_pack)
+    // the lean kernel of the shape (admm_lean.hip.h; lean_plan decides per launch); its pack, and whether the family
+    // qualifies (build_lean_pack)
     const LeanEntry *le = nullptr;
     bool lean_jit = false;                // no built-in lean instantiation: single variants specialised at the launches that need them
     const LeanEntry *le_var[LV_COUNT] = {};
@@ -320,25 +349,35 @@ struct Solver {
     int ensure_extension_buffers();
     int reset();
     int solve_async(hipStream_t stream, int mpc_steps = 0);
-    // one kernel launch over `n_slots` instances (idx: their ids, NULL = 0..n_slots-1) for at most `max_iter_pass`
-    // iterations, the instances having done `iter_offset` already
-    bool lean_ws_takes(const int *idx) const;     // TINYMPC_HIP_LEAN_WS: warm / saving solves on the lean kernel (launch_pass)
-    int launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n_slots, int iter_offset, int max_iter_pass,
-                    bool cold, bool save);
+    // one kernel launch over `slots` instances (idx: their ids, NULL = 0..slots-1) for at most `iters` iterations, the
+    // instances having done `iter_offset` already
+    struct Pass {
+        const int *idx = nullptr;
+        int slots = 0, iter_offset = 0, iters = 0;
+        bool cold = false, save = false;
+        int mpc_steps = 0;
+        const double *x0d = nullptr;                        // the fp64 plant state of a closed loop stepped outside the quad kernel
+        const float *xref = nullptr, *uref = nullptr;       // shared references where not the solver's own (a step of a reference sequence)
+        bool loop = false;                                  // the lean kernel's in-kernel closed loop, or nothing
+    };
+    static constexpr int NO_LOOP_KERNEL = 1;                // launch_pass with Pass::loop: nothing was launched, the chain takes the loop
+    Pass whole_batch(bool cold, bool save, int mpc_steps = 0) const;
+    int launch_pass(hipStream_t stream, const Pass &);
+    LeanPlan plan_lean(const Pass &) const;                 // lean_plan of this solver and that launch
+    void fill_params(AdmmParams &P, const Pass &) const;
+    int ensure_mpc_log(int mpc_steps);                      // the closed loops' log buffers
+    int record_done(hipStream_t stream, hipEvent_t carried = nullptr);   // the completion event every getter waits for
     // tolerance-terminated solves of big batches in chunks of `chunk_iters` iterations: after each chunk the
     // instances still iterating are compacted, so wavefronts do not idle behind their slowest instance
     int solve_chunked(hipStream_t stream);
     // closed loop on the matrix-core kernel: per step one WS launch and a plant-update kernel, stream-ordered, the plant
     // state kept in fp64 on the device between steps (what the quad kernel's fused loop keeps in registers)
     int rollout_steps(hipStream_t stream, int mpc_steps);
-    // TINYMPC_HIP_LEAN_LOOP: the same loop as ONE launch of the lean kernel's in-kernel loop (1: no loop kernel for this
+    // TINYMPC_HIP_LEAN_LOOP: the same loop as ONE launch of the lean kernel's in-kernel loop (NO_LOOP_KERNEL: none for this
     // calling pattern, nothing launched)
     int rollout_lean_loop(hipStream_t stream, int mpc_steps);
-    bool lean_loop_launch = false;                // handed to the next launch_pass: the lean kernel's loop form, or nothing
     int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout (-1: none has run)
     double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B] column-major fp64; [B][nx] plant state
-    const double *x0d_launch = nullptr;           // handed to the next launch_pass
-    const float *xref_launch = nullptr, *uref_launch = nullptr;   // ... and its shared references, where not the solver's own (a step of a reference sequence)
     int check_ref_sequence(int mpc_steps) const;
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};

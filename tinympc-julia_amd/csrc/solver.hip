@@ -676,7 +676,7 @@ int Solver::upload_packs() {
     // the lean kernel's own pack where the selected entry has one lane per instance and the shape a lean instantiation
     le = (ke && ke->G == 1 && lean_enabled) ? find_lean_kernel(nx, nu, N) : nullptr;
     // (a shape without one — cartpole at another horizon, a unit specialised at setup with four lanes per instance: where one
-    // lane per instance is the batch's variant, launch_pass specialises the variant it needs, jit_lean_for)
+    // lane per instance is the batch's variant, launch_pass specialises the variant lean_plan asks for, jit_lean_for)
     lean_jit = !le && ke && lean_enabled && !sw.no_jit && !no_specialise && (ke->G == 1 || (ke->jit && ke->G < 16 && batch >= 20480));
     // precision 2 (the generic kernel's fp64-state form, one lane per instance like this one): one-shot solves of a shape the lean
     // kernel holds run on ITS fp64-state form, specialised on request — the reference's digits at the headline kernel's speed
@@ -688,31 +688,7 @@ int Solver::upload_packs() {
     if (le || lean_jit) {
         std::vector<double> lp;
         if (build_lean_pack(*this, lp)) {
-            if (!le && (!ke || ke->G != 1)) {
-                // the lean kernel reads the one-lane-per-instance bound pack — [knot][x_min x_max u_min u_max], then diag(Q) + rho,
-                // diag(R) + rho (quad_entry.hip.h: build_quad_bounds with G = 1); the selected entry's pack is four lanes per
-                // instance: the lean one rides behind the coefficient doubles (launch_pass points P.bounds there)
-                constexpr float kInf = std::numeric_limits<float>::infinity();
-                const int BW = 2 * nx + 2 * nu;
-                std::vector<float> lb((size_t)N * BW + nx + nu + 1, 0.f);
-                for (int k = 0; k < N; ++k) {
-                    float *p = lb.data() + (size_t)k * BW;
-                    for (int r = 0; r < nx; ++r) {
-                        p[r] = st.en_state_bound ? (float)x_min[r + (size_t)k * nx] : -kInf;
-                        p[nx + r] = st.en_state_bound ? (float)x_max[r + (size_t)k * nx] : kInf;
-                    }
-                    for (int a = 0; a < nu; ++a) {
-                        const bool on = st.en_input_bound && k < N - 1;
-                        p[2 * nx + a] = on ? (float)u_min[a + (size_t)k * nu] : -kInf;
-                        p[2 * nx + nu + a] = on ? (float)u_max[a + (size_t)k * nu] : kInf;
-                    }
-                }
-                for (int r = 0; r < nx; ++r) lb[(size_t)N * BW + r] = (float)cache.Qd[r];
-                for (int a = 0; a < nu; ++a) lb[(size_t)N * BW + nx + a] = (float)cache.Rd[a];
-                const size_t at = lp.size();
-                lp.resize(at + (lb.size() + 1) / 2, 0.0);
-                std::memcpy(lp.data() + at, lb.data(), lb.size() * sizeof(float));
-            }
+            if (!le && (!ke || ke->G != 1)) append_lean_bounds(*this, lp);   // (the selected entry's bound pack is not the one-lane one)
             if (dev_alloc(d_lean, lp.size())) return -1;
             HIP_TRY(hipMemcpy(d_lean, lp.data(), lp.size() * sizeof(double), hipMemcpyHostToDevice));
             lean_ok = true;
@@ -1117,21 +1093,22 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     // fp64 between them) instead of the quad kernel's in-kernel loop; with a reference sequence each launch gets its step's
     if (mpc_steps > 0 && sw.lean_ws && warm_start) {
         if ((packs_dirty && upload_packs()) || upload_refs()) return -1;   // (the lean entry and its pack are found there; the reference mode here)
-        if (lean_ws_takes(nullptr)) {
+        Pass step = whole_batch(false, true);
+        step.iters = 1;                                                    // (the calling pattern, whatever the iteration count)
+        if (plan_lean(step).take) {
             // ... and with TINYMPC_HIP_LEAN_LOOP beside it, the whole loop as ONE launch of the lean kernel's in-kernel loop
             // (admm_lean.hip.h, MPC).  What keeps the chain, each by name: per-step references (the kernel stages the shared
             // references once per launch), and a calling pattern without a loop kernel — the entry has none for it, or its
-            // specialisation was refused or failed (rollout_lean_loop returns 1)
+            // specialisation was refused or failed
             const bool ref_sequence = ref_seq_steps > 0;
             if (sw.lean_loop && !ref_sequence) {
                 const int rc = rollout_lean_loop(stream, mpc_steps);
-                const bool no_loop_kernel = rc == 1;
-                if (!no_loop_kernel) return rc;
+                if (rc != NO_LOOP_KERNEL) return rc;
             }
             return rollout_steps(stream, mpc_steps);
         }
     }
-    const int rc = launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, !warm_start, warm_start);
+    const int rc = launch_pass(stream, whole_batch(!warm_start, warm_start, mpc_steps));
     if (rc == 0 && mpc_steps > 0) last_rollout_launches = 1;              // (an in-kernel loop: quad, mfmat)
     return rc;
 }
@@ -1151,7 +1128,10 @@ int Solver::solve_chunked(hipStream_t stream) {
     int n = batch, offset = 0, cur = 0;
     for (;;) {
         const int iters = std::min(chunk, st.max_iter - offset);
-        if (launch_pass(stream, 0, idx, n, offset, iters, offset == 0 && !warm_start, true)) return -1;
+        Pass chunk_pass;
+        chunk_pass.idx = idx, chunk_pass.slots = n, chunk_pass.iter_offset = offset, chunk_pass.iters = iters;
+        chunk_pass.cold = offset == 0 && !warm_start, chunk_pass.save = true;
+        if (launch_pass(stream, chunk_pass)) return -1;
         offset += iters;
         HIP_TRY(hipMemcpyAsync(h_gstat, d_gstat, GSTAT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         const bool last = offset >= st.max_iter;
@@ -1182,49 +1162,41 @@ int Solver::solve_chunked(hipStream_t stream) {
     return 0;
 }
 
-// Whether the workspace-keeping lean kernels (admm_lean.hip.h, WS; TINYMPC_HIP_LEAN_WS) take this solver's warm / saving
-// solves: a lanes-per-instance entry, fp32 state, a family the lean pack holds, zero or shared references, the family's rho —
-// and a kernel: the one-lane-per-instance entry's built-in ones, or one variant specialised on request where the one-shot
-// solves of the shape get theirs that way (lean_jit, upload_packs; every quad variant keeps the workspace in the same layout)
-// (jit.cpp: registers and LDS of the variant this solver's settings ask for — a shape beyond them stays where it is, its
-// mpc_rollout on the quad kernel's fused loop)
-bool lean_ws_fits(int nx, int nu, int N, bool live, bool xb, bool shared, bool knot_bounds);
-bool Solver::lean_ws_takes(const int *idx) const {
-    if (!(sw.lean_ws && ke && ke->G < 16 && precision == 0 && lean_ok && !idx && ref_mode != REF_PER_INSTANCE && !st.adaptive_rho)) return false;
-    if (le) return le->launch_ws != nullptr;
-    const bool xb = state_bounds_active || g_maybe_nonzero, shared = ref_mode == REF_SHARED;
-    const bool live = (st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0) || (xb && shared && lean_knot_bounds);
-    return lean_jit && lean_ws_fits(nx, nu, N, live, xb, shared, lean_knot_bounds);
+Solver::Pass Solver::whole_batch(bool cold, bool save, int mpc_steps) const {
+    Pass a;
+    a.slots = batch, a.iters = st.max_iter, a.cold = cold, a.save = save, a.mpc_steps = mpc_steps;
+    return a;
 }
 
-int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n_slots, int iter_offset, int max_iter_pass,
-                        bool cold, bool save) {
-    if (mpc_steps > 0) {
-        if (!ke && !(ce && ce->ws)) {
-            set_error("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
-            return -1;
-        }
-        if (!warm_start) {
-            set_error("mpc_rollout needs the persistent workspace (set_warm_start(1))");
-            return -1;
-        }
-        if (mpc_cap < mpc_steps) {
-            const size_t n = (size_t)batch * mpc_steps;
-            if (dev_alloc(d_mpc_x, n * nx) || dev_alloc(d_mpc_u, n * nu) || dev_alloc(d_mpc_iter, n)) return -1;
-            mpc_cap = mpc_steps;
-        }
-        mpc_steps_last = mpc_steps;
-    }
-    if (packs_dirty && upload_packs()) return -1;
-    if (upload_refs()) return -1;
-    AdmmParams P;
+// lean_plan (solver.h) of this solver and one launch: what the solver holds and what the launch asks, as scalars
+LeanPlan Solver::plan_lean(const Pass &a) const {
+    LeanPlanIn in;
+    in.nx = nx, in.nu = nu, in.N = N;
+    in.builtin = le != nullptr, in.kinds = le ? le->kinds : 0, in.builtin_sp = le ? le->sp : 0;
+    in.lean_jit = lean_jit, in.lean_ok = lean_ok, in.model_sp = lean_sp, in.knot_bounds = lean_knot_bounds;
+    in.quad_G = ke ? ke->G : 0, in.precision = precision;
+    in.sw_one = sw.lean_one, in.sw_dense = sw.lean_dense, in.sw_ws = sw.lean_ws, in.sw_loop = sw.lean_loop;
+    in.slots = a.slots, in.iters = a.iters, in.mpc_steps = a.mpc_steps;
+    in.cold = a.cold, in.save = a.save, in.indexed = a.idx != nullptr, in.adaptive_rho = st.adaptive_rho != 0;
+    in.ref_mode = ref_mode, in.loop = a.loop;
+    in.state_bounds = state_bounds_active, in.g_maybe_nonzero = g_maybe_nonzero;
+    in.live = st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0;
+    // (behind the stream kernel's fp64-state form the lean kernel is asked launch by launch: constraints added since the packs
+    // were built go to the stream kernel's EXT forms)
+    in.stream_ext = se && extensions_active();
+    in.cus = device_cu_count();
+    return lean_plan(in);
+}
+
+// the kernels' argument block: everything but the bound pack and the events, which depend on the kernel that runs
+void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     std::memset(&P, 0, sizeof(P));
     P.coef = reinterpret_cast<const float *>(d_coef);
     P.bounds = d_bounds;
     P.x0 = d_x0;
-    P.x0d = x0d_launch;
-    P.xref = xref_launch ? xref_launch : d_xref;
-    P.uref = uref_launch ? uref_launch : d_uref;
+    P.x0d = a.x0d;
+    P.xref = a.xref ? a.xref : d_xref;
+    P.uref = a.uref ? a.uref : d_uref;
     P.xout = d_xout;
     P.uout = d_uout;
     P.iter = d_iter;
@@ -1238,21 +1210,21 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     P.gstat = d_gstat;
     P.gacc = d_gstat + GSTAT_WORDS;
     P.scratch = d_scratch;
-    P.idx = idx;
-    P.iter_offset = iter_offset;
-    P.batch = n_slots;
-    P.max_iter = max_iter_pass;
+    P.idx = a.idx;
+    P.iter_offset = a.iter_offset;
+    P.batch = a.slots;
+    P.max_iter = a.iters;
     P.check_termination = st.check_termination;
     P.ref_mode = ref_mode;
-    P.cold_start = cold ? 1 : 0;
-    P.save_state = save ? 1 : 0;
+    P.cold_start = a.cold ? 1 : 0;
+    P.save_state = a.save ? 1 : 0;
     P.abs_pri_tol = (float)st.abs_pri_tol;
     P.abs_dua_tol = (float)st.abs_dua_tol;
     P.rho = (float)cache.rho;
     P.nx = nx;
     P.nu = nu;
     P.N = N;
-    P.mpc_steps = mpc_steps;
+    P.mpc_steps = a.mpc_steps;
     P.mpc_x = d_mpc_x;
     P.mpc_u = d_mpc_u;
     P.mpc_iter = d_mpc_iter;
@@ -1290,17 +1262,60 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     P.svl = d_svl;
     P.syl = d_syl;
     P.szl = d_szl;
-    // the quad and stream kernels keep the status block clean themselves (fold_status); the generic kernel
-    // accumulates straight into it
     P.bounds_stride = (ce && ce->bounds_vary(*this)) ? 1 : 0;
     // per-step references of a loop that runs inside the launch: mfmat's and the quad kernel's (the chain, rollout_steps,
     // hands every launch its step's slice as P.xref / P.uref instead and arrives here with mpc_steps = 0)
-    if (mpc_steps > 0 && ref_seq_steps > 0) {
-        if (!(ce && ce->ws) && !ke) {
-            set_error("mpc_rollout: per-step references need a kernel with a closed loop (mfmat, quad) or the chain of launches (mfma, lean)");
+    if (a.mpc_steps > 0 && ref_seq_steps > 0) {
+        P.xref_seq = d_xref_seq;
+        P.uref_seq = d_uref_seq;
+    }
+    P.lean = d_lean;
+    P.ws64 = d_ws64;
+    P.abs_pri_tol64 = st.abs_pri_tol;
+    P.abs_dua_tol64 = st.abs_dua_tol;
+    P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0);
+}
+
+int Solver::ensure_mpc_log(int mpc_steps) {
+    if (mpc_cap < mpc_steps) {
+        const size_t n = (size_t)batch * mpc_steps;
+        if (dev_alloc(d_mpc_x, n * nx) || dev_alloc(d_mpc_u, n * nu) || dev_alloc(d_mpc_iter, n)) return -1;
+        mpc_cap = mpc_steps;
+    }
+    return 0;
+}
+
+// carried: an event the launch's own dispatch packet already records at its end (a profiled lean launch)
+int Solver::record_done(hipStream_t stream, hipEvent_t carried) {
+    if (carried) {
+        ev_wait = carried;
+    } else {
+        if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(ev_done, stream));
+        ev_wait = ev_done;
+    }
+    ev_done_pending = true;
+    return 0;
+}
+
+int Solver::launch_pass(hipStream_t stream, const Pass &a) {
+    // ---- prepare ----
+    if (a.mpc_steps > 0) {
+        if (!ke && !(ce && ce->ws)) {
+            set_error("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
             return -1;
         }
-        if (ref_seq_steps < mpc_steps || ref_mode != REF_SHARED) {
+        if (!warm_start) {
+            set_error("mpc_rollout needs the persistent workspace (set_warm_start(1))");
+            return -1;
+        }
+        if (ensure_mpc_log(a.mpc_steps)) return -1;
+        mpc_steps_last = a.mpc_steps;
+    }
+    if (packs_dirty && upload_packs()) return -1;
+    if (upload_refs()) return -1;
+    if (a.mpc_steps > 0 && ref_seq_steps > 0) {
+        if (ref_seq_steps < a.mpc_steps || ref_mode != REF_SHARED) {
             set_error("mpc_rollout: per-step references need one shared reference set per step");
             return -1;
         }
@@ -1309,9 +1324,11 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
                       std::to_string((int)QUAD_REF_SEQ_MAX_N) + " (this entry: " + ke->name + "); step the loop from the host");
             return -1;
         }
-        P.xref_seq = d_xref_seq;
-        P.uref_seq = d_uref_seq;
     }
+    AdmmParams P;
+    fill_params(P, a);
+    // the quad and stream kernels keep the status block clean themselves (fold_status); the generic kernel
+    // accumulates straight into it
     if (!ke && !se && !ce) HIP_TRY(hipMemsetAsync(d_gstat, 0, GSTAT_WORDS * sizeof(uint32_t), stream));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (profiling) {
@@ -1324,101 +1341,48 @@ int Solver::launch_pass(hipStream_t stream, int mpc_steps, const int *idx, int n
     }
     // the workspace's state dual is non-zero only if some solve since the last reset had a finite state bound (or the
     // caller wrote one in): the matrix-core kernel (G == 16) carries g only then
-    if (state_bounds_active && save) g_maybe_nonzero = true;
+    if (state_bounds_active && a.save) g_maybe_nonzero = true;
     const bool carry_g = state_bounds_active || (ke && ke->G == 16 && g_maybe_nonzero);
-    // one-shot solves (cold start, nothing of the workspace kept) of a one-lane-per-instance entry, zero or shared references,
-    // fp64 recurrences: the lean kernel (same arithmetic, a third fewer instructions)
-    // (behind the stream kernel's fp64-state form the lean kernel is asked launch by launch: constraints added since the packs
-    // were built go to the stream kernel's EXT forms)
-    const bool lean_f64 = precision == 2 && !ke && lean_jit && !(se && extensions_active());
-    // ... and, with TINYMPC_HIP_LEAN_WS, its workspace-keeping form for every other solve of that kind (lean_ws)
-    const bool lean_ws = !(cold && !save) && lean_ws_takes(idx);
-    // ... and, with TINYMPC_HIP_LEAN_LOOP, that form's in-kernel closed loop (rollout_lean_loop: the only launch with mpc_steps
-    // that comes here for the lean kernel)
-    const bool lean_loop = lean_loop_launch && lean_ws && mpc_steps > 0;
-    const bool lean_call = (ke ? precision == 0 : lean_f64) && lean_ok && ((cold && !save) || lean_ws) && (mpc_steps == 0 || lean_loop) && !idx &&
-                           ref_mode != REF_PER_INSTANCE && !st.adaptive_rho && max_iter_pass >= 1;
-    // the kernels without a state bound take the state dual for zero: a kept workspace whose g may hold something goes to the
-    // state-bounded form (whose clamps then clamp nothing) rather than dropping it
-    const bool lean_xb = state_bounds_active || (lean_ws && g_maybe_nonzero);
-    const bool lean_live = st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0;
-    const LeanEntry *lk = lean_call ? le : nullptr;
-    // the sweeps: the sparse form where a kernel's (A, B) pattern covers the model's and costs less per knot than the dense
-    // form it replaces (lean_pick_form; TINYMPC_HIP_LEAN_DENSE: never).  The built-in entry's sparse kernels take zero
-    // references and uniform input bounds; a specialised variant carries the model's own pattern, any calling pattern
-    int form = LF_NONE;
-    uint64_t form_sp = 0;
-    bool one = false;
-    if (lean_call && le) {
-        one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_ws;   // (the WS kernels: the 512-register form only)
-        const bool has_sparse = lean_loop ? le->launch_sparse_mpc != nullptr : (lean_ws ? le->launch_sparse_ws != nullptr : le->launch_sparse != nullptr);
-        const bool can = has_sparse && !sw.lean_dense && ref_mode == REF_ZERO && !lean_knot_bounds;
-        form_sp = has_sparse ? le->sp : 0;
-        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live || lean_loop, lean_xb, can);   // (the loop kernels are tolerance-terminated ones)
-    }
-    if (lean_call && !le && lean_jit) {
-        // the one variant this launch needs (lean_entry.hip.h: launch_lean_v's choices), compiled on first use
-        one = lean_one_form(P.batch, lean_live, sw.lean_one) || lean_f64 || lean_ws;
-        if (2 * N * nx + 3 * N * nu + 50 > 250) one = true;   // (the 256-register form does not hold this horizon)
-        form_sp = lean_sp;
-        form = lean_pick_form(nx, nu, form_sp, lean_sp, one, lean_live || lean_loop, lean_xb, !sw.lean_dense);
-        // (the one WS calling pattern whose fixed-iteration kernel parks a register runs the tolerance-terminated kernel of the
-        // same flags, as the built-in launcher does: lean_entry.hip.h, launch_lean_v)
-        // (... and so does every in-kernel loop: its kernels are the tolerance-terminated ones)
-        const bool live_v = lean_live || (lean_ws && lean_xb && ref_mode == REF_SHARED && lean_knot_bounds) || lean_loop;
-        const int v = (live_v ? LV_LIVE : 0) | (lean_knot_bounds ? 0 : LV_UBK) | (one ? LV_ONE : 0) | (lean_xb ? LV_XB : 0) |
-                      (ref_mode == REF_SHARED ? LV_SHARED : 0) | (lean_f64 ? LV_F64 : 0) | (form == LF_SPARSE ? LV_SPARSE : 0) |
-                      (lean_ws ? LV_WS : 0) | (lean_loop ? LV_MPC : 0);
-        if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, form == LF_SPARSE ? lean_sp : 0, verbose), le_var_tried[v] = true;
+    // ---- plan: the lean kernel (same arithmetic as the quad entry's, a third fewer instructions) where lean_plan takes the
+    // launch — the built-in entry, or the one variant of a shape without one, compiled on first use ----
+    const LeanPlan plan = plan_lean(a);
+    const LeanEntry *lk = plan.take ? le : nullptr;
+    if (plan.take && !le) {
+        const int v = plan.variant;
+        if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, plan.form == LF_SPARSE ? plan.sp : 0, verbose), le_var_tried[v] = true;
         lk = le_var[v];
     }
-    if (lean_loop_launch) {   // the loop kernel of this calling pattern, or nothing: the caller falls back to the chain
-        if (!lk || !(form == LF_SPARSE && le ? le->launch_sparse_mpc : lk->launch_mpc)) return 1;
-    }
     const bool lean = lk != nullptr;
-    last_lean_form = lean ? form : LF_NONE;
-    last_lean_cost[0] = lean && form_sp ? lean_cost_sparse(form_sp, nx, nu) : 0;
-    last_lean_cost[1] = !lean ? 0 : (one && !lean_live && !lean_loop && !lean_xb) ? lean_cost_hessenberg(nx, nu) : lean_cost_dense(nx, nu);
+    if (a.loop && !lean) return NO_LOOP_KERNEL;   // the loop kernel of this calling pattern, or nothing: the caller falls back to the chain
     if (lean && !le && (!ke || ke->G != 1)) P.bounds = reinterpret_cast<const float *>(d_lean + lean_layout(nx, nu).total);   // (upload_packs)
-    P.lean = d_lean;
-    P.ws64 = d_ws64;
-    P.abs_pri_tol64 = st.abs_pri_tol;
-    P.abs_dua_tol64 = st.abs_dua_tol;
-    P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0) | (sw.lean_one ? HF_LEAN_ONE : 0);
-    last_launch_name = lean ? lk->name : kernel_name;
+    // ---- launch ----
     // A profiled lean launch carries its two timing events in the kernel's own dispatch packet (start and end of the kernel):
     // recorded on their own they are marker packets the command processor handles between two kernels that are already
     // serialised, and a third one for the completion wait — four packets per solve where one does.  The stop event then
     // serves the completion wait too.  TINYMPC_HIP_EVENT_MARKERS: the separate records (timing aid).
     const bool attached = profiling && lean && !sw.event_markers;
     if (profiling && !attached) HIP_TRY(hipEventRecord(ev0, stream));
-    if (lean) {
-        hipEvent_t a0 = attached ? ev0 : nullptr, a1 = attached ? ev1 : nullptr;
-        if (lean_loop) HIP_TRY((form == LF_SPARSE && le ? le->launch_sparse_mpc : lk->launch_mpc)(P, true, lean_knot_bounds, lean_xb, stream, a0, a1));
-        else if (form == LF_SPARSE && le) HIP_TRY((lean_ws ? le->launch_sparse_ws : le->launch_sparse)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
-        else HIP_TRY((lean_ws ? lk->launch_ws : lk->launch)(P, lean_live, lean_knot_bounds, lean_xb, stream, a0, a1));
-    } else
-    HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
-               : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
-                     : (se ? (precision == 2 ? se->launch_f64(P, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), stream)
-                                             : se->launch(P, precision, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), hetero, stream))
-                           : launch_generic(P, precision, stream))));
+    if (lean)
+        HIP_TRY(lk->launch(P, plan.variant, stream, attached ? ev0 : nullptr, attached ? ev1 : nullptr));
+    else
+        HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
+                   : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
+                         : (se ? (precision == 2 ? se->launch_f64(P, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), stream)
+                                                 : se->launch(P, precision, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), hetero, stream))
+                               : launch_generic(P, precision, stream))));
+    // ---- record ----
     if (profiling) {
         if (!attached) HIP_TRY(hipEventRecord(ev1, stream));
         launches += 1;
     }
+    last_launch_name = lean ? lk->name : kernel_name;
+    last_lean_form = lean ? plan.form : LF_NONE;
+    last_lean_cost[0] = lean ? plan.cost_sparse : 0;
+    last_lean_cost[1] = lean ? plan.cost_dense : 0;
     // the status block stays on the device; solve_status() fetches it when asked (nothing but the kernel and the
     // 32-byte clear is enqueued per solve)
     solved_once = true;
-    if (attached) {
-        ev_wait = ev1;
-    } else {
-        if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev_done, stream));
-        ev_wait = ev_done;
-    }
-    ev_done_pending = true;
-    return 0;
+    return record_done(stream, attached ? ev1 : nullptr);
 }
 
 // x0d <- x0 (start of a closed loop)
@@ -1459,11 +1423,7 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
         return -1;
     }
     const size_t Bn = (size_t)batch;
-    if (mpc_cap < mpc_steps) {
-        const size_t n = Bn * mpc_steps;
-        if (dev_alloc(d_mpc_x, n * nx) || dev_alloc(d_mpc_u, n * nu) || dev_alloc(d_mpc_iter, n)) return -1;
-        mpc_cap = mpc_steps;
-    }
+    if (ensure_mpc_log(mpc_steps)) return -1;
     if (!d_x0d && dev_alloc(d_x0d, Bn * nx)) return -1;
     if (!d_plant) {
         if (dev_alloc(d_plant, (size_t)nx * nx + (size_t)nx * nu)) return -1;
@@ -1476,13 +1436,11 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     // with a reference sequence every launch reads its step's slice of the sequence as its shared references (step 0's are the
     // solver's own, which stay installed: nothing is copied, and the stream is not synchronised between steps)
     const size_t EX = (size_t)ex(), EU = (size_t)eu();
+    Pass pass = whole_batch(false, true);
+    pass.x0d = d_x0d;
     for (int step = 0; step < mpc_steps; ++step) {
-        x0d_launch = d_x0d;
-        if (ref_seq_steps > 0 && step > 0) xref_launch = d_xref_seq + step * EX, uref_launch = d_uref_seq + step * EU;
-        const int rc = launch_pass(stream, 0, nullptr, batch, 0, st.max_iter, false, true);
-        x0d_launch = nullptr;
-        xref_launch = uref_launch = nullptr;
-        if (rc) return -1;
+        if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
+        if (launch_pass(stream, pass)) return -1;
         plant_step_kernel<<<(unsigned)((Bn + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
                                                                         d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,
                                                                         (long)Bn, mpc_steps, step);
@@ -1490,26 +1448,21 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     HIP_TRY(hipGetLastError());
     mpc_steps_last = mpc_steps;
     last_rollout_launches = mpc_steps;
-    if (!ev_done) HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ev_done, stream));
-    ev_wait = ev_done;
-    ev_done_pending = true;
-    return 0;
+    return record_done(stream);
 }
 
 // The closed loop as one launch of the lean kernel's in-kernel loop: log buffers as every fused loop has them (launch_pass),
 // the fp64 plant state set up as rollout_steps does (x0d <- x0) and handed to the launch, which leaves x0 and x0d as the
-// chain leaves them.  1: no loop kernel for this solver's calling pattern (no solve was launched; the chain takes the loop).
+// chain leaves them.  NO_LOOP_KERNEL: none for this solver's calling pattern (no solve was launched; the chain takes the loop).
 int Solver::rollout_lean_loop(hipStream_t stream, int mpc_steps) {
     if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
     const long n0 = (long)batch * nx;
     plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
     HIP_TRY(hipGetLastError());
-    lean_loop_launch = true;
-    x0d_launch = d_x0d;
-    const int rc = launch_pass(stream, mpc_steps, nullptr, batch, 0, st.max_iter, false, true);
-    lean_loop_launch = false;
-    x0d_launch = nullptr;
+    Pass pass = whole_batch(false, true, mpc_steps);
+    pass.x0d = d_x0d;
+    pass.loop = true;
+    const int rc = launch_pass(stream, pass);
     if (rc == 0) last_rollout_launches = 1;
     return rc;
 }
