@@ -57,6 +57,20 @@ def nrel_batch(a, ref):
     return np.abs(a - ref).max(axis=(0, 1)) / den
 
 
+def precision1_limit(r32, r64, factor=4.0):
+    """The bar of a precision-1 (all-fp32 recurrences) kernel against orc64, from the reference model alone: orc32 is the same
+    loop in fp32, one realisation of fp32 rounding; the kernel (other summation order, FMA contraction, float-rounded
+    coefficient pack) is another, and two realisations differ in their worst instance by a small factor.
+      e32_case   = worst nrel_batch(orc32, orc64) over x and u, over the instances where both oracles agree on (iter, solved)
+      limit_case = max(FP32_TOL, factor * e32_case)
+    r32, r64: dicts with x, u, iter, solved (solve_batch's).  Returns (limit_case, e32_case, share of agreeing instances)."""
+    same = (np.asarray(r32["iter"]) == np.asarray(r64["iter"])) & (np.asarray(r32["solved"]) == np.asarray(r64["solved"]))
+    if not same.any():
+        return FP32_TOL, 0.0, 0.0
+    e32 = max(float(nrel_batch(r32["x"], r64["x"])[same].max()), float(nrel_batch(r32["u"], r64["u"])[same].max()))
+    return max(FP32_TOL, factor * e32), e32, float(same.mean())
+
+
 def _ratio(res, pri_tol, dua_tol):
     """how far the four residuals are from the tolerances: converged iff < 1 (admm.cpp:99-103)"""
     res = np.asarray(res, dtype=np.float64)

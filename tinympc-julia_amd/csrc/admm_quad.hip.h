@@ -224,11 +224,13 @@ template <class RT, int G>
 struct CoefLds {
     static constexpr int VEC = 16 / (int)sizeof(RT);
     const RT *base;  // s_coef + q * VEC
+    int off = 0;     // element offset of a pack section inside the role's pack
     __device__ __forceinline__ static int slot(int i, int q) { return ((i / VEC) * G + q) * VEC + i % VEC; }
-    __device__ __forceinline__ RT operator[](int i) const { return base[(i / VEC) * G * VEC + i % VEC]; }
-    __device__ __forceinline__ CoefLds operator+(int off) const {
-        // offsets used are multiples of VEC (every pack section is a multiple of G rows), so chunking commutes
-        return CoefLds{base + (off / VEC) * G * VEC};
+    __device__ __forceinline__ RT operator[](int i) const { return base[((off + i) / VEC) * G * VEC + (off + i) % VEC]; }
+    __device__ __forceinline__ CoefLds operator+(int o) const {
+        // the section offset is carried and chunked together with the index: a section need not start on a chunk (two lanes
+        // per instance with float rows: sections are multiples of 2 elements, chunks hold 4 — (6,3) has O_K = 18)
+        return CoefLds{base, off + o};
     }
 };
 // G = 1: a lane is an instance, so the coefficient rows are wave-uniform.  Each sweep fetches the
