@@ -208,6 +208,60 @@ def case_live_adaptive(name, prob, x0s, settings, adaptive, note=""):
                 dKinf_drho=_l(sens[0]), dPinf_drho=_l(sens[1]), x0=_l(x0s), batch=int(x0s.shape[1]), expect=inst)
 
 
+def nonsymmetric_dP(dP, seed=31):
+    """dPinf/drho plus a strictly upper-triangular perturbation of its own scale: the only input that tells Pinf' x from
+    Pinf x in the terminal rows and in the reference term"""
+    rng = np.random.default_rng(seed)
+    return np.asfortranarray(dP + np.triu(0.2 * np.abs(dP).max() * rng.standard_normal(dP.shape), 1))
+
+
+def case_live_adaptive_refs_bounds(name, N, batch, settings, adaptive, note=""):
+    """Adaptive rho on the zero-initialised snapshot ("refa") where L2 / G9 do not reach: shared references, a finite state
+    bound on every knot (position rows +-0.31: just outside the initial states, binds on overshoot), both, and both with a
+    dPinf/drho that is not symmetric.  Per instance two consecutive solves of one solver (kept workspace, adapted cache),
+    the second from the plant's next state A x0 + B u0 of the snapshot's own first solve, stored as an input.  The tables
+    are the ones G9a stores (the snapshot's built-in ones)."""
+    with open(os.path.join(OUT, "G9a_quadrotor_adaptive_fixed100.json")) as f:
+        g9 = json.load(f)
+    dK = np.asarray(g9["dKinf_drho"]).reshape((4, 12), order="F")
+    dP = np.asarray(g9["dPinf_drho"]).reshape((12, 12), order="F")
+    dPn = nonsymmetric_dP(dP)
+    rng = np.random.default_rng(53)
+    xref, uref = 0.05 * rng.standard_normal((12, N)), 0.02 * rng.standard_normal((4, N - 1))
+    x0s = P.quadrotor_x0(batch, seed=12)
+    runs = []
+    for label, refs, bound, table in (("shared_refs", True, False, dP), ("state_bound", False, True, dP),
+                                      ("refs_and_bound", True, True, dP), ("refs_and_bound_nonsymmetric", True, True, dPn)):
+        prob = P.quadrotor(N)
+        if bound:
+            prob.x_min, prob.x_max = np.full((12, N), -1e17), np.full((12, N), 1e17)
+            prob.x_min[:3, :], prob.x_max[:3, :] = -0.31, 0.31
+        inst, x1s = [], np.zeros_like(x0s)
+        for b in range(batch):
+            s = CpuSolver("refa", prob.A, prob.B, prob.Q, prob.R, prob.rho, prob.N)
+            s.update_settings(**settings)
+            s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+            s.set_sensitivity(dK, table)
+            s.set_adaptive_rho(1, adaptive["rho_min"], adaptive["rho_max"], adaptive["clip"])
+            if refs:
+                s.set_x_ref(xref)
+                s.set_u_ref(uref)
+            seq, x = [], x0s[:, b]
+            for k in range(2):
+                s.set_x0(x)
+                o = _sol(s, s.solve())
+                a = s.get_adapted()
+                o.update(rho=a["rho"], Kinf=_l(a["Kinf"]), Pinf=_l(a["Pinf"]))
+                seq.append(o)
+                if k == 0:
+                    x = x1s[:, b] = prob.A @ x + prob.B @ np.array(o["u"][:4])
+            inst.append(seq)
+        runs.append(dict(label=label, problem=_prob_dict(prob), xref=_l(xref) if refs else None,
+                         uref=_l(uref) if refs else None, dPinf_drho=_l(table), x1=_l(x1s), expect=inst))
+    return dict(case=name, note=note, settings=settings, adaptive=adaptive, dKinf_drho=_l(dK), x0=_l(x0s), batch=batch,
+                runs=runs)
+
+
 def main():
     only = sys.argv[1] if len(sys.argv) > 1 else ""
     build(port=False, ref=True)
@@ -301,6 +355,12 @@ def main():
                                     dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=60, check_termination=1),
                                     dict(rho_min=1.0, rho_max=20.0, clip=True),
                                     note="tests/test_oracle.py::test_adaptive_rho_live_reference"))
+    if not only or "L3_live_reference_adaptive_refs_bounds".startswith(only):   # (reads G9a's tables: written above, or present)
+        cases.append(case_live_adaptive_refs_bounds(
+            "L3_live_reference_adaptive_refs_bounds", 10, 4,
+            dict(abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=40, check_termination=1),
+            dict(rho_min=0.1, rho_max=10.0, clip=True),
+            note="tests/test_oracle.py::test_adaptive_rho_refs_bounds_live_reference"))
 
     for c in cases:
         if only and not c["case"].startswith(only):

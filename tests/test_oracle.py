@@ -232,6 +232,57 @@ def test_adaptive_rho_live_reference(oracle_built):
         assert nrel(out[1]["x"], out[0]["x"]) <= 1e-10 and nrel(out[1]["u"], out[0]["u"]) <= 1e-10
 
 
+L3_RUNS = ["shared_refs", "state_bound", "refs_and_bound", "refs_and_bound_nonsymmetric"]
+
+
+@pytest.mark.parametrize("label", L3_RUNS)
+def test_adaptive_rho_refs_bounds_live_reference(oracle_built, label):
+    """Adaptive rho where G9 / L2 do not reach — shared references, a finite state bound on every knot, both, and both with
+    a dPinf/drho that is not symmetric (it alone tells Pinf' x from Pinf x in the terminal rows and the reference term) —
+    over two consecutive solves of one solver, the second from the plant's next state.  The restatement is held to the
+    zero-initialised snapshot's outputs as recorded in tests/golden/L3_live_reference_adaptive_refs_bounds.json, and to
+    the snapshot re-run live where it is built: equal iteration counts and exits, rho, x, u and the adapted Kinf / Pinf
+    within 1e-10.  This is what lets orc64 arbitrate the matrix-core kernel's adaptive variants (tests/mfma_cases.py)."""
+    import os
+    g = load_golden("L3_live_reference_adaptive_refs_bounds")
+    assert [r["label"] for r in g["runs"]] == L3_RUNS
+    run = g["runs"][L3_RUNS.index(label)]
+    prob = problem_of(run)
+    B, ad = g["batch"], g["adaptive"]
+    x0, x1 = cm(g["x0"], prob.nx, B), cm(run["x1"], prob.nx, B)
+    dK, dP = cm(g["dKinf_drho"], prob.nu, prob.nx), cm(run["dPinf_drho"], prob.nx, prob.nx)
+    assert (np.abs(dP - dP.T).max() > 0.01 * np.abs(dP).max()) == label.endswith("nonsymmetric")
+    assert (np.abs(prob.x_max).min() < 1e17) == ("bound" in label) and (run["xref"] is not None) == ("refs" in label)
+    kinds = ("orc64", "refa") if os.path.isfile(oracle_built.REF_ADAPT_LIB) else ("orc64",)
+    moved = 0
+    for b in range(B):
+        for kind in kinds:
+            s = oracle_built.CpuSolver(kind, prob.A, prob.B, prob.Q, prob.R, prob.rho, prob.N)
+            s.update_settings(**g["settings"])
+            s.set_bound_constraints(prob.x_min, prob.x_max, prob.u_min, prob.u_max)
+            s.set_sensitivity(dK, dP)
+            s.set_adaptive_rho(1, ad["rho_min"], ad["rho_max"], ad["clip"])
+            if run["xref"] is not None:
+                s.set_x_ref(cm(run["xref"], prob.nx, prob.N))
+                s.set_u_ref(cm(run["uref"], prob.nu, prob.N - 1))
+            for k, x in enumerate((x0[:, b], x1[:, b])):
+                exp = run["expect"][b][k]
+                s.set_x0(x)
+                status = s.solve()
+                o = s.get_solution()
+                assert (status, o["iter"], o["solved"]) == (exp["status"], exp["iter"], exp["solved"]), (kind, b, k)
+                _cmp(o, exp, prob, 1e-10)
+                a = s.get_adapted()
+                assert abs(a["rho"] - exp["rho"]) <= 1e-10 * exp["rho"], (kind, b, k)
+                assert nrel(a["Kinf"], cm(exp["Kinf"], prob.nu, prob.nx)) <= 1e-10, (kind, b, k)
+                assert nrel(a["Pinf"], cm(exp["Pinf"], prob.nx, prob.nx)) <= 1e-10, (kind, b, k)
+                if k == 0 and kind == "orc64":
+                    assert np.abs(prob.A @ x + prob.B @ o["u"][:, 0] - x1[:, b]).max() <= 1e-10
+            moved += kind == "orc64" and abs(a["rho"] - prob.rho) > 1e-3
+            s.close()
+    assert moved >= B // 2                                 # the recorded runs do adapt
+
+
 def test_host_sensitivity_matches_the_recipe():
     """The library's host finite differences (csrc/host_setup.cpp) against the numpy mirror of TinyMPC.jl:301-352
     in tinympc.py; both difference two Riccati fixed points with h = 1e-6, so agreement is to the fixed points'

@@ -55,7 +55,7 @@ struct MfmaShape {
     static constexpr int NF = 5 * VX + 3;               // operand doubles per lane: Mf[VX] Bf Mb[VX] KTn QI PT[VX] AT[VX] SP[VX]
     static constexpr int O_MF = 0, O_BF = VX, O_MB = VX + 1, O_KT = 2 * VX + 1, O_QI = 2 * VX + 2, O_PT = 2 * VX + 3,
                          O_AT = 3 * VX + 3,             // AT: [A^T; B^T] (adaptive rho: the norms' A'g, B'g)
-                         O_SP = 4 * VX + 3;             // SP: (dPinf/drho)^T (adaptive rho: the terminal knot's Pinf_b x)
+                         O_SP = 4 * VX + 3;             // SP: dPinf/drho (adaptive rho: the terminal knot's Pinf_b x)
     // behind the lane fields: the family's Kinf, row-major [NU][NX] (adaptive rho: an instance's own Kinf enters as a
     // correction to the products formed with this one)
     // ... and its Pinf, row-major [NX][NX] (what an instance's adaptive state is rebuilt from when it finishes)

@@ -25,8 +25,9 @@ void build_mfma_coef(const Solver &sv, std::vector<unsigned char> &out) {
             const int col = 4 * s + kq;             // state index the slice's column stands for
             double mf = 0.0, mb = 0.0, pt = 0.0, at = 0.0, sp = 0.0;
             if (col < NX) {
-                // (dPinf/drho)^T [i][col]: row i of the product = sum_col dPinf[col][i] x_col, like Pinf^T above
-                if (xrow && sv.sens.size() == (size_t)NU * NX + (size_t)NX * NX) sp = sv.sens[(size_t)NU * NX + col + (size_t)i * NX];
+                // (dPinf/drho)[i][col], NOT transposed: the terminal norm row is P x (rho_benchmark.cpp: P = blkdiag(.., Pinf)), and
+                // a table handed in need not be symmetric (Pinf_0, a Riccati fixed point, is: PT serves for it)
+                if (xrow && sv.sens.size() == (size_t)NU * NX + (size_t)NX * NX) sp = sv.sens[(size_t)NU * NX + i + (size_t)col * NX];
                 at = xrow ? sv.A(col, i) : (urow ? sv.B(col, a) : 0.0);   // ([A'; B'])[i][col]: A'g, B'g of the adaptive-rho norms
                 if (xrow) {
                     mf = sv.A(i, col);              // (A - B Kinf)[i][col], from A, B, Kinf themselves (set_cache_terms may
