@@ -238,7 +238,17 @@ int tinympc_unpin_host(tinympc_solver *s, void *ptr);
  * cartpole-class shape with at least 20 480 instances on the headline (lean) kernel, as a stream-ordered chain of `steps`
  * workspace-carrying launches and plant updates; TINYMPC_HIP_LEAN_LOOP=1 beside it (no effect alone) as ONE launch of that
  * kernel's in-kernel loop, every instance's workspace kept on chip between the steps — except with a reference sequence
- * (below), which keeps the chain.  Results, logs and workspace are those of the chain. */
+ * (below), which keeps the chain.  Results, logs and workspace are those of the chain.
+ * Shapes and option sets that run on the stream or the generic kernel — a horizon without a built-in entry, linear rows,
+ * cone / affine-term layouts outside the transposed-sets kernel, per-instance families, any (nx, nu) outside the stream
+ * grid, every solver at precision 2 — have no closed loop by default: the call fails, naming the condition.
+ * TINYMPC_HIP_STREAM_MPC=1 (off by default, read when the solver is created) gives them one as the same kind of chain —
+ * `steps` workspace-carrying launches, the plant x0 = f + A x0 + B u0 (per-instance A, B on a family solver) in fp64
+ * between them, each solve started from the fp32 rounding of the plant state — at precision 0, 1 and 2, with a reference
+ * sequence too; TINYMPC_HIP_STREAM_LOOP=1 beside it (no effect alone) runs ONE launch of the stream kernel's in-kernel loop
+ * where one is built ((4,1), (6,3) at precision 0 and 2, (12,4) at precision 2; bit-identical to the chain) and the chain
+ * elsewhere.  Still refused there: adaptive rho, families at precision 2, a solver without the persistent workspace.
+ * Two such loops in a row continue the fp64 plant state of the first unless x0 was set in between. */
 int tinympc_mpc_rollout(tinympc_solver *s, int steps, void *hip_stream);
 int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter);
 /* Shared references of EVERY step of the next closed loops — the caller pattern of
@@ -253,7 +263,8 @@ int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter);
  * step's slice of the sequence in place.  tinympc_mpc_rollout fails, naming the condition, with fewer sequence steps than
  * loop steps, with per-instance references (set after the sequence, or through tinympc_set_ref_mode(2)), with adaptive rho,
  * at precision 2, on a quad entry with a horizon above 20, and on shapes that have no closed loop at all (stream / generic
- * kernels); a sharded solver takes no sequence. */
+ * kernels) — the last two unless TINYMPC_HIP_STREAM_MPC=1 gives those solvers their chained loop (above), whose launches
+ * read their step's slice like the other chains'; a sharded solver takes no sequence. */
 int tinympc_set_ref_sequence(tinympc_solver *s, const double *x_ref_seq, int x_rows, int x_cols, const double *u_ref_seq,
                              int u_rows, int u_cols, int steps);
 /* Tolerance-terminated solves of big batches: with chunk_iters > 0 (rounded up to a multiple of check_termination)
@@ -273,7 +284,7 @@ double tinympc_kernel_elapsed_mean_ms(tinympc_solver *s, int last_n);
  * with fp64 coefficients (default; ADMM state and elementwise steps stay fp32), 1 = all fp32,
  * 2 = all fp64 — the reference's own arithmetic end to end (types.hpp:15): recurrences, slacks, duals, residual
  * comparisons and the workspace kept between solves in fp64, on the generic kernel (any shape and option set of the
- * single-family solvers; no fused closed loop); x0 / references / bounds go in and the solution comes out as the fp32
+ * single-family solvers; no closed loop unless TINYMPC_HIP_STREAM_MPC=1, see tinympc_mpc_rollout); x0 / references / bounds go in and the solution comes out as the fp32
  * device arrays.  It is the mode for callers who need the reference's digits rather than the 1e-5 of the fp32-state
  * kernels (families whose duals lose digits to fp32 rounding miss 1e-5 there); it is the slowest path of the library —
  * except cold one-shot solves of cartpole-class shapes ((4,1) to N = 30, (3,2), (2,x)), which are launched on the headline

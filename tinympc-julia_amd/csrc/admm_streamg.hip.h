@@ -19,7 +19,9 @@
 //     quad kernel); one family per instance (HET): the same rows as per-lane columns in HBM;
 //   * second-order cones may straddle lanes: squared head norms and the axis value are summed over
 //     the group with DPP steps.
-#pragma once
+#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself once, at its end, for the loop form's entry point)
+#define TMPC_ADMM_STREAMG_HIP_H
+#define TMPC_STREAMG_MPC 0
 #include <hip/hip_runtime.h>
 
 #include "admm_generic.hip.h"   // Ws64, the type-generic gmin / gmax / gsqrt / gfma / gupmax
@@ -258,6 +260,12 @@ struct StreamTune {
 #define TMPC_STREAM_WAVES64(G, EXT, OS) StreamTune<G>::waves64(EXT, OS)
 #endif
 
+}  // namespace tmpc
+#endif  // TMPC_ADMM_STREAMG_HIP_H
+
+#ifndef TMPC_STREAMG_BOTH
+namespace tmpc {
+
 // ADP: adaptive rho (admm.cpp:147-174 with rho_benchmark.cpp:44-213).  One family for the batch (its rows in LDS), but
 // rho, Kinf and Pinf are every instance's own: the rows built from them (Kinf, Kinf^T, Pinf^T) are read from the lane's
 // column of a scratch matrix that the kernel fills from the solver's adaptive state at entry and re-writes, together
@@ -268,11 +276,33 @@ struct StreamTune {
 // RT = double; one family, no adaptive rho): the reference's arithmetic end to end, as the generic kernel's fp64-state form
 // computes it — same values, same order within a row; only the mat-vec sums are ordered by lane — with the workspace in the
 // fp64 block P.ws64 (Ws64) and the tolerances compared in fp64.  Inputs, the LDS image and the outputs are the same fp32 arrays.
+//
+// MPC: the closed loop inside the launch (TINYMPC_HIP_STREAM_LOOP; workspace-keeping form, fixed rho, four lanes, fp64
+// recurrences).  P.mpc_steps warm solves, each followed by the plant step the chain of launches takes between two of them
+// (Solver::rollout_steps, plant_step_affine_kernel): u0 = the fp32 control of knot 0, x+ = f + A x + B u0 in fp64 — f, then
+// A's row by ascending column, then B's, one fma each — on the fp64 plant state in P.x0d, each lane its own rows, the other
+// lanes' x_j and u_a by quad broadcasts; the next solve starts from (float)x+ with the workspace as the scratch block
+// already holds it (what saving and reloading it would give: the kept arrays stay, the work arrays are zeroed), with the
+// step's slice of P.xref_seq / P.uref_seq as its references.  The last solve leaves through the ordinary epilogue.
+// The kernel below is compiled twice from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1 — as
+// admm_streamg_kernel and as the loop form's admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST>.  The preprocessor decides what
+// `if constexpr` cannot wrap (the loop over steps around the iteration loop, the step's reference pointers), so that the plain
+// kernel's text, name and code are what they were before the loop form existed.
+#if !TMPC_STREAMG_MPC
 template <int NX, int NU, int G, class RT, int EXT, bool HET, bool OS, bool ADP = false, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, OS) : TMPC_STREAM_WAVES(G)))) void admm_streamg_kernel(const AdmmParams P) {
+    constexpr bool MPC = false;
+#else
+template <int NX, int NU, int G, int EXT, bool HET, class ST = float>
+__global__ __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, false) : TMPC_STREAM_WAVES(G)))) void admm_streamg_mpc_kernel(const AdmmParams P) {
+    using RT = double;
+    constexpr bool OS = false, ADP = false, MPC = true;
+#endif
     static_assert(!ADP || (!HET && EXT == 0), "adaptive rho: one family, box sets only");
     static_assert(sizeof(ST) == 4 || (sizeof(RT) == 8 && !HET && !ADP), "fp64 state: fp64 recurrences, one family, fixed rho");
+    static_assert(!MPC || (!OS && !ADP && G == 4 && sizeof(RT) == 8), "in-kernel closed loop: workspace kept, fixed rho, four lanes, fp64 recurrences");
     constexpr bool WIDE = sizeof(ST) == 8;
     using PK = StreamPackG<NX, NU, G>;
     using S = typename PK::S;
@@ -536,15 +566,23 @@ __global__ __launch_bounds__(256)
                 }
             }
     }
+#if TMPC_STREAMG_MPC
+    const float *xrefp = P.xref, *urefp = P.uref;   // the step's slice of the reference sequence
+#define TMPC_XREF xrefp
+#define TMPC_UREF urefp
+#else
+#define TMPC_XREF P.xref
+#define TMPC_UREF P.uref
+#endif
     auto ref_x = [&](int k, int m) __attribute__((always_inline)) -> float {
         const int row = q * RX + m;
         if (row >= NX || P.ref_mode == REF_ZERO) return 0.f;
-        return P.ref_mode == REF_SHARED ? P.xref[k * NX + row] : P.xref[b * EX + k * NX + row];
+        return P.ref_mode == REF_SHARED ? TMPC_XREF[k * NX + row] : TMPC_XREF[b * EX + k * NX + row];
     };
     auto ref_u = [&](int k, int m) __attribute__((always_inline)) -> float {
         const int row = q * RU + m;
         if (row >= NU || P.ref_mode == REF_ZERO) return 0.f;
-        return P.ref_mode == REF_SHARED ? P.uref[k * NU + row] : P.uref[b * EU + k * NU + row];
+        return P.ref_mode == REF_SHARED ? TMPC_UREF[k * NU + row] : TMPC_UREF[b * EU + k * NU + row];
     };
 
     int it = 0, conv = 0;
@@ -570,6 +608,10 @@ __global__ __launch_bounds__(256)
         ST w[RX], g[RX], wc[RX], gc[RX], wl[RX], gl[RX], zw[RU], y[RU], zwc[RU], yc[RU], zwl[RU], yl[RU];
     };
 
+#if TMPC_STREAMG_MPC
+    const int nsteps = P.mpc_steps;
+    for (int step = 0; step < nsteps; ++step) {   // (the iteration loop below keeps its indentation)
+#endif
     for (int i = 0; i < P.max_iter; ++i) {
         if (active && !conv) {
             const bool check = ct > 0 && (i + 1) % ct == 0;  // lanes still iterating have it == i: wave-uniform
@@ -1069,6 +1111,90 @@ __global__ __launch_bounds__(256)
         }
         if (!__builtin_amdgcn_ballot_w64(active && !conv)) break;
     }
+#if TMPC_STREAMG_MPC
+    {
+        // ---- one closed-loop step behind the solve (every lane of the wavefront is here: the loop above ends wave-wide) ----
+        double *const xplant = const_cast<double *>(P.x0d);   // the launch owns the plant state, as plant_step_affine_kernel does in the chain
+        float u0[RU];
+        double xd[RX], u0d[RU], xn[RX];
+#pragma unroll
+        for (int m = 0; m < RU; ++m) {
+            u0[m] = (active && q * RU + m < NU) ? (float)*SUP(Szw, 0, m) : 0.f;
+            u0d[m] = (double)u0[m];
+        }
+#pragma unroll
+        for (int m = 0; m < RX; ++m) {
+            xd[m] = (active && q * RX + m < NX) ? xplant[b * NX + q * RX + m] : 0.0;
+            xn[m] = 0.0;
+            if constexpr (EXT != 0)
+                if (P.has_fdyn) xn[m] = (double)cF[m];
+        }
+        sfor<0, NXL>([&](auto s) {
+            constexpr int S_ = decltype(s)::value;
+#pragma unroll
+            for (int k = 0; k < RX; ++k) {
+                const double xv = gbcast<G, S_>(xd[k]);
+                if (S_ * RX + k < NX) {
+#pragma unroll
+                    for (int m = 0; m < RX; ++m) xn[m] = fma((double)cA[m * NXP + S_ * RX + k], xv, xn[m]);
+                }
+            }
+        });
+        sfor<0, NUL>([&](auto s) {
+            constexpr int S_ = decltype(s)::value;
+#pragma unroll
+            for (int k = 0; k < RU; ++k) {
+                const double uv = gbcast<G, S_>(u0d[k]);
+                if (S_ * RU + k < NU) {
+#pragma unroll
+                    for (int m = 0; m < RX; ++m) xn[m] = fma((double)cB[m * NUP + S_ * RU + k], uv, xn[m]);
+                }
+            }
+        });
+        const bool more = step + 1 < nsteps;
+        if (active) {
+            const long so = b * nsteps + step;
+#pragma unroll
+            for (int m = 0; m < RX; ++m)
+                if (q * RX + m < NX) {
+                    xplant[b * NX + q * RX + m] = xn[m];
+                    P.mpc_x[so * NX + q * RX + m] = (float)xn[m];
+                    if (!more) P.x0_out[b * NX + q * RX + m] = (float)xn[m];
+                }
+#pragma unroll
+            for (int m = 0; m < RU; ++m)
+                if (q * RU + m < NU) P.mpc_u[so * NU + q * RU + m] = u0[m];
+            if (q == 0) P.mpc_iter[so] = conv ? P.iter_offset + it : -(P.iter_offset + it);
+        }
+        if (more) {
+            // the next solve: from the rounded plant state, iteration count and flag reset, residuals kept (a warm launch reads
+            // back what the previous one wrote), the work arrays zeroed as the warm load zeroes them
+#pragma unroll
+            for (int m = 0; m < RX; ++m) x0[m] = (active && q * RX + m < NX) ? (RT)(float)xn[m] : (RT)0;
+            it = 0, conv = 0;
+            if (P.xref_seq) xrefp = P.xref_seq + (long)(step + 1) * EX, urefp = P.uref_seq + (long)(step + 1) * EU;
+            if (active) {
+                for (int k = 0; k < N; ++k)
+#pragma unroll
+                    for (int m = 0; m < RX; ++m) {
+                        if (q * RX + m >= NX) continue;
+                        *SXP(Sw, k, m) = 0.f;
+                        if (soc_x) *SXP(Swc, k, m) = 0.f;
+                        if (lin_x) *SXP(Swl, k, m) = 0.f;
+                    }
+                for (int k = 0; k < N - 1; ++k)
+#pragma unroll
+                    for (int m = 0; m < RU; ++m) {
+                        if (q * RU + m >= NU) continue;
+                        *SUP(Szw, k, m) = 0.f;
+                        if (soc_u) *SUP(Szwc, k, m) = 0.f;
+                        if (lin_u) *SUP(Szwl, k, m) = 0.f;
+                    }
+            }
+        }
+    }
+    }
+#endif
 
     if (active) {
         for (int k = 0; k < N; ++k)
@@ -1132,6 +1258,8 @@ __global__ __launch_bounds__(256)
 #undef SUP
 #undef OKX
 #undef OKU
+#undef TMPC_XREF
+#undef TMPC_UREF
     {
         float m0 = active ? res0 : 0.f, m1 = active ? res1 : 0.f, m2 = active ? res2 : 0.f, m3 = active ? res3 : 0.f;
 #pragma unroll
@@ -1147,3 +1275,10 @@ __global__ __launch_bounds__(256)
 }
 
 }  // namespace tmpc
+#if !TMPC_STREAMG_MPC
+#undef TMPC_STREAMG_MPC
+#define TMPC_STREAMG_MPC 1
+#include "admm_streamg.hip.h"
+#define TMPC_STREAMG_BOTH
+#endif
+#endif  // TMPC_STREAMG_BOTH

@@ -131,6 +131,10 @@ struct StreamEntry {
     // rho) and the name it reports, "stream4<NX,NU;f64>" — both null where the form is not built (sinst_f64_*.hip)
     hipError_t (*launch_f64)(const AdmmParams &, int ext, hipStream_t) = nullptr;
     const char *name_f64 = nullptr;
+    // the in-kernel closed loop (TINYMPC_HIP_STREAM_LOOP; sinst_mpc_*.hip), null where it is not built.  hipErrorNotSupported:
+    // no loop kernel for that precision / family kind, nothing launched
+    hipError_t (*launch_mpc)(const AdmmParams &, int precision, int ext, bool het, hipStream_t) = nullptr;
+    bool (*has_mpc)(int precision, int ext, bool het) = nullptr;   // whether launch_mpc has a kernel for the call
 };
 const StreamEntry *find_stream_kernel(int nx, int nu);
 // One (nx, nu) instantiation of the LDS-resident matrix-core kernel with a run-time horizon (admm_mfmac.hip.h):
@@ -167,6 +171,8 @@ struct Switches {
          lean_ws = false,                                   // TINYMPC_HIP_LEAN_WS: warm / kept-workspace solves and mpc_rollout on the lean kernel
          lean_loop = false,                                 // TINYMPC_HIP_LEAN_LOOP: with lean_ws, mpc_rollout as one launch of the lean kernel's in-kernel loop
          stream_f64 = false,                                // TINYMPC_HIP_STREAM_F64: precision 2 on the stream kernel's fp64-state form where it is built
+         stream_mpc = false,                                // TINYMPC_HIP_STREAM_MPC: mpc_rollout on the stream and generic kernels (every precision), as the chain of launches
+         stream_loop = false,                               // TINYMPC_HIP_STREAM_LOOP: with stream_mpc, one launch of the stream kernel's in-kernel loop where it is built
          event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
     int mfmac_debug = 0;    // timing probe builds only
 };
@@ -359,6 +365,7 @@ struct Solver {
         const double *x0d = nullptr;                        // the fp64 plant state of a closed loop stepped outside the quad kernel
         const float *xref = nullptr, *uref = nullptr;       // shared references where not the solver's own (a step of a reference sequence)
         bool loop = false;                                  // the lean kernel's in-kernel closed loop, or nothing
+        bool stream_loop = false;                           // the stream kernel's in-kernel closed loop, or nothing
     };
     static constexpr int NO_LOOP_KERNEL = 1;                // launch_pass with Pass::loop: nothing was launched, the chain takes the loop
     Pass whole_batch(bool cold, bool save, int mpc_steps = 0) const;
@@ -376,8 +383,19 @@ struct Solver {
     // TINYMPC_HIP_LEAN_LOOP: the same loop as ONE launch of the lean kernel's in-kernel loop (NO_LOOP_KERNEL: none for this
     // calling pattern, nothing launched)
     int rollout_lean_loop(hipStream_t stream, int mpc_steps);
+    // TINYMPC_HIP_STREAM_MPC: the stream and generic kernels' closed loop is rollout_steps too (stream_chain: the routed kernel
+    // is one of them and the switch is set); with TINYMPC_HIP_STREAM_LOOP, ONE launch of the stream kernel's in-kernel loop
+    // (NO_LOOP_KERNEL: none for this shape / precision / family kind, nothing launched)
+    bool stream_chain() const { return sw.stream_mpc && warm_start && !ke && !ce && !st.adaptive_rho; }
+    int rollout_stream_loop(hipStream_t stream, int mpc_steps);
+    int stream_ext() const { return lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0); }   // the stream kernel's EXT of this solver
     int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout (-1: none has run)
-    double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B] column-major fp64; [B][nx] plant state
+    double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B | f] column-major fp64 (f: the affine term, follows set_fdyn); [B][nx] plant state
+    double *d_plant_het = nullptr;                // a per-instance-family solver: [batch][A_b | B_b] column-major fp64 (het_A, het_B)
+    bool plant_dirty = true;                      // d_plant is to be (re)written before the next chain
+    bool x0d_live = false;                        // d_x0d holds the plant state a stream / generic closed loop left (plant_start)
+    void plant_start(hipStream_t stream);         // the plant state a stream / generic closed loop starts from
+    int ensure_plant();
     int check_ref_sequence(int mpc_steps) const;
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};

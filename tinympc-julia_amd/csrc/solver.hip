@@ -145,6 +145,7 @@ Solver::~Solver() {
     dev_free(d_sens);
     dev_free(d_lean);
     dev_free(d_plant);
+    dev_free(d_plant_het);
     if (h_gstat) (void)hipHostFree(h_gstat);
     h_gstat = nullptr;
     for (hipEvent_t e : ev_ring)
@@ -227,6 +228,7 @@ void Solver::free_batch() {
     dev_free(d_adp_cols);
     adp_cols_bytes = 0;
     dev_free(d_x0d);
+    x0d_live = false;
     adapt_dirty = true;
     dev_free(d_mpc_x);
     dev_free(d_mpc_u);
@@ -353,6 +355,8 @@ Switches read_switches() {
     w.lean_ws = on("TINYMPC_HIP_LEAN_WS");
     w.lean_loop = on("TINYMPC_HIP_LEAN_LOOP");
     w.stream_f64 = on("TINYMPC_HIP_STREAM_F64");
+    w.stream_mpc = on("TINYMPC_HIP_STREAM_MPC");
+    w.stream_loop = on("TINYMPC_HIP_STREAM_LOOP");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     return w;
@@ -498,7 +502,7 @@ int Solver::select_kernel(bool rollout) {
         return -1;
     }
     if (precision == 2) {   // fp64 end to end: the stream kernel's fp64-state form (route_stream_f64), else the generic kernel's, whatever the shape
-        if (hetero || rollout) {
+        if (hetero || (rollout && !sw.stream_mpc)) {   // (TINYMPC_HIP_STREAM_MPC: the closed loop as a chain of these launches, solve_async)
             set_error(hetero ? "precision 2 is not available on a per-instance-family solver" : "precision 2 has no fused closed loop (step it from the host)");
             return -1;
         }
@@ -837,6 +841,7 @@ int Solver::set_fdyn(const double *f) {
     }
     has_fdyn = nz;
     packs_dirty = true;
+    plant_dirty = true;   // (the chained closed loop's plant carries f)
     return select_kernel() || ensure_extension_buffers();
 }
 
@@ -1073,7 +1078,7 @@ int Solver::check_ref_sequence(int mpc_steps) const {
         set_error("mpc_rollout: a reference sequence is not available with adaptive rho");
         return -1;
     }
-    if (precision == 2) {
+    if (precision == 2 && !sw.stream_mpc) {
         set_error("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
         return -1;
     }
@@ -1107,6 +1112,17 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
             }
             return rollout_steps(stream, mpc_steps);
         }
+    }
+    // TINYMPC_HIP_STREAM_MPC: the stream and generic kernels, which have no fused loop of their own, take the closed loop as
+    // that chain too — every precision, the affine term (in the plant as well), cones, linear rows, per-instance references
+    // and families.  With TINYMPC_HIP_STREAM_LOOP beside it, ONE launch of the stream kernel's in-kernel loop where one is
+    // built (admm_streamg.hip.h, MPC); what keeps the chain: the generic kernel, precision 1, a shape or form without a loop kernel
+    if (mpc_steps > 0 && stream_chain()) {
+        if (sw.stream_loop) {
+            const int rc = rollout_stream_loop(stream, mpc_steps);
+            if (rc != NO_LOOP_KERNEL) return rc;
+        }
+        return rollout_steps(stream, mpc_steps);
     }
     const int rc = launch_pass(stream, whole_batch(!warm_start, warm_start, mpc_steps));
     if (rc == 0 && mpc_steps > 0) last_rollout_launches = 1;              // (an in-kernel loop: quad, mfmat)
@@ -1301,7 +1317,9 @@ int Solver::record_done(hipStream_t stream, hipEvent_t carried) {
 int Solver::launch_pass(hipStream_t stream, const Pass &a) {
     // ---- prepare ----
     if (a.mpc_steps > 0) {
-        if (!ke && !(ce && ce->ws)) {
+        // (TINYMPC_HIP_STREAM_MPC opens this gate for the stream / generic kernels — adaptive rho excepted — so that a cold
+        // solver hears what it lacks; a warm one never arrives here but for the stream kernel's loop: solve_async)
+        if (!ke && !(ce && ce->ws) && !(sw.stream_mpc && !st.adaptive_rho)) {
             set_error("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
             return -1;
         }
@@ -1354,6 +1372,12 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
     }
     const bool lean = lk != nullptr;
     if (a.loop && !lean) return NO_LOOP_KERNEL;   // the loop kernel of this calling pattern, or nothing: the caller falls back to the chain
+    const bool sloop = a.stream_loop && !lean && se && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);
+    if (a.stream_loop && !sloop) return NO_LOOP_KERNEL;
+    if (a.mpc_steps > 0 && !ke && !(ce && ce->ws) && !sloop) {   // (unreachable: the stream / generic kernels' own launches are single solves)
+        set_error("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
+        return -1;
+    }
     if (lean && !le && (!ke || ke->G != 1)) P.bounds = reinterpret_cast<const float *>(d_lean + lean_layout(nx, nu).total);   // (upload_packs)
     // ---- launch ----
     // A profiled lean launch carries its two timing events in the kernel's own dispatch packet (start and end of the kernel):
@@ -1367,8 +1391,9 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
     else
         HIP_TRY(ke ? ke->launch(P, precision, carry_g, stream)
                    : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
-                         : (se ? (precision == 2 ? se->launch_f64(P, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), stream)
-                                                 : se->launch(P, precision, lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0), hetero, stream))
+                         : (se ? (sloop ? se->launch_mpc(P, precision, stream_ext(), hetero, stream)
+                                        : (precision == 2 ? se->launch_f64(P, stream_ext(), stream)
+                                                          : se->launch(P, precision, stream_ext(), hetero, stream)))
                                : launch_generic(P, precision, stream))));
     // ---- record ----
     if (profiling) {
@@ -1417,6 +1442,74 @@ __global__ void plant_step_kernel(double *x0d, float *x0, const float *uout, con
     mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
 }
 
+// The stream / generic kernels' step (TINYMPC_HIP_STREAM_MPC): the same rule with the affine term and, on a per-instance-family
+// solver, every instance's own A_b, B_b (ABb: [batch][A_b | B_b], NULL: the family's AB) — x0 <- f + A x0 + B u0, the sum
+// started at f_r, then A's row by ascending column, then B's, one fma each.  With f = 0 that is plant_step_kernel's sum.
+__global__ void plant_step_affine_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved,
+                                         const double *AB, const double *ABb, float *mpc_x, float *mpc_u, int *mpc_iter, int nx,
+                                         int nu, int N, long batch, int steps, int step) {
+    // one thread per (instance, row), an instance's rows in one workgroup: every row reads the old state, a barrier, then the writes
+    const int per_block = (int)blockDim.x / nx, t = (int)threadIdx.x, r = t % nx;
+    const long b = (long)blockIdx.x * per_block + t / nx;
+    const bool on = t < per_block * nx && b < batch;
+    double acc = 0.0;
+    if (on) {
+        const double *A = ABb ? ABb + b * (long)(nx * nx + nx * nu) : AB, *Bm = A + nx * nx;
+        const float *u0 = uout + b * (long)nu * (N - 1);
+        acc = AB[nx * nx + nx * nu + r];
+        for (int j = 0; j < nx; ++j) acc = fma(A[r + j * nx], x0d[b * nx + j], acc);
+        for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
+    }
+    __syncthreads();
+    if (!on) return;
+    const long so = b * steps + step;
+    x0d[b * nx + r] = acc;
+    x0[b * nx + r] = (float)acc;
+    mpc_x[so * nx + r] = (float)acc;
+    for (int a = r; a < nu; a += nx) mpc_u[so * nu + a] = uout[b * (long)nu * (N - 1) + a];
+    if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
+}
+
+// ... of a stream / generic closed loop behind an earlier one: where x0 still is the fp32 rounding of the fp64 plant state that
+// loop left, the loop goes on from that state — mpc_rollout(a) then mpc_rollout(b) is mpc_rollout(a + b) — and from x0
+// wherever the caller has set another one since (on the host or in the device buffer)
+__global__ void plant_resume_kernel(double *x0d, const float *x0, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (float)x0d[i] != x0[i]) x0d[i] = (double)x0[i];
+}
+
+void Solver::plant_start(hipStream_t stream) {
+    const long n0 = (long)batch * nx;
+    if (x0d_live)
+        plant_resume_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+    else
+        plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+    x0d_live = true;
+}
+
+// the plant on the device: [A | B | f] (f as set_fdyn left it, zero without an affine term), per-instance families' [A_b | B_b]
+int Solver::ensure_plant() {
+    const size_t nab = (size_t)nx * nx + (size_t)nx * nu;
+    if (d_plant && !plant_dirty) return 0;
+    if (wait_last_launch()) return -1;   // (a chain still running reads it)
+    if (!d_plant && dev_alloc(d_plant, nab + nx)) return -1;
+    std::vector<double> ab(A.a);
+    ab.insert(ab.end(), B.a.begin(), B.a.end());
+    for (int r = 0; r < nx; ++r) ab.push_back(has_fdyn ? fdyn[r] : 0.0);
+    HIP_TRY(hipMemcpy(d_plant, ab.data(), ab.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (hetero && !d_plant_het) {
+        std::vector<double> abb((size_t)batch * nab);
+        for (size_t b = 0; b < (size_t)batch; ++b) {
+            std::copy(het_A.begin() + b * nx * nx, het_A.begin() + (b + 1) * nx * nx, abb.begin() + b * nab);
+            std::copy(het_B.begin() + b * nx * nu, het_B.begin() + (b + 1) * nx * nu, abb.begin() + b * nab + (size_t)nx * nx);
+        }
+        if (dev_alloc(d_plant_het, abb.size())) return -1;
+        HIP_TRY(hipMemcpy(d_plant_het, abb.data(), abb.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    plant_dirty = false;
+    return 0;
+}
+
 int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     if (!warm_start) {
         set_error("mpc_rollout needs the persistent workspace (set_warm_start(1))");
@@ -1425,25 +1518,29 @@ int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
     const size_t Bn = (size_t)batch;
     if (ensure_mpc_log(mpc_steps)) return -1;
     if (!d_x0d && dev_alloc(d_x0d, Bn * nx)) return -1;
-    if (!d_plant) {
-        if (dev_alloc(d_plant, (size_t)nx * nx + (size_t)nx * nu)) return -1;
-        std::vector<double> ab(A.a);
-        ab.insert(ab.end(), B.a.begin(), B.a.end());
-        HIP_TRY(hipMemcpy(d_plant, ab.data(), ab.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if (ensure_plant()) return -1;
+    const bool affine = !ke;   // the stream / generic kernels' chain: f and per-instance families in the plant
     const long n0 = (long)Bn * nx;
-    plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+    if (affine)
+        plant_start(stream);
+    else
+        plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
     // with a reference sequence every launch reads its step's slice of the sequence as its shared references (step 0's are the
     // solver's own, which stay installed: nothing is copied, and the stream is not synchronised between steps)
     const size_t EX = (size_t)ex(), EU = (size_t)eu();
     Pass pass = whole_batch(false, true);
-    pass.x0d = d_x0d;
+    pass.x0d = affine ? nullptr : d_x0d;   // (the stream / generic chain: every solve starts from the fp32 rounding in d_x0, whatever kernel takes it)
     for (int step = 0; step < mpc_steps; ++step) {
         if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
         if (launch_pass(stream, pass)) return -1;
-        plant_step_kernel<<<(unsigned)((Bn + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
-                                                                        d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,
-                                                                        (long)Bn, mpc_steps, step);
+        if (affine)
+            plant_step_affine_kernel<<<(unsigned)((Bn + 256 / nx - 1) / (256 / nx)), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
+                                                                                   hetero ? d_plant_het : nullptr, d_mpc_x, d_mpc_u,
+                                                                                   d_mpc_iter, nx, nu, N, (long)Bn, mpc_steps, step);
+        else
+            plant_step_kernel<<<(unsigned)((Bn + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
+                                                                            d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,
+                                                                            (long)Bn, mpc_steps, step);
     }
     HIP_TRY(hipGetLastError());
     mpc_steps_last = mpc_steps;
@@ -1462,6 +1559,22 @@ int Solver::rollout_lean_loop(hipStream_t stream, int mpc_steps) {
     Pass pass = whole_batch(false, true, mpc_steps);
     pass.x0d = d_x0d;
     pass.loop = true;
+    const int rc = launch_pass(stream, pass);
+    if (rc == 0) last_rollout_launches = 1;
+    return rc;
+}
+
+// ... and of the stream kernel's (TINYMPC_HIP_STREAM_LOOP): the same set-up; the kernel reads its plant coefficients from its
+// own pack (the fp64 A, B, f rows: the doubles ensure_plant uploads for the chain).
+int Solver::rollout_stream_loop(hipStream_t stream, int mpc_steps) {
+    if (!se || !se->launch_mpc) return NO_LOOP_KERNEL;
+    if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
+    Pass pass = whole_batch(false, true, mpc_steps);
+    pass.x0d = d_x0d;
+    pass.stream_loop = true;
+    if (!se->has_mpc(precision, stream_ext(), hetero)) return NO_LOOP_KERNEL;
+    plant_start(stream);
+    HIP_TRY(hipGetLastError());
     const int rc = launch_pass(stream, pass);
     if (rc == 0) last_rollout_launches = 1;
     return rc;

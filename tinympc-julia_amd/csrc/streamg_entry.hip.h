@@ -208,19 +208,73 @@ hipError_t launch_streamg_f64(const AdmmParams &P, int ext, hipStream_t stream) 
     return hipGetLastError();
 }
 
+// The in-kernel closed loop (admm_streamg_mpc_kernel): the workspace-keeping form with fp64 recurrences — fp32 state (precision
+// 0) for one family or one per instance, fp64 state (precision 2) for one family; EXT in {0, 1, 2}: up to nine kernels per
+// (nx, nu).  A form is built only where the compiler holds it in registers at the wavefronts per SIMD its plain twin is held
+// to (StreamTune); the others stay with the chain of launches:
+//   (12, 4) fp32 state, every EXT, one family or one per instance — three wavefronts leave 168 registers, the loop forms
+//           spill 28 .. 161 of them (their plain twins already spill 4 .. 148);
+//   (6, 3)  fp32 state, one family per instance, EXT = 2 — 2 spilled registers.
+constexpr bool streamg_mpc_built(int nx, int nu, int ext, bool het, bool wide) {
+    if (wide) return !het;
+    if (nx == 12 && nu == 4) return false;
+    if (nx == 6 && nu == 3 && het && ext == 2) return false;
+    return true;
+}
+template <int NX, int NU>
+bool streamg_mpc_has(int precision, int ext, bool het) {
+    return precision != 1 && streamg_mpc_built(NX, NU, ext, het, precision == 2);
+}
+// hipErrorNotSupported: no loop kernel for the call (precision 1; families at precision 2; a form not built) — nothing was launched.
+template <int NX, int NU, int G>
+hipError_t launch_streamg_mpc(const AdmmParams &P, int precision, int ext, bool het, hipStream_t stream) {
+    if (precision == 1 || !streamg_mpc_built(NX, NU, ext, het, precision == 2)) return hipErrorNotSupported;
+    const int grid = (P.batch + 256 / G - 1) / (256 / G);
+    const size_t lds = streamg_lds_bytes<NX, NU, G>(P.N, precision);
+#define TMPC_LAUNCH(EXT_, HET_, ST_)                                                                                   \
+    do {                                                                                                               \
+        if constexpr (streamg_mpc_built(NX, NU, EXT_, HET_, sizeof(ST_) == 8)) {                                       \
+            if (lds > 48 * 1024)                                                                                       \
+                (void)hipFuncSetAttribute((const void *)admm_streamg_mpc_kernel<NX, NU, G, EXT_, HET_, ST_>,           \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
+            hipLaunchKernelGGL((admm_streamg_mpc_kernel<NX, NU, G, EXT_, HET_, ST_>), dim3(grid), dim3(256), lds, stream, P); \
+        }                                                                                                              \
+    } while (0)
+#define TMPC_LAUNCH_EXT(HET_, ST_)                   \
+    do {                                             \
+        if (ext == 2) TMPC_LAUNCH(2, HET_, ST_);     \
+        else if (ext == 1) TMPC_LAUNCH(1, HET_, ST_); \
+        else TMPC_LAUNCH(0, HET_, ST_);              \
+    } while (0)
+    if (precision == 2) TMPC_LAUNCH_EXT(false, double);
+    else if (het) TMPC_LAUNCH_EXT(true, float);
+    else TMPC_LAUNCH_EXT(false, float);
+#undef TMPC_LAUNCH_EXT
+#undef TMPC_LAUNCH
+    return hipGetLastError();
+}
+
+// the loop launcher of a shape, in a translation unit of its own (sinst_mpc_*.hip)
+#define TMPC_DEFINE_STREAMG_MPC(NX, NU, GG)                                                                              \
+    hipError_t launch_stream##GG##_mpc_##NX##_##NU(const AdmmParams &P, int precision, int ext, bool het, hipStream_t stream) { \
+        return launch_streamg_mpc<NX, NU, GG>(P, precision, ext, het, stream);                                           \
+    }
 // the fp64-state launcher of a shape, in a translation unit of its own (sinst_f64_*.hip) ...
 #define TMPC_DEFINE_STREAMG_F64(NX, NU, GG)                                                                   \
     hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &P, int ext, hipStream_t stream) {        \
         return launch_streamg_f64<NX, NU, GG>(P, ext, stream);                                                \
     }
-// ... and the entry of a shape that has one: TMPC_DEFINE_STREAMG_ENTRY plus that launcher and its reported name
+// ... and the entry of a shape that has one: TMPC_DEFINE_STREAMG_ENTRY plus that launcher and its reported name — and, the same
+// three shapes having them, the loop launcher (sinst_mpc_*.hip)
 #define TMPC_DEFINE_STREAMG_ENTRY_F64(NX, NU, GG)                                                                   \
     hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &, int, hipStream_t);                          \
+    hipError_t launch_stream##GG##_mpc_##NX##_##NU(const AdmmParams &, int, int, bool, hipStream_t);               \
     const StreamEntry *stream##GG##_entry_##NX##_##NU() {                                                          \
         static const StreamEntry e = {NX, NU, GG, "stream" #GG "<" #NX "," #NU ">", &build_streamg_coef<NX, NU, GG>, \
                                       &build_streamg_bounds<NX, NU, GG>, &streamg_lds_bytes<NX, NU, GG>,           \
                                       &streamg_scratch_floats<NX, NU>, &launch_streamg<NX, NU, GG>,                \
-                                      &launch_stream##GG##_f64_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";f64>"}; \
+                                      &launch_stream##GG##_f64_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";f64>",  \
+                                      &launch_stream##GG##_mpc_##NX##_##NU, &streamg_mpc_has<NX, NU>};             \
         return &e;                                                                                                 \
     }
 

@@ -110,7 +110,8 @@ get_gpus() = Int(ccall((:get_gpus, _lib_path()), Int32, ()))
 # the on-chip kernels); true (default): the reference's semantics, the workspace persists between solves
 # Arithmetic of the solver: 0 = fp64 recurrences over fp32 state (default, 1e-5 of the reference), 1 = all fp32 (faster on
 # shapes without a matrix-core kernel, does not hold 1e-5 on every instance), 2 = fp64 end to end like the reference
-# (types.hpp:15) — for validation against the CPU solver; slow.
+# (types.hpp:15) — for validation against the CPU solver; slow.  mpc_rollout fails at precision 2 unless the library's
+# TINYMPC_HIP_STREAM_MPC=1 is in the environment at setup (see mpc_rollout).
 function set_precision(solver::TinyMPCSolver, precision::Integer)
     _need(solver)
     _ok(ccall((:set_precision, _lib_path()), Int32, (Int32,), precision), "Failed to set precision")
@@ -221,7 +222,8 @@ end
 # TINYMPC_HIP_LEAN_LOOP=1 asks for that kernel's in-kernel loop, which takes constant references only).  mpc_rollout fails, naming the
 # condition, with fewer sequence steps than loop steps, per-instance references, adaptive rho, precision 2, a lanes-per-instance
 # entry with a horizon above 20, shapes without a
-# closed loop (stream / generic kernels); a sharded solver (set_gpus > 1) takes no sequence.
+# closed loop (stream / generic kernels) — precision 2 and those shapes unless TINYMPC_HIP_STREAM_MPC=1 gives them their
+# chained loop (mpc_rollout below); a sharded solver (set_gpus > 1) takes no sequence.
 # (julia/examples/rocket_landing_batch_closed_loop.jl, julia/examples/quadrotor_batch_tracking.jl)
 function set_ref_sequence(solver::TinyMPCSolver, x_ref_seq::Array{Float64,3}, u_ref_seq::Array{Float64,3})
     _need(solver)
@@ -237,6 +239,10 @@ end
 # warm-start workspace staying on chip (the host loops of cartpole_example_mpc.jl:35-51, rocket_landing_constraints.jl:97-134).
 # Returns (status of the last solve, x (nx, steps, batch) plant states, u (nu, steps, batch) applied controls,
 # iter (steps, batch) ADMM iterations per step, negative where the step hit max_iter).
+# Problems that run on the stream / generic kernels (other horizons, linear rows, per-instance families, precision 2, ...)
+# have no closed loop by default and fail here.  TINYMPC_HIP_STREAM_MPC=1 in the environment at setup runs it as a chain of
+# `steps` warm launches with the fp64 plant step between them; TINYMPC_HIP_STREAM_LOOP=1 beside it as one launch of the
+# stream kernel's in-kernel loop where one is built (the same results, bit for bit).  Both are off by default.
 function mpc_rollout(solver::TinyMPCSolver, steps::Integer)
     _need(solver)
     nx, nu, B = solver.nx, solver.nu, solver.batch

@@ -785,7 +785,9 @@ class BatchSolver:
         kernels at horizons up to 20 (quad), launch by launch on the chained loops (mfma; the lean kernel's with TINYMPC_HIP_LEAN_WS=1).  mpc_rollout
         raises TinyMPCError, naming the condition, with fewer sequence steps than loop steps, with per-instance references
         (set after the sequence — a later SHARED set_x_ref / set_u_ref drops the sequence instead), with adaptive rho, at
-        precision 2, on a quad entry with a horizon above 20, and on shapes without a closed loop (stream / generic kernels)"""
+        precision 2, on a quad entry with a horizon above 20, and on shapes without a closed loop (stream / generic kernels) —
+        the last two unless TINYMPC_HIP_STREAM_MPC=1 (see mpc_rollout) gives those solvers their chained loop, which takes the
+        sequence launch by launch"""
         if x_ref_seq is None:
             self._chk(self.lib.tinympc_set_ref_sequence(self.h, None, 0, 0, None, 0, 0, 0), "set_ref_sequence")
             return
@@ -801,6 +803,12 @@ class BatchSolver:
         """`steps` fused closed-loop MPC steps in one launch (plant = the family's own A, B).
         (TINYMPC_HIP_LEAN_WS=1 when the solver is created: cartpole-class shapes on the lean kernel, as a chain of `steps`
         launches; with TINYMPC_HIP_LEAN_LOOP=1 beside it as one launch of its in-kernel loop — the same results.)
+        Solvers on the stream / generic kernels (a horizon without a built-in entry, linear rows, cones or the affine term
+        outside mfmat, per-instance families, other (nx, nu), precision 2) raise TinyMPCError by default.  With
+        TINYMPC_HIP_STREAM_MPC=1 when the solver is created they run the loop as a chain of `steps` warm launches with the
+        plant x+ = f + A x + B u0 in fp64 between them (precision 0, 1, 2; reference sequences; each solve starts from the
+        fp32 rounding of x+); TINYMPC_HIP_STREAM_LOOP=1 beside it: one launch of the stream kernel's in-kernel loop where it
+        is built, bit-identical to the chain.  Adaptive rho, families at precision 2 and set_warm_start(0) stay refused.
         Returns dict(status, x=(nx, steps, B), u=(nu, steps, B), iter=(steps, B), solved=(steps, B))."""
         st = int(self.lib.tinympc_mpc_rollout(self.h, int(steps), c_vp(stream or 0)))
         if st < 0:
@@ -831,7 +839,9 @@ class BatchSolver:
         """0: fp64 recurrences, fp32 state (default); 1: all fp32; 2: all fp64 like the reference — on the generic kernel
         (slow), except cold one-shot solves of the lean kernel's shapes (its fp64-state form, specialised on request) and, with
         TINYMPC_HIP_STREAM_F64=1 set when the solver is created, every fixed-rho unchunked solve of (4,1), (6,3), (12,4) shapes
-        on the stream kernel's fp64-state form ("stream4<NX,NU;f64>")"""
+        on the stream kernel's fp64-state form ("stream4<NX,NU;f64>").  Precision 2 has no closed loop (mpc_rollout raises)
+        unless TINYMPC_HIP_STREAM_MPC=1 is set when the solver is created: then the chain of launches, or with
+        TINYMPC_HIP_STREAM_LOOP=1 the fp64-state form's in-kernel loop"""
         self._chk(self.lib.tinympc_set_precision(self.h, int(precision)), "set_precision")
 
     def reload_switches(self):
