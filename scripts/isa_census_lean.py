@@ -14,8 +14,11 @@ if not os.environ.get("TMPC_CENSUS_ASM"):
                stderr=subprocess.DEVNULL)
 lines = open(asm).read().splitlines()
 # (the trailing template argument is the (A, B) pattern: 0x1000a0021cc63 = 281517928598627, the cartpole model's; 0 the dense form)
-KERNELS = {"sparse": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm281517928598627EEEvNS_10AdmmParamsE:",
-           "dense": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm0EEEvNS_10AdmmParamsE:"}
+# (WS = MPC = false behind the pattern since the workspace-keeping forms exist)
+KERNELS = {"sparse": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm281517928598627ELb0ELb0EEEvNS_10AdmmParamsE:",
+           "dense": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm0ELb0ELb0EEEvNS_10AdmmParamsE:"}
+if tag < "r08":
+    KERNELS = {k: v.replace("ELb0ELb0EEEv", "EEEv") for k, v in KERNELS.items()}
 if tag < "r06":
     KERNELS = {"dense": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfEEvNS_10AdmmParamsE:"}
 
@@ -43,6 +46,7 @@ def census_of(start):
         ("fp64 FMA / mul / add (the recurrences)", r"v_(fma|fmac|mul|add)_f64"),
         ("fp32 <-> fp64 conversions", r"v_cvt_f(32_f64|64_f32)"),
         ("AGPR moves (v_accvgpr_read / write)", r"v_accvgpr_"),
+        ("fp32 packed add / sub (two knots per instruction)", r"v_pk_(add|mul|fma)_f32"),
         ("fp32 arithmetic (add / sub)", r"v_(add|sub|subrev|mul|fma|fmac)_f32"),
         ("fp32 med3 (the box projection)", r"v_(min|max|med3)_f32"),
         ("moves / selects / integer VALU", r"v_(mov|cndmask|readlane|readfirstlane|writelane|add_u32|lshl|and|or|cmp)"),

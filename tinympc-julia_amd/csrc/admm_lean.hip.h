@@ -56,6 +56,12 @@
 #ifndef TMPC_LEAN_STORE_W
 #define TMPC_LEAN_STORE_W 0       // floats per instance and pass of the wide store; 0: wide_stage_width(EX) (tuning aid)
 #endif
+#ifndef TMPC_LEAN_PK
+// 1: the headline form (PK, at the kernel) updates input slack and dual of two knots at a time with packed fp32 adds
+// (v_pk_add_f32: a lone wavefront issues it at the rate of any vector instruction, profiles/r07_fp64_issue_probe.txt);
+// 0: one knot at a time everywhere (the A/B switch)
+#define TMPC_LEAN_PK 1
+#endif
 #ifndef TMPC_LEAN_FOLD_FIRST
 // 1: the status fold ahead of the final store (its fence then has no solution stores to wait for).  Tried and left off: the
 // folding wavefront's stores then wait for the fold's atomics and ticket (the fold is 11-20 us behind 256 workgroups, not 3),
@@ -72,6 +78,8 @@ struct LeanPack {
     static constexpr int O_M = LL.oM, O_K = LL.oK, O_B = LL.oB, O_C = LL.oC, O_H = LL.oH, O_S = LL.oS, O_P = LL.oP, O_T = LL.oT, LEN = LL.len;
     static constexpr int NLOADS = LL.padded / 8;     // s_load_dwordx16 per 8 doubles
 };
+
+typedef float lean_f2 __attribute__((ext_vector_type(2)));   // a pair of knots' fp32 values (PK)
 
 // clamp(t, lo, hi) as one v_med3_f32 (lo <= hi; +-inf for "no bound")
 __device__ __forceinline__ float clamp3(float t, float lo, float hi) { return __builtin_amdgcn_fmed3f(t, lo, hi); }
@@ -149,6 +157,13 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     constexpr bool SPR = SP != 0;
     static_assert(!SPR || (NX <= 4 && NU <= 4), "sparse pattern: nx, nu <= 4");
     constexpr bool HB = !SPR && !LIVE && !XB && ONE;
+    // PK (the headline form: one wavefront per SIMD, fixed iterations, no state bound, nothing kept, one set of input bounds,
+    // fp32 state): the iterations without residuals update slack and dual of the knots (k - 1, k), k odd, together — per input
+    // row t = {u_{k-1}, u_k} + {y_{k-1}, y_k} and y = t - znew as packed adds (the clamp has no packed form), and in the
+    // backward sweep r~ = znew - y of both knots in one packed subtract.  The slack is not on the rollout's chain (x+ takes the
+    // unclamped u), so the even knot only parks (float)u for one knot; an unpaired last knot stays scalar.  The same IEEE
+    // operations on the same values: results are bit-identical to the scalar form.
+    constexpr bool PK = TMPC_LEAN_PK && ONE && !LIVE && !XB && !WS && UBK && !F64;
     auto mh_zero = [](int m, int j) { return HB && j < m - NU; };               // M^[m][j] outside the band
     auto bh_zero = [](int m, int a) { return HB && m > a; };                    // b^[m][a] below the trapezoid
     auto a_nz = [](int m, int j) { return !SPR || lsp_a(SP, NX, m, j); };       // SP: A[m][j] is not zero
@@ -457,6 +472,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         double xr[NX];                                                          // XB: the running x_k
 #pragma unroll
         for (int m = 0; m < NX; ++m) xr[m] = X[0][m];
+        float upk[PK ? NU : 1];                                                 // PK: the even knot's (float)u, until its partner
         sfor<0, N - 1>([&](auto kk) {
             constexpr int k = decltype(kk)::value;
             constexpr int kx = XB ? 0 : k;                                      // where x_k lives: the running vector, or the trajectory
@@ -541,6 +557,22 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                     }
                 }
             }
+            constexpr bool PK_ODD = PK && !RES && (k & 1), PK_EVEN = PK && !RES && !(k & 1) && k + 1 < N - 1;
+            if constexpr (PK_EVEN) {
+#pragma unroll
+                for (int a = 0; a < NU; ++a) upk[a] = (float)u[a];
+            }
+            if constexpr (PK_ODD) {                                             // knots k - 1 and k: admm.cpp:45, :50-52, :67
+#pragma unroll
+                for (int a = 0; a < NU; ++a) {
+                    const lean_f2 t = lean_f2{upk[a], (float)u[a]} + lean_f2{(float)Y[k - 1][a], (float)Y[k][a]};
+                    const lean_f2 zn = {clamp3(t.x, (float)lo[a], (float)hi[a]), clamp3(t.y, (float)lo[a], (float)hi[a])};
+                    const lean_f2 yn = t - zn;
+                    Y[k - 1][a] = yn.x, Y[k][a] = yn.y;
+                    Z[k - 1][a] = zn.x, Z[k][a] = zn.y;
+                }
+            }
+            if constexpr (!PK_ODD && !PK_EVEN)
 #pragma unroll
             for (int a = 0; a < NU; ++a) {
                 const ST uf = (ST)u[a];
@@ -611,12 +643,20 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             p[m] = XB ? (double)QT[N - 1][m] : X[XB ? 0 : N - 1][m];
             if constexpr (REFS == REF_SHARED) p[m] += s_cpt[m];
         }
+        float rpk[PK ? NU : 1];                                                 // PK: the even knot's r~, formed with its partner's
         sfor<0, N - 1>([&](auto kk) {
             constexpr int k = N - 2 - decltype(kk)::value;
             double r[NU], t[NU];
             if constexpr (REFS == REF_SHARED) asm volatile("" ::: "memory");
 #pragma unroll
             for (int a = 0; a < NU; ++a) {
+                if constexpr (PK && (k & 1)) {                                  // r~ of knots k - 1 and k
+                    const lean_f2 rp = lean_f2{(float)Z[k - 1][a], (float)Z[k][a]} - lean_f2{(float)Y[k - 1][a], (float)Y[k][a]};
+                    rpk[a] = rp.x;
+                    r[a] = (double)rp.y;
+                } else if constexpr (PK && k + 1 < N - 1) {
+                    r[a] = (double)rpk[a];
+                } else
                 r[a] = (double)(Z[k][a] - Y[k][a]);                             // r~ = znew - y  (:77-78)
                 if constexpr (REFS == REF_SHARED) r[a] += s_cr[k * NU + a];     //      + R~ uref / rho
                 t[a] = r[a];
@@ -962,7 +1002,10 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             m3 = fmaxf(m3, __shfl_xor(m3, o, 64));
         }
         const unsigned long long unsolved = __builtin_amdgcn_ballot_w64(active && !conv);
-        fold_status(P, m0, m1, m2, m3, __popcll(unsolved), tid);   // (one set of atomics per workgroup)
+        // (one record and one ticket per workgroup; the workspace-keeping forms, at the edge of their registers and LDS, keep
+        // the accumulator fold every other family has)
+        if constexpr (WS) fold_status(P, m0, m1, m2, m3, __popcll(unsolved), tid);
+        else fold_status_records(P, m0, m1, m2, m3, __popcll(unsolved), tid);
     };
 #ifdef TMPC_LEAN_CLOCK_PROBE
     const unsigned long long probe_t1 = __builtin_amdgcn_s_memtime(), probe_r1 = __builtin_amdgcn_s_memrealtime();   // loop end

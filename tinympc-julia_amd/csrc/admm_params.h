@@ -21,6 +21,8 @@ enum { QUAD_REF_SEQ_MAX_N = 20 };
 //   [4]    number of instances that hit max_iter without converging
 //   [5]    number of instances whose solution contains a non-finite value
 enum { GSTAT_WORDS = 8 };
+// A workgroup's record of the status fold: the four maxima as float bits, its unsolved count, padding — 32 bytes, aligned
+enum { GSLOT_WORDS = 8, GSLOT_DEFAULT_CAP = 1024 };
 
 // generic (runtime-shape) kernel limits
 constexpr int LIN_MAX_ROWS = 8, GEN_MAX_NX = 64;
@@ -100,6 +102,9 @@ struct AdmmParams {
     // ---- generic kernel, precision 2 (fp64 end to end): the workspace kept between solves (Ws64) and the tolerances in fp64 ----
     double *ws64;
     double abs_pri_tol64, abs_dua_tol64;
+    // ---- lean kernel, one-shot forms: the status fold's records (fold_status_records) ----
+    uint32_t *gslot;  // [gslot_cap][GSLOT_WORDS] one status record per workgroup; never zeroed.  NULL: none
+    int gslot_cap;    // workgroups with blockIdx.x below it write a record, the others accumulate in gacc
 };
 enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4 };
 
@@ -234,6 +239,123 @@ __device__ __forceinline__ void fold_status(const AdmmParams &P, float m0, float
 #pragma unroll
             for (int i = 0; i < 5; ++i) P.gstat[i] = tot[i];
         }
+    }
+}
+
+// fold_status with one record per workgroup: what the one-shot lean kernels call (admm_lean.hip.h).  Same contract, same
+// accumulator block and ticket, so launches of either kind may follow each other on one solver.  The wavefronts of a
+// workgroup (at most four) meet in LDS and ONE lane per workgroup reports; the last workgroup to finish (ticket in gacc[7])
+// publishes the totals to P.gstat and hands the accumulator back zeroed to the next launch.
+// How a workgroup reports:
+//   * record (P.gslot set, blockIdx.x < P.gslot_cap, at most four wavefronts): the lane writes the five values to the
+//     workgroup's own 32-byte record with agent-scope write-through stores, waits for them (s_waitcnt vmcnt(0)) and takes its
+//     ticket with ONE relaxed atomic — no fence (a fence writes the L2 back, behind megabytes of solution stores that nothing
+//     here needs ordered) and one atomic on the shared line where the accumulator path has six.  Records are overwritten, not
+//     accumulated, and never zeroed: every workgroup below min(gridDim.x, cap) rewrites its record in every launch before
+//     its ticket, and the last arriver reads that range only (records beyond it may be older launches');
+//   * accumulator (every other workgroup): atomicMax / atomicAdd on gacc[0..4], a fence, the ticket.
+// The last arriver — wavefront 0 of its workgroup, told by lane 0's ticket — executes one agent-scope acquire, lane 0 swaps
+// the accumulator words out (issued together), all lanes load the records `lane, lane + 64, ...` with agent-scope loads,
+// four rounds in flight, the wavefront reduces and lane 0 stores the block.
+// EVERY thread of the workgroup must call it, EXACTLY ONCE per launch (a second call would overwrite the record where the
+// accumulator tolerated it, and take a second ticket): the lean kernel calls it once, outside its loops, either ahead of the
+// final store or behind it (TMPC_LEAN_FOLD_FIRST).  Lane 0 of each wavefront carries that wavefront's values.
+__device__ __forceinline__ void fold_status_records(const AdmmParams &P, float m0, float m1, float m2, float m3,
+                                            int unsolved_in_wave, int tid) {
+    __shared__ float s_fold_m[4][4];
+    __shared__ int s_fold_u[4];
+    const int w = tid >> 6, nw = ((int)blockDim.x + 63) >> 6;
+    const bool merged = nw <= 4;
+    if ((tid & 63) == 0) {
+        if (merged) {
+            s_fold_m[w][0] = m0, s_fold_m[w][1] = m1, s_fold_m[w][2] = m2, s_fold_m[w][3] = m3;
+            s_fold_u[w] = unsolved_in_wave;
+        } else {
+            atomicMax(&P.gacc[0], __float_as_uint(m0));
+            atomicMax(&P.gacc[1], __float_as_uint(m1));
+            atomicMax(&P.gacc[2], __float_as_uint(m2));
+            atomicMax(&P.gacc[3], __float_as_uint(m3));
+            if (unsolved_in_wave) atomicAdd(&P.gacc[4], (uint32_t)unsolved_in_wave);
+        }
+    }
+    __syncthreads();
+    if (tid >= 64) return;                                    // wavefront 0 goes on: its lane 0 reports, all of it may reduce
+    const int nrec = P.gslot ? min((int)gridDim.x, P.gslot_cap) : 0;   // the records of this launch
+    int last = 0;
+    if (tid == 0) {
+        bool recorded = false;
+        if (merged) {
+            int un = 0;
+            for (int i = 0; i < nw; ++i) {
+                m0 = i ? fmaxf(m0, s_fold_m[i][0]) : s_fold_m[0][0];
+                m1 = i ? fmaxf(m1, s_fold_m[i][1]) : s_fold_m[0][1];
+                m2 = i ? fmaxf(m2, s_fold_m[i][2]) : s_fold_m[0][2];
+                m3 = i ? fmaxf(m3, s_fold_m[i][3]) : s_fold_m[0][3];
+                un += s_fold_u[i];
+            }
+            if ((int)blockIdx.x < nrec) {
+                unsigned long long *rec = reinterpret_cast<unsigned long long *>(P.gslot + (size_t)blockIdx.x * GSLOT_WORDS);
+                __hip_atomic_store(rec + 0, (unsigned long long)__float_as_uint(m0) | ((unsigned long long)__float_as_uint(m1) << 32),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(rec + 1, (unsigned long long)__float_as_uint(m2) | ((unsigned long long)__float_as_uint(m3) << 32),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(rec + 2, (unsigned long long)(uint32_t)un, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the record is written through before the ticket says so
+                recorded = true;
+            } else {
+                atomicMax(&P.gacc[0], __float_as_uint(m0));
+                atomicMax(&P.gacc[1], __float_as_uint(m1));
+                atomicMax(&P.gacc[2], __float_as_uint(m2));
+                atomicMax(&P.gacc[3], __float_as_uint(m3));
+                if (un) atomicAdd(&P.gacc[4], (uint32_t)un);
+            }
+        }
+        if (!recorded) __threadfence();  // this workgroup's contributions before its ticket
+        last = __hip_atomic_fetch_add(&P.gacc[7], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    }
+    if (!__shfl(last, 0, 64)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    uint32_t tot[5] = {0, 0, 0, 0, 0};
+    if (tid == 0) {                   // (the swaps issued together and waited for once: this is the tail of the launch)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) tot[i] = atomicExch(&P.gacc[i], 0u);
+        atomicExch(&P.gacc[6], 0u);   // (persistent kernels' tile counter)
+        atomicExch(&P.gacc[7], 0u);
+    }
+    uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0, ru = 0;   // (non-negative floats order like their bits)
+    for (int base = 0; base < nrec; base += 4 * 64) {
+        unsigned long long a[4], b[4], c[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            // (a lane beyond the last record re-reads that record and drops it: no branch between the loads, all twelve in flight)
+            const int s = min(base + q * 64 + tid, nrec - 1);
+            unsigned long long *rec = reinterpret_cast<unsigned long long *>(P.gslot + (size_t)s * GSLOT_WORDS);
+            a[q] = __hip_atomic_load(rec + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            b[q] = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            c[q] = __hip_atomic_load(rec + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (base + q * 64 + tid >= nrec) a[q] = b[q] = c[q] = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            r0 = max(r0, (uint32_t)a[q]), r1 = max(r1, (uint32_t)(a[q] >> 32));
+            r2 = max(r2, (uint32_t)b[q]), r3 = max(r3, (uint32_t)(b[q] >> 32));
+            ru += (uint32_t)c[q];
+        }
+    }
+    if (nrec) {
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            r0 = max(r0, (uint32_t)__shfl_xor((int)r0, off, 64)), r1 = max(r1, (uint32_t)__shfl_xor((int)r1, off, 64));
+            r2 = max(r2, (uint32_t)__shfl_xor((int)r2, off, 64)), r3 = max(r3, (uint32_t)__shfl_xor((int)r3, off, 64));
+            ru += (uint32_t)__shfl_xor((int)ru, off, 64);
+        }
+    }
+    if (tid == 0) {
+        tot[0] = max(tot[0], r0), tot[1] = max(tot[1], r1), tot[2] = max(tot[2], r2), tot[3] = max(tot[3], r3), tot[4] += ru;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) P.gstat[i] = tot[i];
     }
 }
 #endif

@@ -175,6 +175,8 @@ struct Switches {
          stream_loop = false,                               // TINYMPC_HIP_STREAM_LOOP: with stream_mpc, one launch of the stream kernel's in-kernel loop where it is built
          event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
     int mfmac_debug = 0;    // timing probe builds only
+    int fold_slots = -1;    // TINYMPC_HIP_FOLD_SLOTS = n: the status fold's records for the first n workgroups only (at most
+                            // GSLOT_DEFAULT_CAP; 0: none, the accumulator path for all — the A/B switch); unset: all of them
 };
 Switches read_switches();
 
@@ -275,6 +277,7 @@ struct Solver {
     int *d_iter = nullptr, *d_solved = nullptr;
     float *d_sd = nullptr, *d_sy = nullptr, *d_sz = nullptr, *d_sg = nullptr, *d_sv = nullptr;
     uint32_t *d_gstat = nullptr;  // [2 * GSTAT_WORDS]: the public status block, then the kernels' accumulator
+    uint32_t *d_gslot = nullptr;  // [GSLOT_DEFAULT_CAP][GSLOT_WORDS]: the workgroups' status records (fold_status), never zeroed
     uint32_t *h_gstat = nullptr;  // pinned
     // host round trips (fp64 caller buffers <-> fp32 device buffers): pinned staging, copy stream, two chunk slots
     float *h_stage = nullptr;

@@ -142,6 +142,7 @@ Solver::~Solver() {
     dev_free(d_coef);
     dev_free(d_bounds);
     dev_free(d_gstat);
+    dev_free(d_gslot);
     dev_free(d_sens);
     dev_free(d_lean);
     dev_free(d_plant);
@@ -283,6 +284,7 @@ int Solver::init(const double *A_, const double *B_, const double *Q_, const dou
     if (select_kernel()) return -1;
     if (dev_alloc(d_gstat, (size_t)2 * GSTAT_WORDS)) return -1;
     HIP_TRY(hipMemset(d_gstat, 0, 2 * GSTAT_WORDS * sizeof(uint32_t)));
+    if (dev_alloc(d_gslot, (size_t)GSLOT_DEFAULT_CAP * GSLOT_WORDS)) return -1;   // (written before it is read: fold_status)
     HIP_TRY(hipHostMalloc((void **)&h_gstat, GSTAT_WORDS * sizeof(uint32_t), hipHostMallocDefault));
     std::memset(h_gstat, 0, GSTAT_WORDS * sizeof(uint32_t));
     packs_dirty = true;
@@ -359,6 +361,7 @@ Switches read_switches() {
     w.stream_loop = on("TINYMPC_HIP_STREAM_LOOP");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
+    if (const char *f = std::getenv("TINYMPC_HIP_FOLD_SLOTS")) w.fold_slots = std::max(0, std::atoi(f));
     return w;
 }
 
@@ -1225,6 +1228,8 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     P.sv = d_sv;
     P.gstat = d_gstat;
     P.gacc = d_gstat + GSTAT_WORDS;
+    P.gslot_cap = sw.fold_slots < 0 ? (int)GSLOT_DEFAULT_CAP : std::min(sw.fold_slots, (int)GSLOT_DEFAULT_CAP);
+    P.gslot = P.gslot_cap > 0 ? d_gslot : nullptr;
     P.scratch = d_scratch;
     P.idx = a.idx;
     P.iter_offset = a.iter_offset;
