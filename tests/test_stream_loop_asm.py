@@ -31,9 +31,14 @@ def test_switches_are_declared_read_and_off_by_default():
     reader = reader[:reader.index("\n}")]
     assert 'w.stream_mpc = on("TINYMPC_HIP_STREAM_MPC");' in reader
     assert 'w.stream_loop = on("TINYMPC_HIP_STREAM_LOOP");' in reader
-    # the chain asks the first switch, the loop is tried only inside the chain's branch
-    assert re.search(r"bool stream_chain\(\) const \{ return sw\.stream_mpc && warm_start\b", header)
-    assert re.search(r"if \(mpc_steps > 0 && stream_chain\(\)\) \{\s*if \(sw\.stream_loop\) \{", solver)
+    # the chain asks the first switch, the loop is tried only inside the chain's branch (plan_rollout, the one place that reads
+    # the two); a solver without the persistent workspace is refused before either route is taken
+    plan = solver[solver.index("Solver::plan_rollout(int mpc_steps) {"):]
+    plan = plan[:plan.index("\n}")]
+    assert re.search(r"const bool stream = sw\.stream_mpc && !ke && !ce && !st\.adaptive_rho;", plan)
+    assert re.search(r"\} else if \(stream\) \{\s*loop\.stream_loop = true;\s*route = \(sw\.stream_loop && ", plan)
+    assert plan.index("if (!warm_start) return refuse(") < plan.index("} else if (stream) {")
+    assert solver.count("sw.stream_loop") == 1 and plan.count("sw.stream_mpc") == solver.count("sw.stream_mpc") - 1   # (+ select_kernel's precision 2 gate)
     for shape in ("4_1", "6_3", "12_4"):
         assert os.path.isfile(os.path.join(CSRC, f"sinst_mpc_{shape}.hip"))
 

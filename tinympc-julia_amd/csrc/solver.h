@@ -96,7 +96,7 @@ struct LeanPlanIn {
     int slots = 0, iters = 0, mpc_steps = 0;
     bool cold = false, save = false, indexed = false, adaptive_rho = false;
     int ref_mode = REF_ZERO;
-    bool loop = false;               // the in-kernel closed loop or nothing (rollout_lean_loop)
+    bool loop = false;               // the in-kernel closed loop or nothing (Pass::loop)
     bool state_bounds = false;       // some enabled state bound is finite
     bool g_maybe_nonzero = false;    // the kept workspace's state dual may hold something
     bool live = false;               // both tolerances positive
@@ -299,7 +299,6 @@ struct Solver {
     int mpc_cap = 0, mpc_steps_last = 0;
     size_t scratch_cap = 0;
     bool solved_once = false;
-    bool rollout_quad = false;     // the pending closed loop runs fused on the quad kernel
     bool g_maybe_nonzero = false;  // the workspace's state dual may hold non-zeros (see launch_pass)
     bool profiling = false;
     static constexpr int EV_RING = 256;  // event pairs around the most recent launches (profiling mode)
@@ -324,7 +323,7 @@ struct Solver {
     hipEvent_t ev_done = nullptr, ev_wait = nullptr;
     bool ev_done_pending = false;
     int wait_last_launch();
-    int select_kernel(bool rollout = false);  // rollout: the next launch is the fused closed loop
+    int select_kernel(bool rollout = false);  // rollout: for a closed loop (plan_rollout)
     // routing (solver.hip, "kernel routing"): switches, the families' routes, the cached decision
     Switches sw;
     bool strict_precision = false;            // tinympc_set_strict_precision: precision = 1 really means fp32 recurrences
@@ -367,39 +366,51 @@ struct Solver {
         int mpc_steps = 0;
         const double *x0d = nullptr;                        // the fp64 plant state of a closed loop stepped outside the quad kernel
         const float *xref = nullptr, *uref = nullptr;       // shared references where not the solver's own (a step of a reference sequence)
-        bool loop = false;                                  // the lean kernel's in-kernel closed loop, or nothing
-        bool stream_loop = false;                           // the stream kernel's in-kernel closed loop, or nothing
+        bool loop = false;                                  // the lean kernel's in-kernel closed loop (plan_rollout found its kernel)
+        bool stream_loop = false;                           // the stream kernel's in-kernel closed loop (likewise)
     };
-    static constexpr int NO_LOOP_KERNEL = 1;                // launch_pass with Pass::loop: nothing was launched, the chain takes the loop
     Pass whole_batch(bool cold, bool save, int mpc_steps = 0) const;
     int launch_pass(hipStream_t stream, const Pass &);
     LeanPlan plan_lean(const Pass &) const;                 // lean_plan of this solver and that launch
+    // the lean entry and variant that take a launch (null: the selected family's kernel runs it), and whether the stream kernel's
+    // in-kernel loop is built for it: asked by launch_pass for the launch, by plan_rollout before anything is launched
+    struct Pick {
+        LeanPlan plan;
+        const LeanEntry *lean = nullptr;
+        bool stream_loop = false;
+    };
+    Pick pick_kernel(const Pass &);
     void fill_params(AdmmParams &P, const Pass &) const;
     int ensure_mpc_log(int mpc_steps);                      // the closed loops' log buffers
     int record_done(hipStream_t stream, hipEvent_t carried = nullptr);   // the completion event every getter waits for
     // tolerance-terminated solves of big batches in chunks of `chunk_iters` iterations: after each chunk the
     // instances still iterating are compacted, so wavefronts do not idle behind their slowest instance
     int solve_chunked(hipStream_t stream);
-    // closed loop on the matrix-core kernel: per step one WS launch and a plant-update kernel, stream-ordered, the plant
-    // state kept in fp64 on the device between steps (what the quad kernel's fused loop keeps in registers)
-    int rollout_steps(hipStream_t stream, int mpc_steps);
-    // TINYMPC_HIP_LEAN_LOOP: the same loop as ONE launch of the lean kernel's in-kernel loop (NO_LOOP_KERNEL: none for this
-    // calling pattern, nothing launched)
-    int rollout_lean_loop(hipStream_t stream, int mpc_steps);
-    // TINYMPC_HIP_STREAM_MPC: the stream and generic kernels' closed loop is rollout_steps too (stream_chain: the routed kernel
-    // is one of them and the switch is set); with TINYMPC_HIP_STREAM_LOOP, ONE launch of the stream kernel's in-kernel loop
-    // (NO_LOOP_KERNEL: none for this shape / precision / family kind, nothing launched)
-    bool stream_chain() const { return sw.stream_mpc && warm_start && !ke && !ce && !st.adaptive_rho; }
-    int rollout_stream_loop(hipStream_t stream, int mpc_steps);
+    // mpc_rollout.  plan_rollout decides the route, once and before anything is launched — every condition and every refusal
+    // of a closed loop is there (solver.hip) — and solve_async launches it:
+    //   Fused       the loop inside the selected kernel (the lanes-per-instance kernels, mfmat): one launch_pass
+    //   Chain       per step one workspace-carrying launch and the plant step, stream-ordered, the plant state kept in fp64 on
+    //               the device between steps (mfma; the lean kernel under TINYMPC_HIP_LEAN_WS; the stream / generic kernels
+    //               under TINYMPC_HIP_STREAM_MPC, stream_plant: f and per-instance families in the plant, the state resumed)
+    //   LeanLoop    ONE launch of the lean kernel's in-kernel loop (TINYMPC_HIP_LEAN_LOOP)
+    //   StreamLoop  ONE launch of the stream kernel's (TINYMPC_HIP_STREAM_LOOP)
+    //   Refused     the reason is the last error
+    enum class Rollout { Refused, Fused, Chain, LeanLoop, StreamLoop };
+    struct RolloutPlan {
+        Rollout route = Rollout::Refused;
+        bool stream_plant = false;
+    };
+    RolloutPlan plan_rollout(int mpc_steps);
+    int rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant);
+    int rollout_loop(hipStream_t stream, int mpc_steps, Rollout route);   // LeanLoop | StreamLoop
     int stream_ext() const { return lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0); }   // the stream kernel's EXT of this solver
-    int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout (-1: none has run)
+    int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout enqueued (-1: none has run)
     double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B | f] column-major fp64 (f: the affine term, follows set_fdyn); [B][nx] plant state
     double *d_plant_het = nullptr;                // a per-instance-family solver: [batch][A_b | B_b] column-major fp64 (het_A, het_B)
     bool plant_dirty = true;                      // d_plant is to be (re)written before the next chain
     bool x0d_live = false;                        // d_x0d holds the plant state a stream / generic closed loop left (plant_start)
-    void plant_start(hipStream_t stream);         // the plant state a stream / generic closed loop starts from
+    int plant_start(hipStream_t stream, bool resume);   // x0d <- x0, or (resume, x0d_live) the state the last loop left where x0 still is its rounding
     int ensure_plant();
-    int check_ref_sequence(int mpc_steps) const;
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};
     int *d_count = nullptr;

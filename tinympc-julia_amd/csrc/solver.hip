@@ -505,7 +505,7 @@ int Solver::select_kernel(bool rollout) {
         return -1;
     }
     if (precision == 2) {   // fp64 end to end: the stream kernel's fp64-state form (route_stream_f64), else the generic kernel's, whatever the shape
-        if (hetero || (rollout && !sw.stream_mpc)) {   // (TINYMPC_HIP_STREAM_MPC: the closed loop as a chain of these launches, solve_async)
+        if (hetero || (rollout && !sw.stream_mpc)) {   // (TINYMPC_HIP_STREAM_MPC: the closed loop as a chain of these launches, plan_rollout)
             set_error(hetero ? "precision 2 is not available on a per-instance-family solver" : "precision 2 has no fused closed loop (step it from the host)");
             return -1;
         }
@@ -516,7 +516,6 @@ int Solver::select_kernel(bool rollout) {
         const StreamEntry *s2 = route_stream_f64();
         if (ke || ce || s2 != se) packs_dirty = true;
         ke = nullptr, se = s2, ce = nullptr;
-        rollout_quad = false;
         kernel_name = se ? se->name_f64 : "generic<f64>";
         routed_key = std::move(key);
         routed = true;
@@ -535,7 +534,6 @@ int Solver::select_kernel(bool rollout) {
     const ConeEntry *c2 = route_cone(rollout, k != nullptr, s2 != nullptr), *ct = route_trans(rollout, c2);
     if (ct) c2 = ct;
     if (c2) k = nullptr, s2 = nullptr;
-    rollout_quad = rollout && rollout_on_quad() && !ct;   // else: rollout_steps() on the matrix-core kernel / mfmat's fused loop
     if (k != ke || s2 != se || c2 != ce) packs_dirty = true;
     ke = k, se = s2, ce = c2;
     kernel_name = ke ? ke->name : (se ? se->name : (ce ? ce->name : "generic"));
@@ -1064,72 +1062,87 @@ __global__ void residual_max_kernel(const float *res, long batch, uint32_t *gsta
     }
 }
 
-// A closed loop with per-step shared references (set_ref_sequence): what no route offers, each named
-int Solver::check_ref_sequence(int mpc_steps) const {
-    if (mpc_steps <= 0 || ref_seq_steps <= 0) return 0;
-    if (ref_seq_steps < mpc_steps) {
-        set_error("mpc_rollout: the reference sequence holds " + std::to_string(ref_seq_steps) + " steps, the loop asks for " +
-                  std::to_string(mpc_steps) + " (one reference set per step)");
-        return -1;
+// mpc_rollout: WHICH of its routes a closed loop takes — the one place that decides it, before anything is launched.
+// Refusals first, each named once: what a reference sequence (set_ref_sequence: per-step shared references) does not go
+// with; select_kernel's own; a selection without a closed loop — the stream / generic kernels have none unless
+// TINYMPC_HIP_STREAM_MPC is set, and none with adaptive rho; a solver without the persistent workspace.  Then, in order of
+// preference:
+//   the matrix-core kernel of the box-only shapes (mfma): the chain — per step one workspace-carrying launch and the plant
+//     step, stream-ordered, the plant state in fp64 on the device between them;
+//   TINYMPC_HIP_LEAN_WS, where lean_plan takes a warm whole-batch launch (the calling pattern, whatever the iteration count):
+//     that chain on the lean kernel; with TINYMPC_HIP_LEAN_LOOP beside it ONE launch of the lean kernel's in-kernel loop
+//     (admm_lean.hip.h, MPC) — not with a reference sequence (the kernel stages the shared references once per launch), and
+//     only where the loop kernel of the calling pattern exists: the entry has it, or its specialisation compiled;
+//   the stream / generic kernels under their switch: that chain too — every precision, the affine term (in the plant as
+//     well), cones, linear rows, per-instance references and families; with TINYMPC_HIP_STREAM_LOOP beside it ONE launch of
+//     the stream kernel's in-kernel loop where one is built (admm_streamg.hip.h, MPC; not the generic kernel, precision 1, a
+//     shape or form without a loop kernel);
+//   else the loop fused into the selected kernel: the lanes-per-instance kernels, mfmat.
+// A loop that runs inside one launch takes a reference sequence only as one shared reference set per step.
+Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
+    RolloutPlan rp;
+    auto refuse = [&rp](const std::string &why) {
+        set_error(why);
+        return rp;
+    };
+    if (ref_seq_steps > 0) {
+        if (ref_seq_steps < mpc_steps)
+            return refuse("mpc_rollout: the reference sequence holds " + std::to_string(ref_seq_steps) + " steps, the loop asks for " +
+                          std::to_string(mpc_steps) + " (one reference set per step)");
+        if (refs_per_instance())
+            return refuse("mpc_rollout: a reference sequence is shared by the batch and cannot be combined with per-instance references "
+                          "(set_ref_sequence with steps = 0 drops the sequence)");
+        if (st.adaptive_rho) return refuse("mpc_rollout: a reference sequence is not available with adaptive rho");
+        if (precision == 2 && !sw.stream_mpc)
+            return refuse("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
     }
-    if (refs_per_instance()) {
-        set_error("mpc_rollout: a reference sequence is shared by the batch and cannot be combined with per-instance references "
-                  "(set_ref_sequence with steps = 0 drops the sequence)");
-        return -1;
+    if (select_kernel(true) || ensure_extension_buffers()) return rp;
+    const bool fused = ke || (ce && ce->ws);
+    const bool stream = sw.stream_mpc && !ke && !ce && !st.adaptive_rho;   // the stream or the generic kernel, under its switch
+    if (!fused && !stream) return refuse("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
+    if (!warm_start) return refuse("mpc_rollout needs the persistent workspace (set_warm_start(1))");
+    if ((packs_dirty && upload_packs()) || upload_refs()) return rp;   // (the lean entry and its pack are found there; the reference mode here)
+    Pass step = whole_batch(false, true), loop = whole_batch(false, true, mpc_steps);
+    step.iters = 1;
+    Rollout route = Rollout::Fused;
+    if (ke && ke->G == 16) {
+        route = Rollout::Chain;
+    } else if (sw.lean_ws && plan_lean(step).take) {
+        loop.loop = true;
+        route = (sw.lean_loop && ref_seq_steps == 0 && pick_kernel(loop).lean) ? Rollout::LeanLoop : Rollout::Chain;
+    } else if (stream) {
+        loop.stream_loop = true;
+        route = (sw.stream_loop && pick_kernel(loop).stream_loop) ? Rollout::StreamLoop : Rollout::Chain;
     }
-    if (st.adaptive_rho) {
-        set_error("mpc_rollout: a reference sequence is not available with adaptive rho");
-        return -1;
-    }
-    if (precision == 2 && !sw.stream_mpc) {
-        set_error("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
-        return -1;
-    }
-    return 0;
+    if (route != Rollout::Chain && ref_seq_steps > 0 && ref_mode != REF_SHARED)
+        return refuse("mpc_rollout: per-step references need one shared reference set per step");
+    rp.route = route, rp.stream_plant = stream;
+    return rp;
 }
 
+// A single solve is one launch_pass (or solve_chunked's); a closed loop is planned (plan_rollout), then launched as its route
+// asks.  What a rollout leaves for get_mpc_log and the launch count are set here, once it has been enqueued.
 int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     HIP_TRY(hipSetDevice(device));
     layout_final = true;
-    if (check_ref_sequence(mpc_steps)) return -1;
-    if (select_kernel(mpc_steps > 0) || ensure_extension_buffers()) return -1;
-    const bool chunkable = chunk_iters > 0 && mpc_steps == 0 && !hetero && (ke || se || (ce && ce->ws)) && st.check_termination > 0 &&
-                           st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0 && st.max_iter > chunk_iters;
-    if (chunkable) return solve_chunked(stream);
-    if (mpc_steps > 0 && ke && ke->G == 16) return rollout_steps(stream, mpc_steps);
-    // TINYMPC_HIP_LEAN_WS: the closed loop as the same chain of workspace-carrying launches on the lean kernel (plant state in
-    // fp64 between them) instead of the quad kernel's in-kernel loop; with a reference sequence each launch gets its step's
-    if (mpc_steps > 0 && sw.lean_ws && warm_start) {
-        if ((packs_dirty && upload_packs()) || upload_refs()) return -1;   // (the lean entry and its pack are found there; the reference mode here)
-        Pass step = whole_batch(false, true);
-        step.iters = 1;                                                    // (the calling pattern, whatever the iteration count)
-        if (plan_lean(step).take) {
-            // ... and with TINYMPC_HIP_LEAN_LOOP beside it, the whole loop as ONE launch of the lean kernel's in-kernel loop
-            // (admm_lean.hip.h, MPC).  What keeps the chain, each by name: per-step references (the kernel stages the shared
-            // references once per launch), and a calling pattern without a loop kernel — the entry has none for it, or its
-            // specialisation was refused or failed
-            const bool ref_sequence = ref_seq_steps > 0;
-            if (sw.lean_loop && !ref_sequence) {
-                const int rc = rollout_lean_loop(stream, mpc_steps);
-                if (rc != NO_LOOP_KERNEL) return rc;
-            }
-            return rollout_steps(stream, mpc_steps);
-        }
+    if (mpc_steps <= 0) {
+        if (select_kernel() || ensure_extension_buffers()) return -1;
+        const bool chunkable = chunk_iters > 0 && !hetero && (ke || se || (ce && ce->ws)) && st.check_termination > 0 &&
+                               st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0 && st.max_iter > chunk_iters;
+        return chunkable ? solve_chunked(stream) : launch_pass(stream, whole_batch(!warm_start, warm_start));
     }
-    // TINYMPC_HIP_STREAM_MPC: the stream and generic kernels, which have no fused loop of their own, take the closed loop as
-    // that chain too — every precision, the affine term (in the plant as well), cones, linear rows, per-instance references
-    // and families.  With TINYMPC_HIP_STREAM_LOOP beside it, ONE launch of the stream kernel's in-kernel loop where one is
-    // built (admm_streamg.hip.h, MPC); what keeps the chain: the generic kernel, precision 1, a shape or form without a loop kernel
-    if (mpc_steps > 0 && stream_chain()) {
-        if (sw.stream_loop) {
-            const int rc = rollout_stream_loop(stream, mpc_steps);
-            if (rc != NO_LOOP_KERNEL) return rc;
-        }
-        return rollout_steps(stream, mpc_steps);
+    const RolloutPlan rp = plan_rollout(mpc_steps);
+    if (rp.route == Rollout::Refused || ensure_mpc_log(mpc_steps)) return -1;
+    int rc = -1;
+    switch (rp.route) {
+    case Rollout::Fused: rc = launch_pass(stream, whole_batch(false, true, mpc_steps)); break;
+    case Rollout::Chain: rc = rollout_chain(stream, mpc_steps, rp.stream_plant); break;
+    default: rc = rollout_loop(stream, mpc_steps, rp.route); break;
     }
-    const int rc = launch_pass(stream, whole_batch(!warm_start, warm_start, mpc_steps));
-    if (rc == 0 && mpc_steps > 0) last_rollout_launches = 1;              // (an in-kernel loop: quad, mfmat)
-    return rc;
+    if (rc) return rc;
+    mpc_steps_last = mpc_steps;
+    last_rollout_launches = rp.route == Rollout::Chain ? mpc_steps : 1;
+    return 0;
 }
 
 // Chunks of (a multiple of check_termination) iterations; between chunks the unconverged instances are gathered
@@ -1284,7 +1297,7 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     P.syl = d_syl;
     P.szl = d_szl;
     P.bounds_stride = (ce && ce->bounds_vary(*this)) ? 1 : 0;
-    // per-step references of a loop that runs inside the launch: mfmat's and the quad kernel's (the chain, rollout_steps,
+    // per-step references of a loop that runs inside the launch: mfmat's and the quad kernel's (the chain, rollout_chain,
     // hands every launch its step's slice as P.xref / P.uref instead and arrives here with mpc_steps = 0)
     if (a.mpc_steps > 0 && ref_seq_steps > 0) {
         P.xref_seq = d_xref_seq;
@@ -1319,34 +1332,30 @@ int Solver::record_done(hipStream_t stream, hipEvent_t carried) {
     return 0;
 }
 
-int Solver::launch_pass(hipStream_t stream, const Pass &a) {
-    // ---- prepare ----
-    if (a.mpc_steps > 0) {
-        // (TINYMPC_HIP_STREAM_MPC opens this gate for the stream / generic kernels — adaptive rho excepted — so that a cold
-        // solver hears what it lacks; a warm one never arrives here but for the stream kernel's loop: solve_async)
-        if (!ke && !(ce && ce->ws) && !(sw.stream_mpc && !st.adaptive_rho)) {
-            set_error("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
-            return -1;
-        }
-        if (!warm_start) {
-            set_error("mpc_rollout needs the persistent workspace (set_warm_start(1))");
-            return -1;
-        }
-        if (ensure_mpc_log(a.mpc_steps)) return -1;
-        mpc_steps_last = a.mpc_steps;
+// Which kernel beside the selected family's takes a launch: the lean kernel (same arithmetic as the quad entry's, a third fewer
+// instructions) where lean_plan takes it — the built-in entry, or the one variant of a shape without one, compiled on first
+// use — and, for the stream kernel's in-kernel closed loop, whether that kernel is built for this solver
+Solver::Pick Solver::pick_kernel(const Pass &a) {
+    Pick k;
+    k.plan = plan_lean(a);
+    k.lean = k.plan.take ? le : nullptr;
+    if (k.plan.take && !le) {
+        const int v = k.plan.variant;
+        if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, k.plan.form == LF_SPARSE ? k.plan.sp : 0, verbose), le_var_tried[v] = true;
+        k.lean = le_var[v];
     }
+    k.stream_loop = a.stream_loop && !k.lean && se && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);
+    return k;
+}
+
+int Solver::launch_pass(hipStream_t stream, const Pass &a) {
+    // ---- prepare (a closed loop arrives planned: plan_rollout; what is refused here depends on the kernel that runs) ----
     if (packs_dirty && upload_packs()) return -1;
     if (upload_refs()) return -1;
-    if (a.mpc_steps > 0 && ref_seq_steps > 0) {
-        if (ref_seq_steps < a.mpc_steps || ref_mode != REF_SHARED) {
-            set_error("mpc_rollout: per-step references need one shared reference set per step");
-            return -1;
-        }
-        if (ke && ke->N > QUAD_REF_SEQ_MAX_N) {
-            set_error("mpc_rollout: the lanes-per-instance kernels take a reference sequence at horizons up to " +
-                      std::to_string((int)QUAD_REF_SEQ_MAX_N) + " (this entry: " + ke->name + "); step the loop from the host");
-            return -1;
-        }
+    if (a.mpc_steps > 0 && ref_seq_steps > 0 && ke && ke->N > QUAD_REF_SEQ_MAX_N) {
+        set_error("mpc_rollout: the lanes-per-instance kernels take a reference sequence at horizons up to " +
+                  std::to_string((int)QUAD_REF_SEQ_MAX_N) + " (this entry: " + ke->name + "); step the loop from the host");
+        return -1;
     }
     AdmmParams P;
     fill_params(P, a);
@@ -1366,23 +1375,11 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
     // caller wrote one in): the matrix-core kernel (G == 16) carries g only then
     if (state_bounds_active && a.save) g_maybe_nonzero = true;
     const bool carry_g = state_bounds_active || (ke && ke->G == 16 && g_maybe_nonzero);
-    // ---- plan: the lean kernel (same arithmetic as the quad entry's, a third fewer instructions) where lean_plan takes the
-    // launch — the built-in entry, or the one variant of a shape without one, compiled on first use ----
-    const LeanPlan plan = plan_lean(a);
-    const LeanEntry *lk = plan.take ? le : nullptr;
-    if (plan.take && !le) {
-        const int v = plan.variant;
-        if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, plan.form == LF_SPARSE ? plan.sp : 0, verbose), le_var_tried[v] = true;
-        lk = le_var[v];
-    }
-    const bool lean = lk != nullptr;
-    if (a.loop && !lean) return NO_LOOP_KERNEL;   // the loop kernel of this calling pattern, or nothing: the caller falls back to the chain
-    const bool sloop = a.stream_loop && !lean && se && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);
-    if (a.stream_loop && !sloop) return NO_LOOP_KERNEL;
-    if (a.mpc_steps > 0 && !ke && !(ce && ce->ws) && !sloop) {   // (unreachable: the stream / generic kernels' own launches are single solves)
-        set_error("mpc_rollout: this problem shape / option set has no kernel with a fused closed loop");
-        return -1;
-    }
+    // ---- plan ----
+    const Pick pick = pick_kernel(a);
+    const LeanPlan &plan = pick.plan;
+    const LeanEntry *lk = pick.lean;
+    const bool lean = lk != nullptr, sloop = pick.stream_loop;
     if (lean && !le && (!ke || ke->G != 1)) P.bounds = reinterpret_cast<const float *>(d_lean + lean_layout(nx, nu).total);   // (upload_packs)
     // ---- launch ----
     // A profiled lean launch carries its two timing events in the kernel's own dispatch packet (start and end of the kernel):
@@ -1419,6 +1416,25 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
 __global__ void plant_init_kernel(double *x0d, const float *x0, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x0d[i] = (double)x0[i];
+}
+
+// ... of a stream / generic closed loop behind an earlier one: where x0 still is the fp32 rounding of the fp64 plant state that
+// loop left, the loop goes on from that state — mpc_rollout(a) then mpc_rollout(b) is mpc_rollout(a + b) — and from x0
+// wherever the caller has set another one since (on the host or in the device buffer)
+__global__ void plant_resume_kernel(double *x0d, const float *x0, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (float)x0d[i] != x0[i]) x0d[i] = (double)x0[i];
+}
+
+// the fp64 plant state a closed loop outside the selected kernel starts from.  resume: the stream / generic routes, which go on
+// from the state an earlier loop of theirs left (x0d_live); every other route starts from x0
+int Solver::plant_start(hipStream_t stream, bool resume) {
+    if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
+    const long n0 = (long)batch * nx;
+    (resume && x0d_live ? plant_resume_kernel : plant_init_kernel)<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+    HIP_TRY(hipGetLastError());
+    if (resume) x0d_live = true;
+    return 0;
 }
 
 // One closed-loop step after a solve (cartpole_example_mpc.jl:35-51): u0 = first column of the solution,
@@ -1475,23 +1491,6 @@ __global__ void plant_step_affine_kernel(double *x0d, float *x0, const float *uo
     if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
 }
 
-// ... of a stream / generic closed loop behind an earlier one: where x0 still is the fp32 rounding of the fp64 plant state that
-// loop left, the loop goes on from that state — mpc_rollout(a) then mpc_rollout(b) is mpc_rollout(a + b) — and from x0
-// wherever the caller has set another one since (on the host or in the device buffer)
-__global__ void plant_resume_kernel(double *x0d, const float *x0, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (float)x0d[i] != x0[i]) x0d[i] = (double)x0[i];
-}
-
-void Solver::plant_start(hipStream_t stream) {
-    const long n0 = (long)batch * nx;
-    if (x0d_live)
-        plant_resume_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
-    else
-        plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
-    x0d_live = true;
-}
-
 // the plant on the device: [A | B | f] (f as set_fdyn left it, zero without an affine term), per-instance families' [A_b | B_b]
 int Solver::ensure_plant() {
     const size_t nab = (size_t)nx * nx + (size_t)nx * nu;
@@ -1515,74 +1514,40 @@ int Solver::ensure_plant() {
     return 0;
 }
 
-int Solver::rollout_steps(hipStream_t stream, int mpc_steps) {
-    if (!warm_start) {
-        set_error("mpc_rollout needs the persistent workspace (set_warm_start(1))");
-        return -1;
-    }
-    const size_t Bn = (size_t)batch;
-    if (ensure_mpc_log(mpc_steps)) return -1;
-    if (!d_x0d && dev_alloc(d_x0d, Bn * nx)) return -1;
-    if (ensure_plant()) return -1;
-    const bool affine = !ke;   // the stream / generic kernels' chain: f and per-instance families in the plant
-    const long n0 = (long)Bn * nx;
-    if (affine)
-        plant_start(stream);
-    else
-        plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
+// The chain: per step one workspace-carrying launch and the plant step, stream-ordered.  stream_plant: the stream / generic
+// kernels' chain, whose every solve starts from the fp32 rounding in d_x0 (Pass::x0d null) and whose plant state goes on from
+// an earlier loop's; on the other kernels the launch reads the fp64 state itself.
+int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant) {
+    if (ensure_plant() || plant_start(stream, stream_plant)) return -1;
     // with a reference sequence every launch reads its step's slice of the sequence as its shared references (step 0's are the
     // solver's own, which stay installed: nothing is copied, and the stream is not synchronised between steps)
-    const size_t EX = (size_t)ex(), EU = (size_t)eu();
+    const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
     Pass pass = whole_batch(false, true);
-    pass.x0d = affine ? nullptr : d_x0d;   // (the stream / generic chain: every solve starts from the fp32 rounding in d_x0, whatever kernel takes it)
+    pass.x0d = stream_plant ? nullptr : d_x0d;
     for (int step = 0; step < mpc_steps; ++step) {
         if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
         if (launch_pass(stream, pass)) return -1;
-        if (affine)
-            plant_step_affine_kernel<<<(unsigned)((Bn + 256 / nx - 1) / (256 / nx)), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
-                                                                                   hetero ? d_plant_het : nullptr, d_mpc_x, d_mpc_u,
-                                                                                   d_mpc_iter, nx, nu, N, (long)Bn, mpc_steps, step);
+        if (stream_plant)
+            plant_step_affine_kernel<<<(unsigned)((batch + per_block - 1) / per_block), 256, 0, stream>>>(
+                d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, hetero ? d_plant_het : nullptr, d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N, (long)batch,
+                mpc_steps, step);
         else
-            plant_step_kernel<<<(unsigned)((Bn + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant,
-                                                                            d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,
-                                                                            (long)Bn, mpc_steps, step);
+            plant_step_kernel<<<(unsigned)((batch + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, d_mpc_x, d_mpc_u,
+                                                                               d_mpc_iter, nx, nu, N, (long)batch, mpc_steps, step);
     }
     HIP_TRY(hipGetLastError());
-    mpc_steps_last = mpc_steps;
-    last_rollout_launches = mpc_steps;
     return record_done(stream);
 }
 
-// The closed loop as one launch of the lean kernel's in-kernel loop: log buffers as every fused loop has them (launch_pass),
-// the fp64 plant state set up as rollout_steps does (x0d <- x0) and handed to the launch, which leaves x0 and x0d as the
-// chain leaves them.  NO_LOOP_KERNEL: none for this solver's calling pattern (no solve was launched; the chain takes the loop).
-int Solver::rollout_lean_loop(hipStream_t stream, int mpc_steps) {
-    if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
-    const long n0 = (long)batch * nx;
-    plant_init_kernel<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
-    HIP_TRY(hipGetLastError());
+// The closed loop as ONE launch of the lean or the stream kernel's in-kernel loop (plan_rollout found the kernel): the fp64
+// plant state set up as the chain's and handed to the launch, which leaves x0 and x0d as the chain leaves them.  (The stream
+// kernel reads its plant coefficients from its own pack: the fp64 A, B, f rows, the doubles ensure_plant uploads for the chain.)
+int Solver::rollout_loop(hipStream_t stream, int mpc_steps, Rollout route) {
+    if (plant_start(stream, route == Rollout::StreamLoop)) return -1;
     Pass pass = whole_batch(false, true, mpc_steps);
     pass.x0d = d_x0d;
-    pass.loop = true;
-    const int rc = launch_pass(stream, pass);
-    if (rc == 0) last_rollout_launches = 1;
-    return rc;
-}
-
-// ... and of the stream kernel's (TINYMPC_HIP_STREAM_LOOP): the same set-up; the kernel reads its plant coefficients from its
-// own pack (the fp64 A, B, f rows: the doubles ensure_plant uploads for the chain).
-int Solver::rollout_stream_loop(hipStream_t stream, int mpc_steps) {
-    if (!se || !se->launch_mpc) return NO_LOOP_KERNEL;
-    if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
-    Pass pass = whole_batch(false, true, mpc_steps);
-    pass.x0d = d_x0d;
-    pass.stream_loop = true;
-    if (!se->has_mpc(precision, stream_ext(), hetero)) return NO_LOOP_KERNEL;
-    plant_start(stream);
-    HIP_TRY(hipGetLastError());
-    const int rc = launch_pass(stream, pass);
-    if (rc == 0) last_rollout_launches = 1;
-    return rc;
+    (route == Rollout::StreamLoop ? pass.stream_loop : pass.loop) = true;
+    return launch_pass(stream, pass);
 }
 
 int Solver::solve_status() {
