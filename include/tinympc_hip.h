@@ -78,7 +78,10 @@ int update_settings(double abs_pri_tol, double abs_dua_tol, int max_iter, int ch
                     double adaptive_rho_min, double adaptive_rho_max,
                     int adaptive_rho_enable_clipping, int verbose);
 /* replaces bindings.cpp:378-411.  Bounds are per knot (nx x N, nu x (N-1)), shared by the batch;
- * enables en_state_bound and en_input_bound on success. */
+ * enables en_state_bound and en_input_bound on success.  With batch > 1 the batch dimension may ride on the column counts, as
+ * it does for set_x_ref: x_min / x_max nx x (N*batch) together with u_min / u_max nu x ((N-1)*batch) give every instance its own
+ * bounds at every knot (tinympc_set_instance_bounds with per_knot = 1; a set_gpus solver scatters them to its shards).  All
+ * four arrays must then have the per-instance width: mixed widths are an error. */
 int set_bound_constraints(double *x_min_data, int x_min_rows, int x_min_cols, double *x_max_data,
                           int x_max_rows, int x_max_cols, double *u_min_data, int u_min_rows,
                           int u_min_cols, double *u_max_data, int u_max_rows, int u_max_cols,
@@ -153,6 +156,26 @@ int tinympc_update_settings(tinympc_solver *s, double abs_pri_tol, double abs_du
                             int en_input_bound);
 int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const double *x_max,
                                   const double *u_min, const double *u_max);
+/* Box bounds PER INSTANCE (no counterpart in the reference, whose solver holds one constraint set: a fleet with different
+ * actuator limits, a sweep over limits, corridor bounds that differ per instance).
+ *   per_knot = 0: x_min / x_max nx x batch, u_min / u_max nu x batch, column-major; column b is instance b's bound at every knot;
+ *   per_knot = 1: x_min / x_max [batch][N][nx] (nx x (N*batch), the layout of per-instance x_ref), u_min / u_max [batch][N-1][nu].
+ * +-1e17 or beyond, +-inf included, mean "no bound".  Enables en_state_bound and en_input_bound on success, as
+ * tinympc_set_bound_constraints does; tinympc_update_settings switches either side off and on again without a new upload.
+ * The solver keeps host copies (a later tinympc_set_precision keeps the bounds); re-batching a solver (set_batch_size, set_gpus)
+ * drops them and returns to the shared bounds, as it resets every per-instance input.  tinympc_set_bound_constraints
+ * afterwards drops them too: back to the shared set and to the kernels that serve it.
+ * Such a solver runs on the `ib` forms of the run-time-shape kernels, whatever on-chip kernel its shape has (their packs hold
+ * one bound image): the stream kernel's for (nx, nu) in {(4,1), (6,3), (12,4)} at precision 0 — any horizon, one family or one
+ * per instance, the affine term, cones, linear rows, chunked solves — and the generic kernel's for every other shape and for
+ * precision 1 and 2; tinympc_kernel_name reports "stream4<NX,NU;ib>", "generic<ib>" or "generic<f64;ib>".  A per-instance-family
+ * solver needs the stream form.  Refused, tinympc_last_error naming the condition: adaptive rho beside per-instance bounds (in
+ * either order); tinympc_mpc_rollout, unless TINYMPC_HIP_STREAM_MPC=1 gives the solver the chain of launches (there is no
+ * in-kernel loop with per-instance bounds).  Per-instance cones and linear rows do not exist. */
+int tinympc_set_instance_bounds(tinympc_solver *s, const double *x_min, const double *x_max, const double *u_min,
+                                const double *u_max, int per_knot);
+/* 0: shared bounds, 1: per instance and constant over the horizon, 2: per instance and per knot */
+int tinympc_bounds_mode(tinympc_solver *s);
 int tinympc_set_cache_terms(tinympc_solver *s, const double *Kinf, const double *Pinf,
                             const double *Quu_inv, const double *AmBKt);
 /* Unpinned extensions (see setup_solver / set_cone_constraints above). */
@@ -306,14 +329,15 @@ int tinympc_set_strict_precision(tinympc_solver *s, int strict);
 int tinympc_reload_switches(tinympc_solver *s);
 int tinympc_effective_precision(tinympc_solver *s);
 /* Name of the kernel family the solver's shape / options select: "quad<nx,nu,N,gG>", "mfma<...>", "mfmat<...>",
- * "stream4<nx,nu>", "generic", ... */
+ * "stream4<nx,nu>", "generic", ...; with per-instance bounds "stream4<nx,nu;ib>", "generic<ib>", "generic<f64;ib>" */
 const char *tinympc_kernel_name(tinympc_solver *s);
 /* Name of the kernel the most recent launch actually ran: the family above, or the variant a launch of that family took
  * for its calling pattern — "lean<nx,nu,N>" for one-shot solves (cold start, workspace not kept) of a one-lane-per-instance
  * quad entry without an active state bound, zero references, fp64 recurrences (admm_lean.hip.h). */
 const char *tinympc_last_launch_name(tinympc_solver *s);
 /* Algorithmic HBM bytes and FLOPs of one solve of the whole batch (SURVEY.md 8d formulas);
- * flops assume `iters` ADMM iterations per instance. */
+ * flops assume `iters` ADMM iterations per instance.  Per-instance bounds count too: given per knot, 2 (nx N + nu (N-1)) floats
+ * per instance and iteration (max_iter of them); constant over the horizon, 2 (nx + nu) floats per instance, once. */
 double tinympc_algorithmic_bytes(tinympc_solver *s);
 double tinympc_algorithmic_flops(tinympc_solver *s, int iters);
 const char *tinympc_last_error(void);
@@ -371,6 +395,10 @@ int tinympc_sharded_set_warm_start(tinympc_sharded *s, int warm_start);
 int tinympc_sharded_reset(tinympc_sharded *s);
 int tinympc_sharded_set_precision(tinympc_sharded *s, int precision);
 int tinympc_sharded_set_compaction(tinympc_sharded *s, int chunk_iters);
+/* per-instance bounds over the WHOLE batch (arguments as tinympc_set_instance_bounds): both layouts are contiguous per
+ * instance, shard i gets the slice [lo_i, hi_i) */
+int tinympc_sharded_set_instance_bounds(tinympc_sharded *s, const double *x_min, const double *x_max, const double *u_min,
+                                        const double *u_max, int per_knot);
 /* per-instance inputs over the WHOLE batch (cols as tinympc_set_x0 / _x_ref / _u_ref), scattered to the shards */
 int tinympc_sharded_set_x0(tinympc_sharded *s, const double *x0, int cols);
 int tinympc_sharded_set_x_ref(tinympc_sharded *s, const double *x_ref, int cols);

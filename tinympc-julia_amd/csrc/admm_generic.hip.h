@@ -65,7 +65,9 @@ __device__ __forceinline__ double gmax(double a, double b) { return fmax(a, b); 
 __device__ __forceinline__ float gsqrt(float a) { return sqrtf(a); }
 __device__ __forceinline__ double gsqrt(double a) { return sqrt(a); }
 
-template <class RT, class ST = float>
+// IB: box bounds per instance (tinympc_set_instance_bounds) — read from P.ibx / P.ibu ([min | max][knot][instance][row], the
+// knot stride 0 where they are constant over the horizon) at this instance's column instead of the shared pack; fixed rho.
+template <class RT, class ST = float, bool IB = false>
 __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
     constexpr bool WIDE = sizeof(ST) == 8;
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,6 +104,23 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
        *const Psv = WSP(P.sv, w64.sv), *const Psgc = WSP(P.sgc, w64.sgc), *const Psvc = WSP(P.svc, w64.svc),
        *const Psyc = WSP(P.syc, w64.syc), *const Pszc = WSP(P.szc, w64.szc), *const Psgl = WSP(P.sgl, w64.sgl),
        *const Psvl = WSP(P.svl, w64.svl), *const Psyl = WSP(P.syl, w64.syl), *const Pszl = WSP(P.szl, w64.szl);
+    // the bounds of element e = (knot k, row): the shared pack's, or (IB) this instance's own; a side switched off is unbounded
+    auto blo_u = [&](int e, int k, int a) -> ST {
+        if constexpr (IB) return (P.ib_on & IB_INPUT) ? (ST)P.ibu[(long)k * P.ib_ku + b * nu + a] : (ST)-__builtin_inff();
+        else return (ST)umin[e];
+    };
+    auto bhi_u = [&](int e, int k, int a) -> ST {
+        if constexpr (IB) return (P.ib_on & IB_INPUT) ? (ST)P.ibu[P.ib_hu + (long)k * P.ib_ku + b * nu + a] : (ST)__builtin_inff();
+        else return (ST)umax[e];
+    };
+    auto blo_x = [&](int e, int k, int r) -> ST {
+        if constexpr (IB) return (P.ib_on & IB_STATE) ? (ST)P.ibx[(long)k * P.ib_kx + b * nx + r] : (ST)-__builtin_inff();
+        else return (ST)xmin[e];
+    };
+    auto bhi_x = [&](int e, int k, int r) -> ST {
+        if constexpr (IB) return (P.ib_on & IB_STATE) ? (ST)P.ibx[P.ib_hx + (long)k * P.ib_kx + b * nx + r] : (ST)__builtin_inff();
+        else return (ST)xmax[e];
+    };
 #define AT(arr, e) arr[(long)(e)*B]
     // adaptive rho: this instance's own rho, Kinf (nu x nx), Pinf (nx x nx) instead of the family's
     const bool adaptive = P.adaptive_rho != 0;
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
             const int k = e / nu, a = e % nu;
             const ST u = AT(su, e);
             ST zn = u + AT(sy, e);
-            zn = gmin((ST)umax[e], gmax((ST)umin[e], zn));
+            zn = gmin(bhi_u(e, k, a), gmax(blo_u(e, k, a), zn));
             const ST yy = (AT(sy, e) + u) - zn;
             AT(sy, e) = yy;
             AT(szn, e) = zn;
@@ -251,7 +270,7 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
             const int k = e / nx, r = e % nx;
             const ST x = AT(sx, e);
             ST vn = x + AT(sg, e);
-            vn = gmin((ST)xmax[e], gmax((ST)xmin[e], vn));
+            vn = gmin(bhi_x(e, k, r), gmax(blo_x(e, k, r), vn));
             const ST gg = (AT(sg, e) + x) - vn;
             AT(sg, e) = gg;
             AT(svn, e) = vn;

@@ -105,7 +105,16 @@ struct AdmmParams {
     // ---- lean kernel, one-shot forms: the status fold's records (fold_status_records) ----
     uint32_t *gslot;  // [gslot_cap][GSLOT_WORDS] one status record per workgroup; never zeroed.  NULL: none
     int gslot_cap;    // workgroups with blockIdx.x below it write a record, the others accumulate in gacc
+    // ---- stream / generic kernels, `ib` forms: box bounds PER INSTANCE (tinympc_set_instance_bounds), fp32, in the scratch
+    // block's layout [min | max][knot][instance][real row], indexed by the INSTANCE (P.idx[slot] under compaction), never by
+    // the launch's dense slot.  The knot strides are batch * nx / batch * nu elements of the solver's whole batch for bounds
+    // given per knot and 0 for bounds constant over the horizon (one line per instance, re-read at every knot); the max
+    // half starts ib_hx / ib_hu elements behind the min half.  NULL: the bounds are the shared pack's ----
+    const float *ibx, *ibu;
+    long ib_kx, ib_ku, ib_hx, ib_hu;
+    int ib_on;        // IB_STATE | IB_INPUT: the sides the settings leave switched on (the other clamps against -+inf, unread)
 };
+enum : int { IB_STATE = 1, IB_INPUT = 2 };
 enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4 };
 
 // Coefficient pack of the lean kernel (admm_lean.hip.h), fp64, all wave-uniform; filled by build_lean_pack (kernels.hip).

@@ -19,9 +19,10 @@
 //     quad kernel); one family per instance (HET): the same rows as per-lane columns in HBM;
 //   * second-order cones may straddle lanes: squared head norms and the axis value are summed over
 //     the group with DPP steps.
-#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself once, at its end, for the loop form's entry point)
+#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself twice, at its end, for the loop form's and the per-instance-bounds form's entry points)
 #define TMPC_ADMM_STREAMG_HIP_H
 #define TMPC_STREAMG_MPC 0
+#define TMPC_STREAMG_IB 0
 #include <hip/hip_runtime.h>
 
 #include "admm_generic.hip.h"   // Ws64, the type-generic gmin / gmax / gsqrt / gfma / gupmax
@@ -248,6 +249,11 @@ struct StreamTune {
     // workspace-keeping ones with cones / linear rows compiled in, whose backward buffer carries w and g of every set:
     // (12, 4) spills 18 / 91 registers there, so those forms are held to one wavefront (the unified 512-register file)
     static constexpr int waves64(int ext, bool os) { return (ext > 0 && !os) ? 1 : 2; }
+    // per-instance bounds (IB): four more arrays in every knot buffer.  (4, 1) and (6, 3) hold them at the plain forms' three
+    // wavefronts without a spilled register.  (12, 4), whose plain twins already spill there (0 .. 14 registers box-only, 59 ..
+    // 148 with cones / linear rows compiled in), spills 10 .. 34 and 82 .. 166: more than its twins in every form, so its IB
+    // forms are held to two wavefronts (256 registers), as waves64 holds the fp64-state forms
+    static constexpr int waves_ib(int nx) { return nx >= 12 ? 2 : WAVES; }
     static constexpr int DEPTH = G == 4 ? 1 : (G == 2 ? 2 : 3);
 };
 #ifndef TMPC_STREAM_DEPTH
@@ -255,6 +261,9 @@ struct StreamTune {
 #endif
 #ifndef TMPC_STREAM_WAVES
 #define TMPC_STREAM_WAVES(G) StreamTune<G>::WAVES
+#endif
+#ifndef TMPC_STREAM_WAVES_IB
+#define TMPC_STREAM_WAVES_IB(G, NX) StreamTune<G>::waves_ib(NX)
 #endif
 #ifndef TMPC_STREAM_WAVES64
 #define TMPC_STREAM_WAVES64(G, EXT, OS) StreamTune<G>::waves64(EXT, OS)
@@ -284,22 +293,37 @@ namespace tmpc {
 // lanes' x_j and u_a by quad broadcasts; the next solve starts from (float)x+ with the workspace as the scratch block
 // already holds it (what saving and reloading it would give: the kept arrays stay, the work arrays are zeroed), with the
 // step's slice of P.xref_seq / P.uref_seq as its references.  The last solve leaves through the ordinary epilogue.
-// The kernel below is compiled twice from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1 — as
-// admm_streamg_kernel and as the loop form's admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST>.  The preprocessor decides what
+// The kernel below is compiled three times from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1,
+// then with TMPC_STREAMG_IB = 1 — as admm_streamg_kernel, as the loop form's admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST> and
+// as the per-instance-bounds form's admm_streamg_ib_kernel<NX, NU, G, EXT, HET, OS>.  The preprocessor decides what
 // `if constexpr` cannot wrap (the loop over steps around the iteration loop, the step's reference pointers), so that the plain
-// kernel's text, name and code are what they were before the loop form existed.
-#if !TMPC_STREAMG_MPC
+// kernel's text, name and code are what they were before the other forms existed (a further template parameter, even a
+// defaulted one, renames every stream kernel).
+//
+// IB: box bounds PER INSTANCE (tinympc_set_instance_bounds; fp64 recurrences, fp32 state, fixed rho, four lanes).  A knot's
+// bounds are not read from the LDS image but fetched with the knot's other arrays, D knots ahead, from P.ibx / P.ibu — fp32,
+// [min | max][knot][instance][real row], the scratch block's layout — at knot strides that are 0 for bounds constant over the
+// horizon (one line per instance, re-read from cache at every knot: no further HBM stream).  The clamp is the shared form's
+// expression, so per-instance bounds that all equal a shared set give the plain kernel's results bit for bit.
+#if TMPC_STREAMG_IB
+template <int NX, int NU, int G, int EXT, bool HET, bool OS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES_IB(G, NX)))) void admm_streamg_ib_kernel(const AdmmParams P) {
+    using RT = double;
+    using ST = float;
+    constexpr bool ADP = false, MPC = false, IB = true;
+#elif !TMPC_STREAMG_MPC
 template <int NX, int NU, int G, class RT, int EXT, bool HET, bool OS, bool ADP = false, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, OS) : TMPC_STREAM_WAVES(G)))) void admm_streamg_kernel(const AdmmParams P) {
-    constexpr bool MPC = false;
+    constexpr bool MPC = false, IB = false;
 #else
 template <int NX, int NU, int G, int EXT, bool HET, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, false) : TMPC_STREAM_WAVES(G)))) void admm_streamg_mpc_kernel(const AdmmParams P) {
     using RT = double;
-    constexpr bool OS = false, ADP = false, MPC = true;
+    constexpr bool OS = false, ADP = false, MPC = true, IB = false;
 #endif
+    static_assert(!IB || (!ADP && sizeof(ST) == 4 && sizeof(RT) == 8 && G == 4), "per-instance bounds: fixed rho, fp32 state, fp64 recurrences, four lanes");
     static_assert(!ADP || (!HET && EXT == 0), "adaptive rho: one family, box sets only");
     static_assert(sizeof(ST) == 4 || (sizeof(RT) == 8 && !HET && !ADP), "fp64 state: fp64 recurrences, one family, fixed rho");
     static_assert(!MPC || (!OS && !ADP && G == 4 && sizeof(RT) == 8), "in-kernel closed loop: workspace kept, fixed rho, four lanes, fp64 recurrences");
@@ -464,6 +488,26 @@ __global__ __launch_bounds__(256)
         const int rc = UFULL ? (q < NUL ? q : NUL - 1) * RU : (row < NU ? row : NU - 1);
         luo[m] = (unsigned)((bb * NU + rc) * (long)sizeof(ST));
     }
+    // IB: the bound arrays [min | max][knot][instance][real row] are addressed by the INSTANCE b, not by the dense slot bb of
+    // the scratch columns (the two differ under compaction): a second set of lane offsets.  Inactive lanes and lanes without
+    // a row read a clamped, valid address; the consumer discards the value (bxlo .. buhi below).
+    unsigned lxi[IB ? RX : 1], lui[IB ? RU : 1];
+    if constexpr (IB) {
+        const long bi = active ? b : 0;
+#pragma unroll
+        for (int m = 0; m < RX; ++m) {
+            const int row = q * RX + m;
+            const int rc = XFULL ? (q < NXL ? q : NXL - 1) * RX : (row < NX ? row : NX - 1);
+            lxi[m] = (unsigned)((bi * NX + rc) * (long)sizeof(float));
+        }
+#pragma unroll
+        for (int m = 0; m < RU; ++m) {
+            const int row = q * RU + m;
+            const int rc = UFULL ? (q < NUL ? q : NUL - 1) * RU : (row < NU ? row : NU - 1);
+            lui[m] = (unsigned)((bi * NU + rc) * (long)sizeof(float));
+        }
+    }
+    const bool ibx_on = IB && (P.ib_on & IB_STATE) != 0, ibu_on = IB && (P.ib_on & IB_INPUT) != 0;   // wave-uniform: the side is read
     ST *const Sg = reinterpret_cast<ST *>(P.scratch), *const Sw = Sg + SXN, *const Sv = Sw + SXN;
     ST *const Sy = Sv + SXN, *const Szw = Sy + SUN, *const Sz = Szw + SUN, *const Sd = Sz + SUN;
     ST *const Sgc = Sd + SUN, *const Swc = Sgc + SXN, *const Svc = Swc + SXN;
@@ -508,6 +552,29 @@ __global__ __launch_bounds__(256)
 #pragma unroll
             for (int m = 0; m < RU; ++m)
                 if (OKU(m)) *SUP(arr, k, m) = src[m];
+        }
+    };
+    // IB: one half (h = 0 min, 1 max) of a knot's bounds of this lane's rows
+    auto ldbx = [&](int h, int k, float (&dst)[IB ? RX : 1]) {
+        if constexpr (IB) {
+            const float *base = P.ibx + (h ? P.ib_hx : 0) + (long)k * P.ib_kx;
+            if constexpr (XFULL) {
+                load_rows<RX>(lane_elem(sgpr_ptr(base), lxi[0]), dst);
+            } else {
+#pragma unroll
+                for (int m = 0; m < RX; ++m) dst[m] = *lane_elem(sgpr_ptr(base), lxi[m]);
+            }
+        }
+    };
+    auto ldbu = [&](int h, int k, float (&dst)[IB ? RU : 1]) {
+        if constexpr (IB) {
+            const float *base = P.ibu + (h ? P.ib_hu : 0) + (long)k * P.ib_ku;
+            if constexpr (UFULL) {
+                load_rows<RU>(lane_elem(sgpr_ptr(base), lui[0]), dst);
+            } else {
+#pragma unroll
+                for (int m = 0; m < RU; ++m) dst[m] = *lane_elem(sgpr_ptr(base), lui[m]);
+            }
         }
     };
     auto mkx = [&](ST v, int m) __attribute__((always_inline)) { return OKX(m) ? v : (ST)0; };
@@ -603,6 +670,7 @@ __global__ __launch_bounds__(256)
     // what one knot of the forward / backward sweep reads from the scratch block, D knots ahead of its use
     struct FwdBuf {
         ST g[RX], v[RX], gc[RX], vc[RX], gl[RX], vl[RX], d[RU], y[RU], z[RU], yc[RU], zc[RU], yl[RU], zl[RU];
+        float xlo[IB ? RX : 1], xhi[IB ? RX : 1], ulo[IB ? RU : 1], uhi[IB ? RU : 1];   // IB: the instance's bounds at the knot
     };
     struct BwdBuf {  // OS: the fused arrays in w / zw; else all of them
         ST w[RX], g[RX], wc[RX], gc[RX], wl[RX], gl[RX], zw[RU], y[RU], zwc[RU], yc[RU], zwl[RU], yl[RU];
@@ -648,6 +716,12 @@ __global__ __launch_bounds__(256)
 #pragma unroll
                 for (int m = 0; m < RU; ++m)
                     fb[j].d[m] = fb[j].y[m] = fb[j].z[m] = fb[j].yc[m] = fb[j].zc[m] = fb[j].yl[m] = fb[j].zl[m] = (ST)0;
+                if constexpr (IB) {   // a side the settings switch off is never read: it clamps against -+inf
+#pragma unroll
+                    for (int m = 0; m < RX; ++m) fb[j].xlo[m] = -__builtin_inff(), fb[j].xhi[m] = __builtin_inff();
+#pragma unroll
+                    for (int m = 0; m < RU; ++m) fb[j].ulo[m] = -__builtin_inff(), fb[j].uhi[m] = __builtin_inff();
+                }
             }
             auto fetch_x = [&](int k_, FwdBuf &f) __attribute__((always_inline)) {
                 const int k = knot_sgpr(k_);
@@ -661,6 +735,11 @@ __global__ __launch_bounds__(256)
                     ldx(Sgl, k, f.gl);
                     if (need_res) ldx(Svlold, k, f.vl);
                 }
+                if constexpr (IB)
+                    if (ibx_on) {
+                        ldbx(0, k, f.xlo);
+                        ldbx(1, k, f.xhi);
+                    }
             };
             auto fetch_u = [&](int k_, FwdBuf &f) __attribute__((always_inline)) {
                 const int k = knot_sgpr(k_);
@@ -675,6 +754,11 @@ __global__ __launch_bounds__(256)
                     ldu(Syl, k, f.yl);
                     if (need_res) ldu(Szlold, k, f.zl);
                 }
+                if constexpr (IB)
+                    if (ibu_on) {
+                        ldbu(0, k, f.ulo);
+                        ldbu(1, k, f.uhi);
+                    }
             };
             auto fwd_knot = [&](int k_, FwdBuf &f) __attribute__((always_inline)) {
                 asm volatile("" ::: "memory");  // keep coefficient / bound loads per knot (no hoisting into registers)
@@ -682,11 +766,29 @@ __global__ __launch_bounds__(256)
                 const bool pf = k + D < N;  // this knot's buffer is refilled for knot k + D once consumed
                 const float *bk = lb + k * G * PK::BW;
                 ST xf[RX], vn[RX], gn[RX], wc[RX], gcn[RX], wl[RX], gln[RX], sx[RX];
+                // the knot's bounds of this lane's rows: the shared image's, or (IB) the instance's own as fetched with the
+                // knot's other arrays — a row the lane does not own is unbounded, as the shared image has it
+                auto bxlo = [&](int m) __attribute__((always_inline)) -> ST {
+                    if constexpr (IB) return OKX(m) ? (ST)f.xlo[m] : (ST)-__builtin_inff();
+                    else return (ST)bk[m];
+                };
+                auto bxhi = [&](int m) __attribute__((always_inline)) -> ST {
+                    if constexpr (IB) return OKX(m) ? (ST)f.xhi[m] : (ST)__builtin_inff();
+                    else return (ST)bk[RX + m];
+                };
+                auto bulo = [&](int m) __attribute__((always_inline)) -> ST {
+                    if constexpr (IB) return OKU(m) ? (ST)f.ulo[m] : (ST)-__builtin_inff();
+                    else return (ST)bk[2 * RX + m];
+                };
+                auto buhi = [&](int m) __attribute__((always_inline)) -> ST {
+                    if constexpr (IB) return OKU(m) ? (ST)f.uhi[m] : (ST)__builtin_inff();
+                    else return (ST)bk[2 * RX + RU + m];
+                };
 #pragma unroll
                 for (int m = 0; m < RX; ++m) {
                     const ST g_c = nog ? (ST)0 : mkx(f.g[m], m), v_c = mkx(f.v[m], m);
                     xf[m] = (ST)x[m];
-                    vn[m] = gmin((ST)bk[RX + m], gmax((ST)bk[m], xf[m] + g_c));
+                    vn[m] = gmin(bxhi(m), gmax(bxlo(m), xf[m] + g_c));
                     gn[m] = (g_c + xf[m]) - vn[m];
                     gupmax(pri_x, xf[m] - vn[m]);
                     gupmax(dua_x, v_c - vn[m]);
@@ -807,7 +909,7 @@ __global__ __launch_bounds__(256)
                     for (int m = 0; m < RU; ++m) {
                         const ST y_c = mku(f.y[m], m);
                         uf[m] = (ST)u[m];
-                        zn[m] = gmin((ST)bk[2 * RX + RU + m], gmax((ST)bk[2 * RX + m], uf[m] + y_c));
+                        zn[m] = gmin(buhi(m), gmax(bulo(m), uf[m] + y_c));
                         yn[m] = (y_c + uf[m]) - zn[m];
                         gupmax(pri_u, uf[m] - zn[m]);
                         gupmax(dua_u, mku(f.z[m], m) - zn[m]);
@@ -1275,9 +1377,14 @@ __global__ __launch_bounds__(256)
 }
 
 }  // namespace tmpc
-#if !TMPC_STREAMG_MPC
+#if !TMPC_STREAMG_MPC && !TMPC_STREAMG_IB
 #undef TMPC_STREAMG_MPC
 #define TMPC_STREAMG_MPC 1
+#include "admm_streamg.hip.h"
+#undef TMPC_STREAMG_MPC
+#define TMPC_STREAMG_MPC 0
+#undef TMPC_STREAMG_IB
+#define TMPC_STREAMG_IB 1
 #include "admm_streamg.hip.h"
 #define TMPC_STREAMG_BOTH
 #endif

@@ -182,6 +182,18 @@ int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const 
     return guarded("set_bound_constraints", [&] { return s->s.set_bounds(x_min, x_max, u_min, u_max); });
 }
 
+int tinympc_set_instance_bounds(tinympc_solver *s, const double *x_min, const double *x_max, const double *u_min,
+                                const double *u_max, int per_knot) {
+    if (!s) return -1;
+    if (!x_min || !x_max || !u_min || !u_max) {
+        set_error("set_instance_bounds: null bound array");
+        return -1;
+    }
+    return guarded("set_instance_bounds", [&] { return s->s.set_instance_bounds(x_min, x_max, u_min, u_max, per_knot != 0); });
+}
+
+int tinympc_bounds_mode(tinympc_solver *s) { return s ? s->s.bounds_mode : -1; }
+
 int tinympc_set_fdyn(tinympc_solver *s, const double *fdyn) {
     if (!s) return -1;
     return guarded("set_fdyn", [&] { return s->s.set_fdyn(fdyn); });
@@ -234,6 +246,10 @@ int tinympc_set_adaptive_rho(tinympc_solver *s, int enable, double rho_min, doub
     tmpc::Solver &v = s->s;
     if (enable && v.hetero) {
         set_error("adaptive_rho is not available on a per-instance-family solver");
+        return -1;
+    }
+    if (enable && v.bounds_mode) {
+        set_error("adaptive_rho is not available with per-instance bounds (set_instance_bounds)");
         return -1;
     }
     if (enable && !(rho_min > 0.0 && rho_max >= rho_min)) {
@@ -508,6 +524,10 @@ double tinympc_algorithmic_bytes(tinympc_solver *s) {
     double per = 4.0 * v.nx + 4.0 * (EX + EU) + 24.0;             // x0 in, x/u out, iter/solved/4 res
     if (v.ref_mode == tmpc::REF_PER_INSTANCE) per += 4.0 * (EX + EU);
     if (v.warm_start) per += 2.0 * 4.0 * (3.0 * EU + 2.0 * EX);   // d,y,z,g,v in and out
+    // per-instance bounds: min and max of every state and input row — per knot and iteration where they are given per knot
+    // (the kernels stream them with the knot's other arrays), once where they are constant over the horizon
+    if (v.bounds_mode == 2) per += 4.0 * 2.0 * (EX + EU) * v.st.max_iter;
+    if (v.bounds_mode == 1) per += 4.0 * 2.0 * (v.nx + v.nu);
     return per * v.batch;
 }
 
@@ -767,6 +787,31 @@ int set_bound_constraints(double *x_min_data, int x_min_rows, int x_min_cols, do
     (void)verbose;
     if (need_global("set_bound_constraints")) return -1;
     const tmpc::Solver &v = g_solver->s;
+    // the batch dimension rides on the column counts, as set_x_ref's does: nx x (N*batch) with nu x ((N-1)*batch) is one bound
+    // set per instance and knot ([batch][N][nx] / [batch][N-1][nu] in memory)
+    const int gb = global_batch();
+    const int xc[2] = {x_min_cols, x_max_cols}, uc[2] = {u_min_cols, u_max_cols};
+    int wide = 0;
+    for (int i = 0; i < 2; ++i) wide += (gb > 1 && (long)xc[i] == (long)v.N * gb) + (gb > 1 && (long)uc[i] == (long)(v.N - 1) * gb);
+    if (wide > 0) {
+        if (wide != 4 || x_min_rows != v.nx || x_max_rows != v.nx || u_min_rows != v.nu || u_max_rows != v.nu) {
+            set_error("set_bound_constraints: mixed widths — per-instance bounds need all four arrays per instance (x_min, x_max nx x (N*batch) "
+                      "and u_min, u_max nu x ((N-1)*batch)); shared bounds need nx x N and nu x (N-1)");
+            return -1;
+        }
+        if (!x_min_data || !x_max_data || !u_min_data || !u_max_data) return -1;
+        if (g_sharded) {
+            if (g_solver->s.st.adaptive_rho) {
+                set_error("set_bound_constraints: per-instance bounds are not available with adaptive rho");
+                return -1;
+            }
+            g_solver->s.st.en_state_bound = g_solver->s.st.en_input_bound = 1;   // (the master keeps the family-level state)
+            return guarded("set_bound_constraints", [&] {
+                return tinympc_sharded_set_instance_bounds(g_sharded.get(), x_min_data, x_max_data, u_min_data, u_max_data, 1);
+            });
+        }
+        return tinympc_set_instance_bounds(g_solver.get(), x_min_data, x_max_data, u_min_data, u_max_data, 1);
+    }
     if (!dims_ok("x_min", x_min_rows, x_min_cols, v.nx, v.N) ||
         !dims_ok("x_max", x_max_rows, x_max_cols, v.nx, v.N) ||
         !dims_ok("u_min", u_min_rows, u_min_cols, v.nu, v.N - 1) ||

@@ -343,6 +343,15 @@ const StreamEntry *find_stream_kernel(int nx, int nu) {
 hipError_t launch_generic(const AdmmParams &P, int precision, hipStream_t stream) {
     const int threads = 256;
     const int grid = (P.batch + threads - 1) / threads;
+    if (P.ibx) {   // per-instance bounds: the `ib` forms (fixed rho: the solver refuses adaptive rho beside them)
+        if (precision == 2)
+            hipLaunchKernelGGL((admm_generic_kernel<double, double, true>), dim3(grid), dim3(threads), 0, stream, P);
+        else if (precision == 0)
+            hipLaunchKernelGGL((admm_generic_kernel<double, float, true>), dim3(grid), dim3(threads), 0, stream, P);
+        else
+            hipLaunchKernelGGL((admm_generic_kernel<float, float, true>), dim3(grid), dim3(threads), 0, stream, P);
+        return hipGetLastError();
+    }
     if (precision == 2)
         hipLaunchKernelGGL((admm_generic_kernel<double, double>), dim3(grid), dim3(threads), 0, stream, P);
     else if (precision == 0)

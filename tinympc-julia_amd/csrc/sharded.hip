@@ -239,6 +239,21 @@ int tinympc_sharded_set_x0(tinympc_sharded *s, const double *x0, int cols) {
             return -1;
     return 0;
 }
+// per-instance bounds over the WHOLE batch: both layouts are contiguous per instance, shard i takes the slice [lo_i, hi_i)
+int tinympc_sharded_set_instance_bounds(tinympc_sharded *s, const double *x_min, const double *x_max, const double *u_min,
+                                        const double *u_max, int per_knot) {
+    if (!s) return -1;
+    if (!x_min || !x_max || !u_min || !u_max) {
+        set_error("set_instance_bounds: null bound array");
+        return -1;
+    }
+    const size_t px = (size_t)s->nx * (per_knot ? s->N : 1), pu = (size_t)s->nu * (per_knot ? s->N - 1 : 1);   // elements per instance
+    for (int i = 0; i < s->n(); ++i) {
+        const size_t lo = (size_t)s->lo[i];
+        if (tinympc_set_instance_bounds(s->shard[i], x_min + lo * px, x_max + lo * px, u_min + lo * pu, u_max + lo * pu, per_knot)) return -1;
+    }
+    return 0;
+}
 static int sharded_set_ref(tinympc_sharded *s, bool is_x, const double *ref, int cols) {
     if (!s || !ref) return -1;
     const int kn = is_x ? s->N : s->N - 1, rows = is_x ? s->nx : s->nu;

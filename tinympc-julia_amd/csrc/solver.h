@@ -135,6 +135,10 @@ struct StreamEntry {
     // no loop kernel for that precision / family kind, nothing launched
     hipError_t (*launch_mpc)(const AdmmParams &, int precision, int ext, bool het, hipStream_t) = nullptr;
     bool (*has_mpc)(int precision, int ext, bool het) = nullptr;   // whether launch_mpc has a kernel for the call
+    // the per-instance-bounds form (tinympc_set_instance_bounds; precision 0, one family or one per instance, fixed rho) and
+    // the name it reports, "stream4<NX,NU;ib>" — both null where the form is not built (sinst_ib_*.hip)
+    hipError_t (*launch_ib)(const AdmmParams &, int ext, bool het, hipStream_t) = nullptr;
+    const char *name_ib = nullptr;
 };
 const StreamEntry *find_stream_kernel(int nx, int nu);
 // One (nx, nu) instantiation of the LDS-resident matrix-core kernel with a run-time horizon (admm_mfmac.hip.h):
@@ -199,6 +203,17 @@ struct Solver {
     Settings st;
     // per-knot bounds, column-major fp64 (nx x N, nu x (N-1)); +-1e17 until set
     std::vector<double> x_min, x_max, u_min, u_max;
+    // Box bounds PER INSTANCE (tinympc_set_instance_bounds).  bounds_mode 0: the shared set above; 1: one column per instance,
+    // constant over the horizon (ib_x* nx x batch, ib_u* nu x batch); 2: per instance and knot (ib_x* [batch][N][nx], ib_u*
+    // [batch][N-1][nu]).  The host copies are the caller's fp64 arrays as given (they survive a change of precision or of the
+    // settings); the device arrays hold them transposed to the kernels' layout (AdmmParams::ibx).  Such a solver runs on the
+    // `ib` forms of the stream and generic kernels only: the on-chip families' packs hold one bound image.
+    int bounds_mode = 0;
+    std::vector<double> ib_xmin, ib_xmax, ib_umin, ib_umax;
+    float *d_ibx = nullptr, *d_ibu = nullptr;
+    int set_instance_bounds(const double *xmin, const double *xmax, const double *umin, const double *umax, int per_knot);
+    void drop_instance_bounds();
+    int upload_instance_bounds();
     // affine dynamics term and cone constraints (parity UNPINNED: they exist only in the absent
     // TinyMPC submodule; run on the stream kernel, or the generic one for shapes outside its grid)
     std::vector<double> fdyn;  // nx, all zero by default

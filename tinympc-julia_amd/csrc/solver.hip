@@ -213,6 +213,8 @@ void Solver::free_batch() {
     dev_free(d_ws64);
     ws64_cap = 0;
     dev_free(d_het_aux);
+    dev_free(d_ibx);
+    dev_free(d_ibu);
     dev_free(d_sgc);
     dev_free(d_svc);
     dev_free(d_syc);
@@ -377,7 +379,7 @@ Switches read_switches() {
 // lanes-per-instance family, its adaptive-rho variants included (precision = 1 — fp32 recurrences, asked for to save time —
 // stays here only where no matrix-core kernel exists, or with TINYMPC_HIP_STRICT_FP32: route_mfma)
 const KernelEntry *Solver::route_quad(bool rollout) const {
-    if (sw.no_quad || extensions_active() || hetero) return nullptr;
+    if (sw.no_quad || extensions_active() || hetero || bounds_mode) return nullptr;   // (per-instance bounds: the pack holds one bound image)
     if (!st.adaptive_rho) {
         const KernelEntry *k = sw.group ? find_quad_kernel(nx, nu, N, sw.group) : nullptr;
         if (!k) k = select_quad_kernel(nx, nu, N, batch);
@@ -403,7 +405,7 @@ const KernelEntry *Solver::route_quad(bool rollout) const {
 // on the quad kernel), and the adaptive-rho variant (the instance's own Kinf as a correction to the shared products) where
 // the quad family has none
 const KernelEntry *Solver::route_mfma(bool rollout, const KernelEntry *quad) const {
-    if (strict_fp32() || sw.group || sw.no_mfma || sw.no_quad) return nullptr;
+    if (strict_fp32() || sw.group || sw.no_mfma || sw.no_quad || bounds_mode) return nullptr;
     const KernelEntry *m = find_mfma_kernel(nx, nu, N);
     if (!m || (m->jit && sw.no_jit)) return nullptr;
     if (st.adaptive_rho)
@@ -422,6 +424,9 @@ const StreamEntry *Solver::route_stream() const {
     const StreamEntry *s2 = find_stream_kernel(nx, nu);
     if (s2 && 16.0 * batch * std::max(nx, nu) >= 4.0e9) s2 = nullptr;   // 32-bit lane byte offsets into one knot's rows
     if (s2 && s2->lds_bytes(N, precision) > 150 * 1024) s2 = nullptr;   // LDS image of coefficients + bounds
+    // per-instance bounds: the `ib` form, built for the benchmark shapes with fp64 recurrences (the 32-bit guard above covers
+    // its bound arrays: an instance's rows of one knot lie below 4 batch max(nx, nu) bytes)
+    if (s2 && bounds_mode && (precision != 0 || !s2->launch_ib)) s2 = nullptr;
     return s2;
 }
 
@@ -429,7 +434,7 @@ const StreamEntry *Solver::route_stream() const {
 // affine term, cones, linear rows, cold or kept workspace.  One family, fixed rho, the whole batch in one launch (no
 // chunks): everything else stays on the generic kernel's fp64-state form.
 const StreamEntry *Solver::route_stream_f64() const {
-    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0) return nullptr;
+    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0 || bounds_mode) return nullptr;
     const StreamEntry *s2 = find_stream_kernel(nx, nu);
     if (!s2 || !s2->launch_f64) return nullptr;
     if (32.0 * batch * std::max(nx, nu) >= 4.0e9) return nullptr;   // 32-bit lane byte offsets, 8-byte elements
@@ -442,6 +447,7 @@ const StreamEntry *Solver::route_stream_f64() const {
 // against 5.5 on the quad kernel), else the LDS-resident one (mfmac, any horizon).  Only where a workspace-carrying
 // kernel exists to fall back to (`fallback`).
 const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stream) const {
+    if (bounds_mode) return nullptr;
     const ConeEntry *cn = sw.no_mfmar ? nullptr : find_cone_kernel(nx, nu, N);
     if (cn && cn->supports && !cn->supports(*this)) cn = nullptr;
     const bool plain_ok = sw.mfmac_all || (cn != nullptr && cn->plain);
@@ -459,7 +465,7 @@ const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stre
 // transposed-sets matrix-core kernel: every kind of solve (one-shot, warm-started, workspace kept, chunked, the fused closed
 // loop) of a shape that has it, with the affine term / at most one cone per side (box-only problems where the entry says so)
 const ConeEntry *Solver::route_trans(bool rollout, const ConeEntry *oneshot) const {
-    if (sw.no_mfmat || sw.no_mfma || sw.group) return nullptr;
+    if (sw.no_mfmat || sw.no_mfma || sw.group || bounds_mode) return nullptr;
     if (strict_fp32() || hetero || st.adaptive_rho || (rollout && refs_per_instance() && ref_seq_steps > 0) || st.max_iter < 1 || (double)batch * ex() >= 2.0e9)
         return nullptr;
     const ConeEntry *ct = find_trans_kernel(nx, nu, N);
@@ -494,7 +500,7 @@ std::vector<long> Solver::routing_key(bool rollout) const {
             cache_overridden, refs_device_owned, xref_kind, uref_kind, ref_mode, adapt_pure, adapt_dirty, ref_seq_steps,
             st.max_iter < 1, st.en_state_soc, st.en_input_soc, ncx, ncu, Acx[0], qcx[0], Acu[0], qcu[0], mlx, mlu, rollout, strict_precision,
             (long)route_gen, Acx[1], qcx[1], Acu[1], qcu[1], st.en_state_linear, st.en_input_linear,
-            extensions_active() && bounds_vary_by_knot(), layout_final};   // (a unit specialised at setup is compiled for one bound kind)
+            extensions_active() && bounds_vary_by_knot(), layout_final, bounds_mode};   // (a unit specialised at setup is compiled for one bound kind)
 }
 
 int Solver::select_kernel(bool rollout) {
@@ -502,6 +508,10 @@ int Solver::select_kernel(bool rollout) {
     if (routed && key == routed_key) return 0;
     if (st.adaptive_rho && hetero) {
         set_error("adaptive_rho is not available on a per-instance-family solver");
+        return -1;
+    }
+    if (st.adaptive_rho && bounds_mode) {
+        set_error("adaptive_rho is not available with per-instance bounds (set_instance_bounds); shared bounds (set_bound_constraints) drop them");
         return -1;
     }
     if (precision == 2) {   // fp64 end to end: the stream kernel's fp64-state form (route_stream_f64), else the generic kernel's, whatever the shape
@@ -516,7 +526,7 @@ int Solver::select_kernel(bool rollout) {
         const StreamEntry *s2 = route_stream_f64();
         if (ke || ce || s2 != se) packs_dirty = true;
         ke = nullptr, se = s2, ce = nullptr;
-        kernel_name = se ? se->name_f64 : "generic<f64>";
+        kernel_name = se ? se->name_f64 : (bounds_mode ? "generic<f64;ib>" : "generic<f64>");
         routed_key = std::move(key);
         routed = true;
         return 0;
@@ -528,7 +538,8 @@ int Solver::select_kernel(bool rollout) {
     }
     const StreamEntry *s2 = k ? nullptr : route_stream();
     if (hetero && !s2) {
-        set_error("per-instance families need a stream-kernel instantiation for (nx, nu) (nx in {2,3,4,6,8,10,12}, nu <= 4)");
+        set_error(bounds_mode ? "per-instance families with per-instance bounds need the stream kernel's ib form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
+                  "per-instance families need a stream-kernel instantiation for (nx, nu) (nx in {2,3,4,6,8,10,12}, nu <= 4)");
         return -1;
     }
     const ConeEntry *c2 = route_cone(rollout, k != nullptr, s2 != nullptr), *ct = route_trans(rollout, c2);
@@ -536,7 +547,7 @@ int Solver::select_kernel(bool rollout) {
     if (c2) k = nullptr, s2 = nullptr;
     if (k != ke || s2 != se || c2 != ce) packs_dirty = true;
     ke = k, se = s2, ce = c2;
-    kernel_name = ke ? ke->name : (se ? se->name : (ce ? ce->name : "generic"));
+    kernel_name = ke ? ke->name : (se ? (bounds_mode ? se->name_ib : se->name) : (ce ? ce->name : (bounds_mode ? "generic<ib>" : "generic")));
     routed_key = std::move(key);
     routed = true;
     return 0;
@@ -553,6 +564,7 @@ int Solver::alloc_batch(int batch_) {
     }
     HIP_TRY(hipSetDevice(device));
     free_batch();
+    drop_instance_bounds();   // (per-instance inputs do not survive a re-batch: back to the shared bounds)
     batch = batch_;
     if (select_kernel()) return -1;
     const size_t Bn = (size_t)batch, EX = (size_t)ex(), EU = (size_t)eu();
@@ -654,12 +666,14 @@ int Solver::get_adaptive_state(double *rho, double *Kinf, double *Pinf) {
 int Solver::upload_packs() {
     if (wait_last_launch()) return -1;   // (a launch still in flight on another stream reads the packs this overwrites)
     state_bounds_active = false;
+    const std::vector<double> &sxmin = bounds_mode ? ib_xmin : x_min, &sxmax = bounds_mode ? ib_xmax : x_max;
     if (st.en_state_bound)
-        for (size_t i = 0; i < x_min.size(); ++i)
-            if (x_min[i] > -1e17 || x_max[i] < 1e17) {
+        for (size_t i = 0; i < sxmin.size(); ++i)
+            if (sxmin[i] > -1e17 || sxmax[i] < 1e17) {
                 state_bounds_active = true;
                 break;
             }
+    if (bounds_mode && upload_instance_bounds()) return -1;
     std::vector<unsigned char> coef;
     std::vector<float> bnd;
     if (ke) {
@@ -686,7 +700,7 @@ int Solver::upload_packs() {
     // precision 2 (the generic kernel's fp64-state form, one lane per instance like this one): one-shot solves of a shape the lean
     // kernel holds run on ITS fp64-state form, specialised on request — the reference's digits at the headline kernel's speed
     // (`se` at precision 2 is the stream kernel's fp64-state form: it takes what the lean kernel leaves)
-    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise) lean_jit = true;
+    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise && !bounds_mode) lean_jit = true;
     std::fill(le_var_tried, le_var_tried + LV_COUNT, false);
     lean_ok = false;
     lean_sp = lean_pattern(A, B);
@@ -823,6 +837,8 @@ int Solver::upload_refs() {
 
 int Solver::set_bounds(const double *xmin, const double *xmax, const double *umin, const double *umax) {
     route_gen += 1;   // (array-valued state the routes read: the routing key only carries scalars)
+    const bool had_instance_bounds = bounds_mode != 0;
+    drop_instance_bounds();   // the shared set replaces a per-instance one
     x_min.assign(xmin, xmin + ex());
     x_max.assign(xmax, xmax + ex());
     u_min.assign(umin, umin + eu());
@@ -830,7 +846,76 @@ int Solver::set_bounds(const double *xmin, const double *xmax, const double *umi
     st.en_state_bound = 1;  // bindings.cpp:400-404
     st.en_input_bound = 1;
     packs_dirty = true;
+    // back from per-instance bounds: the solver returns to the routes of the shared set at once (kernel_name says so)
+    return had_instance_bounds ? (select_kernel() || ensure_extension_buffers()) : 0;
+}
+
+// Per-instance box bounds.  per_knot = 0: x_* nx x batch, u_* nu x batch (column b: instance b's bound at every knot);
+// per_knot = 1: x_* [batch][N][nx], u_* [batch][N-1][nu] (the layout of per-instance references).  Enables both sides, as
+// set_bounds does.  The solver leaves the on-chip families for the stream / generic kernels' `ib` forms (select_kernel).
+int Solver::set_instance_bounds(const double *xmin, const double *xmax, const double *umin, const double *umax, int per_knot) {
+    if (!xmin || !xmax || !umin || !umax) {
+        set_error("set_instance_bounds: null bound array");
+        return -1;
+    }
+    if (st.adaptive_rho) {
+        set_error("set_instance_bounds: per-instance bounds are not available with adaptive rho");
+        return -1;
+    }
+    if (wait_last_launch()) return -1;
+    const int old_mode = bounds_mode;
+    const size_t Bn = (size_t)batch, nxe = per_knot ? (size_t)ex() * Bn : (size_t)nx * Bn, nue = per_knot ? (size_t)eu() * Bn : (size_t)nu * Bn;
+    route_gen += 1;
+    bounds_mode = per_knot ? 2 : 1;
+    ib_xmin.assign(xmin, xmin + nxe);
+    ib_xmax.assign(xmax, xmax + nxe);
+    ib_umin.assign(umin, umin + nue);
+    ib_umax.assign(umax, umax + nue);
+    const int old_sb = st.en_state_bound, old_ib = st.en_input_bound;
+    st.en_state_bound = 1;
+    st.en_input_bound = 1;
+    packs_dirty = true;
+    if (select_kernel() || ensure_extension_buffers()) {   // (no kernel takes the combination: the solver stays as it was)
+        const std::string why = last_error();
+        st.en_state_bound = old_sb, st.en_input_bound = old_ib;
+        if (!old_mode) drop_instance_bounds();
+        (void)select_kernel();
+        set_error(why);
+        return -1;
+    }
     return 0;
+}
+
+void Solver::drop_instance_bounds() {
+    if (!bounds_mode) return;
+    (void)wait_last_launch();
+    bounds_mode = 0;
+    ib_xmin.clear(), ib_xmax.clear(), ib_umin.clear(), ib_umax.clear();
+    dev_free(d_ibx);
+    dev_free(d_ibu);
+    route_gen += 1;
+    packs_dirty = true;
+}
+
+// the host copies, narrowed to fp32 and transposed from the API's instance-major layout to [min | max][knot][instance][row]
+int Solver::upload_instance_bounds() {
+    HIP_TRY(hipSetDevice(device));
+    const size_t Bn = (size_t)batch, kx = bounds_mode == 2 ? (size_t)N : 1, ku = bounds_mode == 2 ? (size_t)(N - 1) : 1;
+    auto pack = [&](const std::vector<double> &lo, const std::vector<double> &hi, size_t rows, size_t knots, float *&dptr) -> int {
+        const size_t half = knots * Bn * rows;
+        std::vector<float> h(2 * half);
+        for (size_t b = 0; b < Bn; ++b)
+            for (size_t k = 0; k < knots; ++k)
+                for (size_t r = 0; r < rows; ++r) {
+                    const size_t src = (b * knots + k) * rows + r, dst = (k * Bn + b) * rows + r;
+                    h[dst] = (float)lo[src];
+                    h[half + dst] = (float)hi[src];
+                }
+        if (dev_alloc(dptr, h.size())) return -1;
+        HIP_TRY(hipMemcpy(dptr, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    };
+    return pack(ib_xmin, ib_xmax, (size_t)nx, kx, d_ibx) || pack(ib_umin, ib_umax, (size_t)nu, ku, d_ibu);
 }
 
 int Solver::set_fdyn(const double *f) {
@@ -1096,6 +1181,8 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
         if (precision == 2 && !sw.stream_mpc)
             return refuse("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
     }
+    if (bounds_mode && !sw.stream_mpc)
+        return refuse("mpc_rollout: per-instance bounds have no closed loop by default (TINYMPC_HIP_STREAM_MPC=1 gives one as a chain of launches; or step it from the host)");
     if (select_kernel(true) || ensure_extension_buffers()) return rp;
     const bool fused = ke || (ce && ce->ws);
     const bool stream = sw.stream_mpc && !ke && !ce && !st.adaptive_rho;   // the stream or the generic kernel, under its switch
@@ -1307,6 +1394,12 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     P.ws64 = d_ws64;
     P.abs_pri_tol64 = st.abs_pri_tol;
     P.abs_dua_tol64 = st.abs_dua_tol;
+    if (bounds_mode) {
+        P.ibx = d_ibx, P.ibu = d_ibu;
+        P.ib_kx = bounds_mode == 2 ? (long)batch * nx : 0, P.ib_ku = bounds_mode == 2 ? (long)batch * nu : 0;
+        P.ib_hx = (long)batch * nx * (bounds_mode == 2 ? N : 1), P.ib_hu = (long)batch * nu * (bounds_mode == 2 ? N - 1 : 1);
+        P.ib_on = (st.en_state_bound ? IB_STATE : 0) | (st.en_input_bound ? IB_INPUT : 0);
+    }
     P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0);
 }
 
@@ -1344,7 +1437,7 @@ Solver::Pick Solver::pick_kernel(const Pass &a) {
         if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, k.plan.form == LF_SPARSE ? k.plan.sp : 0, verbose), le_var_tried[v] = true;
         k.lean = le_var[v];
     }
-    k.stream_loop = a.stream_loop && !k.lean && se && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);
+    k.stream_loop = a.stream_loop && !k.lean && se && !bounds_mode && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);   // (no `ib` loop form)
     return k;
 }
 
@@ -1395,7 +1488,8 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
                    : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
                          : (se ? (sloop ? se->launch_mpc(P, precision, stream_ext(), hetero, stream)
                                         : (precision == 2 ? se->launch_f64(P, stream_ext(), stream)
-                                                          : se->launch(P, precision, stream_ext(), hetero, stream)))
+                                                          : (bounds_mode ? se->launch_ib(P, stream_ext(), hetero, stream)
+                                                                         : se->launch(P, precision, stream_ext(), hetero, stream))))
                                : launch_generic(P, precision, stream))));
     // ---- record ----
     if (profiling) {

@@ -254,6 +254,43 @@ hipError_t launch_streamg_mpc(const AdmmParams &P, int precision, int ext, bool 
     return hipGetLastError();
 }
 
+// The per-instance-bounds form (admm_streamg_ib_kernel: bounds fetched per instance and knot from P.ibx / P.ibu instead of the LDS image): fp64
+// recurrences, fp32 state, fixed rho; EXT in {0, 2} — an ext == 1 solve runs the EXT = 2 form, where cones and linear rows are
+// run-time flags already — x one family or one per instance x OS: eight kernels per (nx, nu).
+template <int NX, int NU, int G>
+hipError_t launch_streamg_ib(const AdmmParams &P, int ext, bool het, hipStream_t stream) {
+    const int grid = (P.batch + 256 / G - 1) / (256 / G);
+    const size_t lds = streamg_lds_bytes<NX, NU, G>(P.N, 0);
+    const bool oneshot = P.cold_start && !P.save_state;
+#define TMPC_LAUNCH(EXT_, HET_, OS_)                                                                                    \
+    do {                                                                                                                \
+        if (lds > 48 * 1024)                                                                                            \
+            (void)hipFuncSetAttribute((const void *)admm_streamg_ib_kernel<NX, NU, G, EXT_, HET_, OS_>, \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
+        hipLaunchKernelGGL((admm_streamg_ib_kernel<NX, NU, G, EXT_, HET_, OS_>), dim3(grid), dim3(256), \
+                           lds, stream, P);                                                                             \
+    } while (0)
+#define TMPC_LAUNCH_OS(EXT_, HET_)                                                         \
+    do {                                                                                   \
+        if (oneshot) TMPC_LAUNCH(EXT_, HET_, true); else TMPC_LAUNCH(EXT_, HET_, false);   \
+    } while (0)
+#define TMPC_LAUNCH_HET(EXT_)                                                      \
+    do {                                                                           \
+        if (het) TMPC_LAUNCH_OS(EXT_, true); else TMPC_LAUNCH_OS(EXT_, false);     \
+    } while (0)
+    if (ext != 0) TMPC_LAUNCH_HET(2);
+    else TMPC_LAUNCH_HET(0);
+#undef TMPC_LAUNCH_HET
+#undef TMPC_LAUNCH_OS
+#undef TMPC_LAUNCH
+    return hipGetLastError();
+}
+
+// the per-instance-bounds launcher of a shape, in a translation unit of its own (sinst_ib_*.hip)
+#define TMPC_DEFINE_STREAMG_IB(NX, NU, GG)                                                                         \
+    hipError_t launch_stream##GG##_ib_##NX##_##NU(const AdmmParams &P, int ext, bool het, hipStream_t stream) {    \
+        return launch_streamg_ib<NX, NU, GG>(P, ext, het, stream);                                                 \
+    }
 // the loop launcher of a shape, in a translation unit of its own (sinst_mpc_*.hip)
 #define TMPC_DEFINE_STREAMG_MPC(NX, NU, GG)                                                                              \
     hipError_t launch_stream##GG##_mpc_##NX##_##NU(const AdmmParams &P, int precision, int ext, bool het, hipStream_t stream) { \
@@ -265,16 +302,18 @@ hipError_t launch_streamg_mpc(const AdmmParams &P, int precision, int ext, bool 
         return launch_streamg_f64<NX, NU, GG>(P, ext, stream);                                                \
     }
 // ... and the entry of a shape that has one: TMPC_DEFINE_STREAMG_ENTRY plus that launcher and its reported name — and, the same
-// three shapes having them, the loop launcher (sinst_mpc_*.hip)
+// three shapes having them, the loop launcher (sinst_mpc_*.hip) and the per-instance-bounds launcher (sinst_ib_*.hip)
 #define TMPC_DEFINE_STREAMG_ENTRY_F64(NX, NU, GG)                                                                   \
     hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &, int, hipStream_t);                          \
     hipError_t launch_stream##GG##_mpc_##NX##_##NU(const AdmmParams &, int, int, bool, hipStream_t);               \
+    hipError_t launch_stream##GG##_ib_##NX##_##NU(const AdmmParams &, int, bool, hipStream_t);                     \
     const StreamEntry *stream##GG##_entry_##NX##_##NU() {                                                          \
         static const StreamEntry e = {NX, NU, GG, "stream" #GG "<" #NX "," #NU ">", &build_streamg_coef<NX, NU, GG>, \
                                       &build_streamg_bounds<NX, NU, GG>, &streamg_lds_bytes<NX, NU, GG>,           \
                                       &streamg_scratch_floats<NX, NU>, &launch_streamg<NX, NU, GG>,                \
                                       &launch_stream##GG##_f64_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";f64>",  \
-                                      &launch_stream##GG##_mpc_##NX##_##NU, &streamg_mpc_has<NX, NU>};             \
+                                      &launch_stream##GG##_mpc_##NX##_##NU, &streamg_mpc_has<NX, NU>,              \
+                                      &launch_stream##GG##_ib_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";ib>"};   \
         return &e;                                                                                                 \
     }
 

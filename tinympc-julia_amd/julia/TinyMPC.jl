@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_instance_bounds,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -284,6 +284,35 @@ function set_bound_constraints(solver::TinyMPCSolver, x_min::Matrix{Float64}, x_
               x_min, size(x_min, 1), size(x_min, 2), x_max, size(x_max, 1), size(x_max, 2),
               u_min, size(u_min, 1), size(u_min, 2), u_max, size(u_max, 1), size(u_max, 2), _flag(verbose)),
         "Failed to set bound constraints")
+end
+
+# bounds PER INSTANCE AND KNOT, (nx, N, batch) / (nu, N-1, batch) with batch > 1: the batch dimension rides on the column
+# counts, as for set_x_ref.  The solver then runs on the `ib` form of the stream or the generic kernel (kernel_name());
+# the shared method above returns it to shared bounds.  Not with adaptive rho; mpc_rollout only under TINYMPC_HIP_STREAM_MPC.
+function set_bound_constraints(solver::TinyMPCSolver, x_min::Array{Float64,3}, x_max::Array{Float64,3},
+                               u_min::Array{Float64,3}, u_max::Array{Float64,3}; verbose::Bool=false)
+    _need(solver)
+    ms = map(_mat, (x_min, x_max, u_min, u_max))
+    _ok(ccall((:set_bound_constraints, _lib_path()), Int32,
+              (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32,
+               Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Int32),
+              ms[1], size(ms[1], 1), size(ms[1], 2), ms[2], size(ms[2], 1), size(ms[2], 2),
+              ms[3], size(ms[3], 1), size(ms[3], 2), ms[4], size(ms[4], 1), size(ms[4], 2), _flag(verbose)),
+        "Failed to set per-instance bound constraints")
+end
+
+# per-instance bounds: (nx, N, batch) / (nu, N-1, batch) as above, or (nx, batch) / (nu, batch) — one column per instance,
+# constant over the horizon (repeated over the knots here: the process-global entry points take the per-knot layout)
+function set_instance_bounds(solver::TinyMPCSolver, x_min::Array{Float64,3}, x_max::Array{Float64,3},
+                             u_min::Array{Float64,3}, u_max::Array{Float64,3}; verbose::Bool=false)
+    set_bound_constraints(solver, x_min, x_max, u_min, u_max; verbose=verbose)
+end
+function set_instance_bounds(solver::TinyMPCSolver, x_min::Matrix{Float64}, x_max::Matrix{Float64},
+                             u_min::Matrix{Float64}, u_max::Matrix{Float64}; verbose::Bool=false)
+    _need(solver)
+    over(a, knots) = repeat(reshape(a, size(a, 1), 1, size(a, 2)), 1, knots, 1)
+    set_bound_constraints(solver, over(x_min, solver.N), over(x_max, solver.N), over(u_min, solver.N - 1),
+                          over(u_max, solver.N - 1); verbose=verbose)
 end
 
 # Linear inequalities Alin_x x <= blin_x, Alin_u u <= blin_u at every knot (at most 8 rows per side); equalities as

@@ -75,6 +75,8 @@ SIGNATURES = {
     "tinympc_destroy": (None, [c_vp]),
     "tinympc_update_settings": (c_int, [c_vp, c_dbl, c_dbl, c_int, c_int, c_int, c_int]),
     "tinympc_set_bound_constraints": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "tinympc_set_instance_bounds": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_int]),
+    "tinympc_bounds_mode": (c_int, [c_vp]),
     "tinympc_set_cache_terms": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "tinympc_get_cache_terms": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "tinympc_set_fdyn": (c_int, [c_vp, c_dp]),
@@ -143,6 +145,7 @@ SIGNATURES = {
     "tinympc_shard_range": (None, [c_int, c_int, c_int, c_ip, c_ip]),
     "tinympc_sharded_update_settings": (c_int, [c_vp, c_dbl, c_dbl, c_int, c_int, c_int, c_int]),
     "tinympc_sharded_set_bound_constraints": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "tinympc_sharded_set_instance_bounds": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_int]),
     "tinympc_sharded_set_warm_start": (c_int, [c_vp, c_int]),
     "tinympc_sharded_reset": (c_int, [c_vp]),
     "tinympc_sharded_set_precision": (c_int, [c_vp, c_int]),
@@ -417,9 +420,20 @@ def update_settings(solver, *, abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=100,
     return status
 
 
+def _instance_bounds(x_min, x_max, u_min, u_max):
+    """the four arrays of set_instance_bounds in the library's instance-major layout, and whether they are per knot:
+    (nx, B) / (nu, B) constant over the horizon, or (nx, N, B) / (nu, N-1, B)"""
+    arrs = [np.asarray(a, dtype=np.float64) for a in (x_min, x_max, u_min, u_max)]
+    nd = {a.ndim for a in arrs}
+    if nd not in ({2}, {3}):
+        raise TinyMPCError("set_instance_bounds: the four arrays must all be (rows, batch) or all (rows, knots, batch)")
+    return [np.ascontiguousarray(np.asfortranarray(a).reshape(-1, order="F")) for a in arrs], nd == {3}
+
+
 def set_bound_constraints(solver, x_min, x_max, u_min, u_max, *, verbose=False):
-    """TinyMPC.jl:214-227; both bound flags are auto-enabled in the library (bindings.cpp:400-404)."""
-    ms = [_mat(m) for m in (x_min, x_max, u_min, u_max)]
+    """TinyMPC.jl:214-227; both bound flags are auto-enabled in the library (bindings.cpp:400-404).  (nx, N) / (nu, N-1)
+    shared by the batch, or — batch > 1 — (nx, N, batch) / (nu, N-1, batch): every instance its own bounds at every knot."""
+    ms = [_ref3(m) for m in (x_min, x_max, u_min, u_max)]
     args = []
     for m in ms:
         args += [_dp(m), m.shape[0], m.shape[1]]
@@ -623,6 +637,21 @@ class BatchSolver:
     def set_bound_constraints(self, x_min, x_max, u_min, u_max):
         ms = [_mat(m) for m in (x_min, x_max, u_min, u_max)]
         self._chk(self.lib.tinympc_set_bound_constraints(self.h, *[_dp(m) for m in ms]), "set_bound_constraints")
+
+    def set_instance_bounds(self, x_min, x_max, u_min, u_max):
+        """box bounds PER INSTANCE: (nx, B) / (nu, B) constant over the horizon, or (nx, N, B) / (nu, N-1, B) per knot (the layout
+        follows from the number of dimensions).  The solver then runs on the `ib` form of the stream or the generic kernel;
+        set_bound_constraints returns it to shared bounds.  Not with adaptive rho; mpc_rollout only under TINYMPC_HIP_STREAM_MPC."""
+        flat, per_knot = _instance_bounds(x_min, x_max, u_min, u_max)
+        want = [self.nx * (self.N if per_knot else 1), self.nx * (self.N if per_knot else 1),
+                self.nu * (self.N - 1 if per_knot else 1), self.nu * (self.N - 1 if per_knot else 1)]
+        if [f.size for f in flat] != [w * self.batch for w in want]:
+            raise TinyMPCError("set_instance_bounds: expected (nx, batch) / (nu, batch) or (nx, N, batch) / (nu, N-1, batch)")
+        self._chk(self.lib.tinympc_set_instance_bounds(self.h, *[_dp(f) for f in flat], 1 if per_knot else 0), "set_instance_bounds")
+
+    def bounds_mode(self):
+        """0 shared bounds, 1 per instance and constant over the horizon, 2 per instance and per knot"""
+        return int(self.lib.tinympc_bounds_mode(self.h))
 
     def set_cache_terms(self, Kinf, Pinf, Quu_inv, AmBKt):
         ms = [_mat(m) for m in (Kinf, Pinf, Quu_inv, AmBKt)]
@@ -944,6 +973,16 @@ class ShardedBatchSolver:
     def set_bound_constraints(self, x_min, x_max, u_min, u_max):
         ms = [_mat(m) for m in (x_min, x_max, u_min, u_max)]
         self._chk(self.lib.tinympc_sharded_set_bound_constraints(self.h, *[_dp(m) for m in ms]), "set_bound_constraints")
+
+    def set_instance_bounds(self, x_min, x_max, u_min, u_max):
+        """per-instance bounds over the whole batch (shapes as BatchSolver.set_instance_bounds), scattered to the shards"""
+        flat, per_knot = _instance_bounds(x_min, x_max, u_min, u_max)
+        want = [self.nx * (self.N if per_knot else 1), self.nx * (self.N if per_knot else 1),
+                self.nu * (self.N - 1 if per_knot else 1), self.nu * (self.N - 1 if per_knot else 1)]
+        if [f.size for f in flat] != [w * self.batch for w in want]:
+            raise TinyMPCError("set_instance_bounds: expected (nx, batch) / (nu, batch) or (nx, N, batch) / (nu, N-1, batch)")
+        self._chk(self.lib.tinympc_sharded_set_instance_bounds(self.h, *[_dp(f) for f in flat], 1 if per_knot else 0),
+                  "set_instance_bounds")
 
     def set_warm_start(self, on):
         self._chk(self.lib.tinympc_sharded_set_warm_start(self.h, 1 if on else 0), "set_warm_start")
