@@ -132,6 +132,13 @@ int reset_workspace(void);
  * step's solve (0 / 1) or -1; logs (any may be NULL) as tinympc_get_mpc_log. */
 int set_ref_sequence(double *x_ref_seq, int x_rows, int x_cols, double *u_ref_seq, int u_rows, int u_cols, int steps);
 int mpc_rollout(int steps, double *x_log, double *u_log, int *iter_log);
+/* ... against a plant of its own and under an additive disturbance (tinympc_set_plant / tinympc_set_disturbance below, which
+ * describe them).  Shapes are checked: A nx x nx, B nx x nu, f_len nx (f NULL: zero), or with per_instance = 1 A nx x (nx batch),
+ * B nx x (nu batch), f_len nx batch; w nx x steps or nx x (steps batch), the step count taken from w_cols.  A = B = NULL and
+ * w = NULL drop them.  Not on a set_gpus solver, which has no mpc_rollout. */
+int set_plant(double *A_data, int A_rows, int A_cols, double *B_data, int B_rows, int B_cols, double *f_data, int f_len, int per_instance);
+int set_disturbance(double *w_data, int w_rows, int w_cols, int per_instance);
+int plant_mode(void);
 
 /* ------------------------------------------------------------------------- */
 /* (2) handle API                                                            */
@@ -290,6 +297,29 @@ int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter);
  * read their step's slice like the other chains'; a sharded solver takes no sequence. */
 int tinympc_set_ref_sequence(tinympc_solver *s, const double *x_ref_seq, int x_rows, int x_cols, const double *u_ref_seq,
                              int u_rows, int u_cols, int steps);
+/* The plant mpc_rollout steps, when it is not the model: x+ = f_p + A_p x + B_p u0 (+ w).  per_instance = 0: A nx x nx, B nx x nu
+ * (column-major), f nx (NULL = zero).  per_instance = 1: A [batch][nx*nx], B [batch][nx*nu], f [batch][nx] (NULL = zero), the
+ * layout of tinympc_create_families.  A = B = NULL drops it: back to the model and to the routes that serve it.
+ * For Monte-Carlo over disturbances, a fleet whose true parameters differ from the controller's model, robustness sweeps: the
+ * controller (model, caches, kernels) is untouched.  The plant is fp64 on the host and on the device; tinympc_set_precision keeps
+ * it, re-batching (set_batch_size) drops it as it drops every per-instance input.  A solver with a plant or a disturbance
+ * installed takes tinympc_mpc_rollout as a chain — per step its ordinary kept-workspace launch from the fp32 rounding of the
+ * state, then the plant step — on whatever kernel such a solve runs on: every kernel family, every precision, no environment
+ * switch, shapes without a fused closed loop included; a reference sequence is read launch by launch (precision 2 too); two
+ * loops in a row continue the fp64 state unless x0 was set in between.  The step, row r, with u0 the fp32 control of knot 0
+ * widened to fp64: acc = f_p[r]; A_p's row by ascending column, then B_p's, one fma each; with a disturbance one fp64 add
+ * acc + w[r] last; the fp64 state is acc, x0 and the log its fp32 rounding.  Refused by tinympc_mpc_rollout, the error naming
+ * the condition: a disturbance with fewer rows than steps, adaptive rho, no persistent workspace (set_warm_start(0)),
+ * per-instance bounds without TINYMPC_HIP_STREAM_MPC, and the reference sequence's own conditions on length and per-instance
+ * references. */
+int tinympc_set_plant(tinympc_solver *s, const double *A, const double *B, const double *f, int per_instance);
+/* Additive disturbance of every step of the next closed loops: per_instance = 0: w nx x steps, shared; 1: w [batch][steps][nx]
+ * (the layout of the x log).  Every mpc_rollout reads it from row 0 (as a reference sequence is read).  w = NULL or steps = 0 drops it.
+ * Without tinympc_set_plant it disturbs the model plant (A, B and the affine term; on a per-instance-family solver every
+ * instance's own A_b, B_b). */
+int tinympc_set_disturbance(tinympc_solver *s, const double *w, int steps, int per_instance);
+/* 0 model, 1 shared plant, 2 per-instance plant;  | 4 shared disturbance, | 8 per-instance disturbance */
+int tinympc_plant_mode(tinympc_solver *s);
 /* Tolerance-terminated solves of big batches: with chunk_iters > 0 (rounded up to a multiple of check_termination)
  * a solve runs in chunks of that many iterations and, between chunks, gathers the instances still iterating into
  * a dense list, so that wavefronts do not idle behind their slowest instance.  Iterates, iteration counts and

@@ -100,6 +100,9 @@ from .tinympc import (  # noqa: E402,F401
     print_problem_data,
     reset_workspace,
     set_ref_sequence,
+    set_plant,
+    set_disturbance,
+    plant_mode,
     mpc_rollout,
     set_batch_size,
     set_bound_constraints,

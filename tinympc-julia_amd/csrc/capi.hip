@@ -356,6 +356,23 @@ int tinympc_set_ref_sequence(tinympc_solver *s, const double *x_ref_seq, int x_r
         return s->s.set_ref_sequence(x_ref_seq, u_ref_seq, steps);
     });
 }
+int tinympc_set_plant(tinympc_solver *s, const double *A, const double *B, const double *f, int per_instance) {
+    if (!s) return -1;
+    if (per_instance != 0 && per_instance != 1) {
+        set_error("set_plant: per_instance is 0 (A nx x nx, B nx x nu, f nx) or 1 (A [batch][nx*nx], B [batch][nx*nu], f [batch][nx])");
+        return -1;
+    }
+    return guarded("set_plant", [&] { return s->s.set_plant(A, B, f, per_instance); });
+}
+int tinympc_set_disturbance(tinympc_solver *s, const double *w, int steps, int per_instance) {
+    if (!s) return -1;
+    if (steps < 0 || (per_instance != 0 && per_instance != 1)) {
+        set_error("set_disturbance: expected steps >= 0 and per_instance 0 (w nx x steps) or 1 (w [batch][steps][nx])");
+        return -1;
+    }
+    return guarded("set_disturbance", [&] { return s->s.set_disturbance(w, steps, per_instance); });
+}
+int tinympc_plant_mode(tinympc_solver *s) { return s ? s->s.plant_mode() : -1; }
 int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter) {
     if (!s) return -1;
     return guarded("get_mpc_log", [&] { return s->s.get_mpc_log(x, u, iter); });
@@ -935,6 +952,49 @@ int set_ref_sequence(double *x_ref_seq, int x_rows, int x_cols, double *u_ref_se
         return -1;
     }
     return tinympc_set_ref_sequence(g_solver.get(), x_ref_seq, x_rows, x_cols, u_ref_seq, u_rows, u_cols, steps);
+}
+// ... against a plant of its own and under a disturbance (tinympc_set_plant / tinympc_set_disturbance), shapes checked here
+int set_plant(double *A_data, int A_rows, int A_cols, double *B_data, int B_rows, int B_cols, double *f_data, int f_len, int per_instance) {
+    if (need_global("set_plant")) return -1;
+    if (g_sharded) {
+        set_error("set_plant: not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    const tmpc::Solver &v = g_solver->s;
+    if (A_data || B_data) {
+        const int n = per_instance ? v.batch : 1;
+        if (!A_data || !B_data || (per_instance != 0 && per_instance != 1) || A_rows != v.nx || A_cols != v.nx * n || B_rows != v.nx ||
+            B_cols != v.nu * n || (f_data && f_len != v.nx * n)) {
+            set_error("set_plant: expected A nx x nx, B nx x nu, f nx (shared), or A nx x (nx batch), B nx x (nu batch), f nx batch (per instance); here nx = " +
+                      std::to_string(v.nx) + ", nu = " + std::to_string(v.nu) + ", batch = " + std::to_string(v.batch));
+            return -1;
+        }
+    }
+    return tinympc_set_plant(g_solver.get(), A_data, B_data, f_data, per_instance);
+}
+int set_disturbance(double *w_data, int w_rows, int w_cols, int per_instance) {
+    if (need_global("set_disturbance")) return -1;
+    if (g_sharded) {
+        set_error("set_disturbance: not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    const tmpc::Solver &v = g_solver->s;
+    if (!w_data || w_cols == 0) return tinympc_set_disturbance(g_solver.get(), nullptr, 0, 0);
+    const int n = per_instance ? v.batch : 1;
+    if ((per_instance != 0 && per_instance != 1) || w_rows != v.nx || w_cols < 0 || w_cols % n != 0) {
+        set_error("set_disturbance: expected w nx x steps (shared) or nx x (steps batch) (per instance); here nx = " + std::to_string(v.nx) +
+                  ", batch = " + std::to_string(v.batch));
+        return -1;
+    }
+    return tinympc_set_disturbance(g_solver.get(), w_data, w_cols / n, per_instance);
+}
+int plant_mode(void) {
+    if (need_global("plant_mode")) return -1;
+    if (g_sharded) {
+        set_error("plant_mode: not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    return tinympc_plant_mode(g_solver.get());
 }
 int mpc_rollout(int steps, double *x_log, double *u_log, int *iter_log) {
     if (need_global("mpc_rollout")) return -1;

@@ -406,7 +406,8 @@ struct Solver {
     //   Fused       the loop inside the selected kernel (the lanes-per-instance kernels, mfmat): one launch_pass
     //   Chain       per step one workspace-carrying launch and the plant step, stream-ordered, the plant state kept in fp64 on
     //               the device between steps (mfma; the lean kernel under TINYMPC_HIP_LEAN_WS; the stream / generic kernels
-    //               under TINYMPC_HIP_STREAM_MPC, stream_plant: f and per-instance families in the plant, the state resumed)
+    //               under TINYMPC_HIP_STREAM_MPC, stream_plant: f and per-instance families in the plant, the state resumed;
+    //               an own-plant solver on whatever kernel a kept-workspace solve of it takes, no switch: rollout_chain_own)
     //   LeanLoop    ONE launch of the lean kernel's in-kernel loop (TINYMPC_HIP_LEAN_LOOP)
     //   StreamLoop  ONE launch of the stream kernel's (TINYMPC_HIP_STREAM_LOOP)
     //   Refused     the reason is the last error
@@ -414,9 +415,11 @@ struct Solver {
     struct RolloutPlan {
         Rollout route = Rollout::Refused;
         bool stream_plant = false;
+        bool own_plant = false;   // the chain on the plain-solve kernel, stepped by plant_step_own_kernel
     };
     RolloutPlan plan_rollout(int mpc_steps);
     int rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant);
+    int rollout_chain_own(hipStream_t stream, int mpc_steps);   // an own-plant solver's
     int rollout_loop(hipStream_t stream, int mpc_steps, Rollout route);   // LeanLoop | StreamLoop
     int stream_ext() const { return lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0); }   // the stream kernel's EXT of this solver
     int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout enqueued (-1: none has run)
@@ -426,6 +429,23 @@ struct Solver {
     bool x0d_live = false;                        // d_x0d holds the plant state a stream / generic closed loop left (plant_start)
     int plant_start(hipStream_t stream, bool resume);   // x0d <- x0, or (resume, x0d_live) the state the last loop left where x0 still is its rounding
     int ensure_plant();
+    // A plant of its own (tinympc_set_plant) and an additive disturbance (tinympc_set_disturbance): what mpc_rollout steps when it
+    // is not the model, x+ = f_p + A_p x + B_p u0 (+ w).  plant_kind / dist_kind 0: none, 1: shared, 2: per instance.  Host copies
+    // are the caller's fp64 arrays as given (own_A [batch][nx*nx] etc. when per instance; dist_w nx x steps or [batch][steps][nx]);
+    // the device copies are fp64 too: d_own_plant [A | B | f] or [batch][A | B | f] — with a disturbance alone the model's (a
+    // family solver: every instance's own A_b, B_b, and fdyn) — and d_dist as given.  Either makes the solver an own-plant
+    // solver, whose closed loop is the chain on the kernel a kept-workspace solve takes (plan_rollout).
+    int plant_kind = 0, dist_kind = 0, dist_steps = 0;
+    std::vector<double> own_A, own_B, own_f, dist_w;
+    double *d_own_plant = nullptr, *d_dist = nullptr;
+    bool own_plant_dirty = true;
+    bool own_plant() const { return plant_kind != 0 || dist_kind != 0; }
+    bool own_plant_per_instance() const { return plant_kind == 2 || (plant_kind == 0 && hetero); }
+    int plant_mode() const { return plant_kind | (dist_kind == 1 ? 4 : (dist_kind == 2 ? 8 : 0)); }
+    int set_plant(const double *A_, const double *B_, const double *f_, int per_instance);
+    int set_disturbance(const double *w, int steps, int per_instance);
+    void drop_own_plant();   // both pieces (a re-batch)
+    int ensure_own_plant();
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};
     int *d_count = nullptr;

@@ -147,6 +147,8 @@ Solver::~Solver() {
     dev_free(d_lean);
     dev_free(d_plant);
     dev_free(d_plant_het);
+    dev_free(d_own_plant);
+    dev_free(d_dist);
     if (h_gstat) (void)hipHostFree(h_gstat);
     h_gstat = nullptr;
     for (hipEvent_t e : ev_ring)
@@ -565,6 +567,7 @@ int Solver::alloc_batch(int batch_) {
     HIP_TRY(hipSetDevice(device));
     free_batch();
     drop_instance_bounds();   // (per-instance inputs do not survive a re-batch: back to the shared bounds)
+    drop_own_plant();         // (... and back to the model plant)
     batch = batch_;
     if (select_kernel()) return -1;
     const size_t Bn = (size_t)batch, EX = (size_t)ex(), EU = (size_t)eu();
@@ -928,6 +931,7 @@ int Solver::set_fdyn(const double *f) {
     has_fdyn = nz;
     packs_dirty = true;
     plant_dirty = true;   // (the chained closed loop's plant carries f)
+    own_plant_dirty = true;   // (... and a disturbed model plant)
     return select_kernel() || ensure_extension_buffers();
 }
 
@@ -1152,6 +1156,8 @@ __global__ void residual_max_kernel(const float *res, long batch, uint32_t *gsta
 // with; select_kernel's own; a selection without a closed loop — the stream / generic kernels have none unless
 // TINYMPC_HIP_STREAM_MPC is set, and none with adaptive rho; a solver without the persistent workspace.  Then, in order of
 // preference:
+//   an own-plant solver (set_plant / set_disturbance): the chain on whatever kernel a plain kept-workspace solve of it takes,
+//     selected as for a plain solve, every family and precision, no switch (rollout_chain_own); not with adaptive rho;
 //   the matrix-core kernel of the box-only shapes (mfma): the chain — per step one workspace-carrying launch and the plant
 //     step, stream-ordered, the plant state in fp64 on the device between them;
 //   TINYMPC_HIP_LEAN_WS, where lean_plan takes a warm whole-batch launch (the calling pattern, whatever the iteration count):
@@ -1178,11 +1184,24 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
             return refuse("mpc_rollout: a reference sequence is shared by the batch and cannot be combined with per-instance references "
                           "(set_ref_sequence with steps = 0 drops the sequence)");
         if (st.adaptive_rho) return refuse("mpc_rollout: a reference sequence is not available with adaptive rho");
-        if (precision == 2 && !sw.stream_mpc)
+        if (precision == 2 && !sw.stream_mpc && !own_plant())
             return refuse("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
     }
     if (bounds_mode && !sw.stream_mpc)
         return refuse("mpc_rollout: per-instance bounds have no closed loop by default (TINYMPC_HIP_STREAM_MPC=1 gives one as a chain of launches; or step it from the host)");
+    if (own_plant()) {
+        // a plant of its own or a disturbance: the chain on the kernel a plain kept-workspace solve takes (its launches ARE plain
+        // solves, every kernel family and precision has them), stepped by plant_step_own_kernel — ahead of the kernels' own routes
+        if (dist_kind && dist_steps < mpc_steps)
+            return refuse("mpc_rollout: the disturbance holds " + std::to_string(dist_steps) + " steps, the loop asks for " + std::to_string(mpc_steps) +
+                          " (one row per step, read from row 0)");
+        if (st.adaptive_rho) return refuse("mpc_rollout: a plant of its own / a disturbance is not available with adaptive rho");
+        if (!warm_start) return refuse("mpc_rollout needs the persistent workspace (set_warm_start(1))");
+        if (select_kernel(false) || ensure_extension_buffers()) return rp;
+        if ((packs_dirty && upload_packs()) || upload_refs()) return rp;
+        rp.route = Rollout::Chain, rp.own_plant = true;
+        return rp;
+    }
     if (select_kernel(true) || ensure_extension_buffers()) return rp;
     const bool fused = ke || (ce && ce->ws);
     const bool stream = sw.stream_mpc && !ke && !ce && !st.adaptive_rho;   // the stream or the generic kernel, under its switch
@@ -1223,7 +1242,7 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     int rc = -1;
     switch (rp.route) {
     case Rollout::Fused: rc = launch_pass(stream, whole_batch(false, true, mpc_steps)); break;
-    case Rollout::Chain: rc = rollout_chain(stream, mpc_steps, rp.stream_plant); break;
+    case Rollout::Chain: rc = rp.own_plant ? rollout_chain_own(stream, mpc_steps) : rollout_chain(stream, mpc_steps, rp.stream_plant); break;
     default: rc = rollout_loop(stream, mpc_steps, rp.route); break;
     }
     if (rc) return rc;
@@ -1628,6 +1647,135 @@ int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant) 
         else
             plant_step_kernel<<<(unsigned)((batch + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, d_mpc_x, d_mpc_u,
                                                                                d_mpc_iter, nx, nu, N, (long)batch, mpc_steps, step);
+    }
+    HIP_TRY(hipGetLastError());
+    return record_done(stream);
+}
+
+// The step of an own-plant solver's chain (tinympc_set_plant / tinympc_set_disturbance): plant_step_affine_kernel's rule with the
+// coefficients of the plant instead of the model's and the disturbance added last — row r: acc = f_p[r], then A_p's row by
+// ascending column, then B_p's, one fma each; with a disturbance one fp64 add acc + w[r]; x0d = acc, x0 = mpc_x = (float)acc.
+// plant: [A | B | f] column-major fp64, instance b's block at plant + b * plant_stride (0: one shared block; an instance's
+// nx (nx + nu + 1) doubles are contiguous and row r of every column is lane r's, so a workgroup reads one contiguous span).
+// w: this step's row of the disturbance, instance b's at w + b * w_stride (0: shared); null: none.
+__global__ void plant_step_own_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved,
+                                      const double *plant, long plant_stride, const double *w, long w_stride, float *mpc_x,
+                                      float *mpc_u, int *mpc_iter, int nx, int nu, int N, long batch, int steps, int step) {
+    const int per_block = (int)blockDim.x / nx, t = (int)threadIdx.x, r = t % nx;
+    const long b = (long)blockIdx.x * per_block + t / nx;
+    const bool on = t < per_block * nx && b < batch;
+    double acc = 0.0;
+    if (on) {
+        const double *A = plant + b * plant_stride, *Bm = A + nx * nx;
+        const float *u0 = uout + b * (long)nu * (N - 1);
+        acc = Bm[nx * nu + r];
+        for (int j = 0; j < nx; ++j) acc = fma(A[r + j * nx], x0d[b * nx + j], acc);
+        for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
+        if (w) acc = acc + w[b * w_stride + r];
+    }
+    __syncthreads();
+    if (!on) return;
+    const long so = b * steps + step;
+    x0d[b * nx + r] = acc;
+    x0[b * nx + r] = (float)acc;
+    mpc_x[so * nx + r] = (float)acc;
+    for (int a = r; a < nu; a += nx) mpc_u[so * nu + a] = uout[b * (long)nu * (N - 1) + a];
+    if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
+}
+
+int Solver::set_plant(const double *A_, const double *B_, const double *f_, int per_instance) {
+    if (!A_ && !B_) {
+        if (plant_kind && wait_last_launch()) return -1;
+        plant_kind = 0;
+        own_A.clear(), own_B.clear(), own_f.clear();
+        own_plant_dirty = true;
+        if (!own_plant()) dev_free(d_own_plant);
+        return 0;
+    }
+    if (!A_ || !B_) {
+        set_error("set_plant: expected both A (nx x nx) and B (nx x nu), or neither to drop the plant");
+        return -1;
+    }
+    const size_t n = per_instance ? (size_t)batch : 1, na = (size_t)nx * nx, nb = (size_t)nx * nu;
+    own_A.assign(A_, A_ + n * na);
+    own_B.assign(B_, B_ + n * nb);
+    if (f_)
+        own_f.assign(f_, f_ + n * nx);
+    else
+        own_f.assign(n * nx, 0.0);
+    plant_kind = per_instance ? 2 : 1;
+    own_plant_dirty = true;
+    return 0;
+}
+
+int Solver::set_disturbance(const double *w, int steps, int per_instance) {
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;   // (a chain still running reads it)
+    if (!w || steps <= 0) {
+        dist_kind = 0, dist_steps = 0;
+        dist_w.clear();
+        dev_free(d_dist);
+        if (!own_plant()) dev_free(d_own_plant), own_plant_dirty = true;
+        return 0;
+    }
+    const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)steps * nx;
+    dist_w.assign(w, w + n);
+    if (dev_alloc(d_dist, n)) return -1;
+    HIP_TRY(hipMemcpy(d_dist, dist_w.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    dist_kind = per_instance ? 2 : 1, dist_steps = steps;
+    return 0;
+}
+
+void Solver::drop_own_plant() {
+    if (!own_plant()) return;
+    (void)wait_last_launch();
+    plant_kind = dist_kind = dist_steps = 0;
+    own_A.clear(), own_B.clear(), own_f.clear(), dist_w.clear();
+    dev_free(d_own_plant);
+    dev_free(d_dist);
+    own_plant_dirty = true;
+}
+
+// the own plant on the device: [A_p | B_p | f_p], shared or per instance; with a disturbance alone the model's — A, B and the
+// affine term, on a per-instance-family solver every instance's own A_b, B_b
+int Solver::ensure_own_plant() {
+    if (d_own_plant && !own_plant_dirty) return 0;
+    if (wait_last_launch()) return -1;
+    const size_t na = (size_t)nx * nx, nb = (size_t)nx * nu, blk = na + nb + nx, n = own_plant_per_instance() ? (size_t)batch : 1;
+    std::vector<double> h(n * blk);
+    for (size_t b = 0; b < n; ++b) {
+        double *o = h.data() + b * blk;
+        if (plant_kind) {
+            std::copy(own_A.begin() + b * na, own_A.begin() + (b + 1) * na, o);
+            std::copy(own_B.begin() + b * nb, own_B.begin() + (b + 1) * nb, o + na);
+            std::copy(own_f.begin() + b * nx, own_f.begin() + (b + 1) * nx, o + na + nb);
+        } else {
+            const double *Am = hetero ? het_A.data() + b * na : A.a.data(), *Bm = hetero ? het_B.data() + b * nb : B.a.data();
+            std::copy(Am, Am + na, o);
+            std::copy(Bm, Bm + nb, o + na);
+            for (int r = 0; r < nx; ++r) o[na + nb + r] = has_fdyn ? fdyn[r] : 0.0;
+        }
+    }
+    if (dev_alloc(d_own_plant, h.size())) return -1;
+    HIP_TRY(hipMemcpy(d_own_plant, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    own_plant_dirty = false;
+    return 0;
+}
+
+// An own-plant solver's chain: per step the solver's ordinary kept-workspace launch — from the fp32 rounding in d_x0, Pass::x0d
+// null, what a host-stepped loop launches — and plant_step_own_kernel, stream-ordered; the fp64 state resumed as the stream chain's
+int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
+    if (ensure_own_plant() || plant_start(stream, true)) return -1;
+    const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
+    const long blk = (long)nx * nx + (long)nx * nu + nx;
+    Pass pass = whole_batch(false, true);
+    for (int step = 0; step < mpc_steps; ++step) {
+        if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
+        if (launch_pass(stream, pass)) return -1;
+        plant_step_own_kernel<<<(unsigned)((batch + per_block - 1) / per_block), 256, 0, stream>>>(
+            d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L,
+            dist_kind ? d_dist + (size_t)step * nx : nullptr, dist_kind == 2 ? (long)dist_steps * nx : 0L, d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,
+            (long)batch, mpc_steps, step);
     }
     HIP_TRY(hipGetLastError());
     return record_done(stream);

@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_instance_bounds,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_instance_bounds,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -250,6 +250,46 @@ function mpc_rollout(solver::TinyMPCSolver, steps::Integer)
     st = ccall((:mpc_rollout, _lib_path()), Int32, (Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), steps, x, u, it)
     st < 0 && error("mpc_rollout failed ($(_last_error()))")
     return (status=st, x=x, u=u, iter=it)
+end
+
+# The plant mpc_rollout steps when it is not the controller's model, x+ = f_p + A_p x + B_p u0 (+ w) in fp64 — Monte-Carlo over
+# disturbances, a fleet whose true parameters differ from the model, robustness sweeps.  A (nx, nx), B (nx, nu), f (nx,) shared by
+# the batch, or A (nx, nx, batch), B (nx, nu, batch), f (nx, batch) one plant per instance; f = nothing is zero;
+# set_plant(solver, nothing, nothing) drops it.  mpc_rollout then runs as a chain of `steps` ordinary kept-workspace launches with the
+# plant step between them, on whatever kernel such a solve takes (every shape and precision, no environment switch).  Not with
+# adaptive rho, not on a sharded solver (set_gpus > 1).  (Written against the C-ABI like the rest of this file, not executed here.)
+function set_plant(solver::TinyMPCSolver, A::Union{Array{Float64},Nothing}, B::Union{Array{Float64},Nothing},
+                   f::Union{Array{Float64},Nothing}=nothing)
+    _need(solver)
+    if A === nothing && B === nothing
+        return _ok(ccall((:set_plant, _lib_path()), Int32,
+                         (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32),
+                         C_NULL, 0, 0, C_NULL, 0, 0, C_NULL, 0, 0), "Failed to drop the plant")
+    end
+    (A === nothing || B === nothing) && error("set_plant: A and B, or nothing and nothing")
+    per = ndims(A) == 3 ? 1 : 0
+    _ok(ccall((:set_plant, _lib_path()), Int32,
+              (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32),
+              A, size(A, 1), div(length(A), size(A, 1)), B, size(B, 1), div(length(B), size(B, 1)),
+              f === nothing ? C_NULL : f, f === nothing ? 0 : length(f), per), "Failed to set the plant")
+end
+
+# Additive disturbance of every step of the next closed loops: w (nx, steps) shared, or (nx, steps, batch) per instance (the layout
+# of mpc_rollout's x); every mpc_rollout reads it from its first column; nothing drops it.  Without set_plant it disturbs the model.
+function set_disturbance(solver::TinyMPCSolver, w::Union{Array{Float64},Nothing})
+    _need(solver)
+    w === nothing && return _ok(ccall((:set_disturbance, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Int32), C_NULL, 0, 0, 0),
+                                "Failed to drop the disturbance")
+    _ok(ccall((:set_disturbance, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Int32),
+              w, size(w, 1), div(length(w), size(w, 1)), ndims(w) == 3 ? 1 : 0), "Failed to set the disturbance")
+end
+
+# 0 model, 1 shared plant, 2 per-instance plant; + 4 shared disturbance, + 8 per-instance disturbance
+function plant_mode(solver::TinyMPCSolver)
+    _need(solver)
+    m = ccall((:plant_mode, _lib_path()), Int32, ())
+    m < 0 && error("plant_mode failed ($(_last_error()))")
+    return Int(m)
 end
 
 function reset_workspace(solver::TinyMPCSolver)

@@ -115,6 +115,12 @@ SIGNATURES = {
     "set_precision": (c_int, [c_int]),
     "unpin_host_buffer": (c_int, [c_vp]),
     "tinympc_set_ref_sequence": (c_int, [c_vp, c_dp, c_int, c_int, c_dp, c_int, c_int, c_int]),
+    "tinympc_set_plant": (c_int, [c_vp, c_dp, c_dp, c_dp, c_int]),
+    "tinympc_set_disturbance": (c_int, [c_vp, c_dp, c_int, c_int]),
+    "tinympc_plant_mode": (c_int, [c_vp]),
+    "set_plant": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_int, c_dp, c_int, c_int]),
+    "set_disturbance": (c_int, [c_dp, c_int, c_int, c_int]),
+    "plant_mode": (c_int, []),
     "tinympc_set_profiling": (c_int, [c_vp, c_int]),
     "tinympc_set_compaction": (c_int, [c_vp, c_int]),
     "tinympc_set_adaptive_rho": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_int]),
@@ -379,8 +385,56 @@ def set_ref_sequence(solver, x_ref_seq, u_ref_seq):
         raise TinyMPCError(f"Failed to set the reference sequence ({_err()})")
 
 
+def _flat_f(a):
+    return np.ascontiguousarray(np.asfortranarray(np.asarray(a, dtype=np.float64)).reshape(-1, order="F"))
+
+
+def set_plant(solver, A, B, f=None):
+    """the plant the global solver's mpc_rollout steps when it is not the model (see BatchSolver.set_plant): (nx, nx) / (nx, nu) /
+    (nx,) shared, or (nx, nx, B) / (nx, nu, B) / (nx, B) per instance; None, None drops it.  The library checks the shapes;
+    not on a set_gpus solver"""
+    _need_setup(solver)
+    lib = load_library()
+    if A is None and B is None:
+        rc = lib.set_plant(None, 0, 0, None, 0, 0, None, 0, 0)
+    else:
+        A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        per = 1 if A.ndim == 3 else 0
+        Af, Bf = _flat_f(A), _flat_f(B)
+        ff = None if f is None else _flat_f(f)
+        rc = lib.set_plant(_dp(Af), A.shape[0], Af.size // max(1, A.shape[0]), _dp(Bf), B.shape[0], Bf.size // max(1, B.shape[0]),
+                           None if ff is None else _dp(ff), 0 if ff is None else ff.size, per)
+    if rc != 0:
+        raise TinyMPCError(f"Failed to set the plant ({_err()})")
+
+
+def set_disturbance(solver, w):
+    """additive disturbance of every step of the global solver's next closed loops: (nx, steps) shared or (nx, steps, B); None
+    drops it (see BatchSolver.set_disturbance).  Not on a set_gpus solver"""
+    _need_setup(solver)
+    lib = load_library()
+    if w is None:
+        rc = lib.set_disturbance(None, 0, 0, 0)
+    else:
+        w = np.asarray(w, dtype=np.float64)
+        wf = _flat_f(w)
+        rc = lib.set_disturbance(_dp(wf), w.shape[0], wf.size // max(1, w.shape[0]), 1 if w.ndim == 3 else 0)
+    if rc != 0:
+        raise TinyMPCError(f"Failed to set the disturbance ({_err()})")
+
+
+def plant_mode(solver):
+    """0 model, 1 shared plant, 2 per-instance plant; | 4 shared disturbance, | 8 per-instance disturbance"""
+    _need_setup(solver)
+    m = int(load_library().plant_mode())
+    if m < 0:
+        raise TinyMPCError(f"plant_mode failed ({_err()})")
+    return m
+
+
 def mpc_rollout(solver, steps):
-    """`steps` fused closed-loop steps on the global solver: dict(status, x (nx, steps, B), u (nu, steps, B), iter, solved)"""
+    """`steps` closed-loop steps on the global solver — solve, then the plant step x+ = f + A x + B u0 of the model, or of the plant
+    set_plant installed, plus the disturbance of set_disturbance: dict(status, x (nx, steps, B), u (nu, steps, B), iter, solved)"""
     _need_setup(solver)
     nx, nu, B = solver.nx, solver.nu, solver.batch
     x, u = np.zeros(nx * steps * B), np.zeros(nu * steps * B)
@@ -828,8 +882,52 @@ class BatchSolver:
         self._chk(self.lib.tinympc_set_ref_sequence(self.h, _dp(xs), self.nx, self.N * steps, _dp(us), self.nu,
                                                     (self.N - 1) * steps, steps), "set_ref_sequence")
 
+    def set_plant(self, A, B, f=None):
+        """the plant mpc_rollout steps when it is not the controller's model: x+ = f_p + A_p x + B_p u0 (+ w).  The dimensions
+        decide: A (nx, nx), B (nx, nu), f (nx,) shared by the batch, or A (nx, nx, B), B (nx, nu, B), f (nx, B) one plant per
+        instance; f None is zero.  set_plant(None, None) drops it: back to the model and to the routes that serve it.  fp64 on
+        the host and the device; set_precision keeps it.  See mpc_rollout for the route such a solver takes."""
+        if A is None and B is None:
+            self._chk(self.lib.tinympc_set_plant(self.h, None, None, None, 0), "set_plant")
+            return
+        nx, nu, Bn = self.nx, self.nu, self.batch
+        A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        f = None if f is None else np.asarray(f, dtype=np.float64)
+        per = A.ndim == 3
+        want = ((nx, nx, Bn), (nx, nu, Bn), (nx, Bn)) if per else ((nx, nx), (nx, nu), (nx,))
+        if A.shape != want[0] or B.shape != want[1] or (f is not None and f.shape != want[2]):
+            raise TinyMPCError(f"set_plant: expected A {(nx, nx)}, B {(nx, nu)}, f {(nx,)} or A {(nx, nx, Bn)}, B {(nx, nu, Bn)}, f {(nx, Bn)}; "
+                               f"got A {A.shape}, B {B.shape}" + ("" if f is None else f", f {f.shape}"))
+        Af, Bf, ff = _flat_f(A), _flat_f(B), None if f is None else _flat_f(f)
+        self._chk(self.lib.tinympc_set_plant(self.h, _dp(Af), _dp(Bf), None if ff is None else _dp(ff), 1 if per else 0), "set_plant")
+
+    def set_disturbance(self, w):
+        """additive disturbance of every step of the next closed loops: w (nx, steps) shared, or (nx, steps, B) per instance
+        (the layout of mpc_rollout's x).  Every mpc_rollout reads it from row 0; a loop longer than `steps` is refused.
+        Without set_plant it disturbs the model plant.  None drops it."""
+        if w is None:
+            self._chk(self.lib.tinympc_set_disturbance(self.h, None, 0, 0), "set_disturbance")
+            return
+        w = np.asarray(w, dtype=np.float64)
+        if w.ndim not in (2, 3) or w.shape[0] != self.nx or w.shape[1] < 1 or (w.ndim == 3 and w.shape[2] != self.batch):
+            raise TinyMPCError(f"set_disturbance: expected w (nx, steps) = ({self.nx}, steps) or (nx, steps, batch) = "
+                               f"({self.nx}, steps, {self.batch}); got {w.shape}")
+        wf = _flat_f(w)
+        self._chk(self.lib.tinympc_set_disturbance(self.h, _dp(wf), w.shape[1], 1 if w.ndim == 3 else 0), "set_disturbance")
+
+    def plant_mode(self):
+        """0 model, 1 shared plant, 2 per-instance plant; | 4 shared disturbance, | 8 per-instance disturbance"""
+        return int(self.lib.tinympc_plant_mode(self.h))
+
     def mpc_rollout(self, steps, stream=None):
-        """`steps` fused closed-loop MPC steps in one launch (plant = the family's own A, B).
+        """`steps` closed-loop MPC steps without the host in between: solve, apply u0 to the plant, solve again.  By default
+        the plant is the family's own model, x+ = f + A x + B u0, and the loop is fused into one launch where the kernel has one.
+        With set_plant / set_disturbance the plant is the caller's, x+ = f_p + A_p x + B_p u0 (+ w) in fp64: the loop then is a
+        chain of `steps` ordinary kept-workspace launches, each from the fp32 rounding of the state, with the plant step between
+        them — on whatever kernel such a solve takes, every kernel family, shape and precision, no switch, reference sequences
+        included; two loops in a row continue the fp64 state unless x0 was set in between.  Refused there: fewer disturbance
+        rows than steps, adaptive rho, set_warm_start(0), per-instance bounds without TINYMPC_HIP_STREAM_MPC.
+        With the model plant:
         (TINYMPC_HIP_LEAN_WS=1 when the solver is created: cartpole-class shapes on the lean kernel, as a chain of `steps`
         launches; with TINYMPC_HIP_LEAN_LOOP=1 beside it as one launch of its in-kernel loop — the same results.)
         Solvers on the stream / generic kernels (a horizon without a built-in entry, linear rows, cones or the affine term
