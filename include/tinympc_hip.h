@@ -139,6 +139,14 @@ int mpc_rollout(int steps, double *x_log, double *u_log, int *iter_log);
 int set_plant(double *A_data, int A_rows, int A_cols, double *B_data, int B_rows, int B_cols, double *f_data, int f_len, int per_instance);
 int set_disturbance(double *w_data, int w_rows, int w_cols, int per_instance);
 int plant_mode(void);
+/* ... and along a reference trajectory, windowed on the device (tinympc_set_ref_trajectory below, which describes it): x_data
+ * nx x Lx and u_data nu x Lu column-major (u_data NULL: zero input references), or with per_instance = 1 nx x (Lx batch) and
+ * nu x (Lu batch), instance after instance — the batch rides on the column count.  Row counts and widths are checked.
+ * x_data = NULL drops it.  set_ref_cursor (refused when negative) / ref_cursor move and read the cursor.  Not on a set_gpus
+ * solver, which has no mpc_rollout. */
+int set_ref_trajectory(double *x_data, int x_rows, int x_cols, double *u_data, int u_rows, int u_cols, int per_instance, int verbose);
+int set_ref_cursor(int cursor);
+int ref_cursor(void);
 
 /* ------------------------------------------------------------------------- */
 /* (2) handle API                                                            */
@@ -320,6 +328,38 @@ int tinympc_set_plant(tinympc_solver *s, const double *A, const double *B, const
 int tinympc_set_disturbance(tinympc_solver *s, const double *w, int steps, int per_instance);
 /* 0 model, 1 shared plant, 2 per-instance plant;  | 4 shared disturbance, | 8 per-instance disturbance */
 int tinympc_plant_mode(tinympc_solver *s);
+/* A reference trajectory, windowed on the device: every instance tracks a moving target of its own through a closed loop.
+ * x_traj is Lx rows of nx, u_traj (NULL = zero input references) Lu rows of nu, row after row (an nx x Lx / nu x Lu
+ * column-major matrix).  per_instance = 0: one trajectory shared by the batch; 1: x_traj [batch][Lx][nx], u_traj
+ * [batch][Lu][nu], the layout of tinympc_get_mpc_log's x / u, so one run's log can be another run's trajectory.  The rule: with
+ * the cursor c, the references of a solve are the window  x_ref[k] = x_traj[min(c + k, Lx - 1)], k = 0 .. N-1,
+ * u_ref[k] = u_traj[min(c + k, Lu - 1)], k = 0 .. N-2  — the last row is held beyond the end, so any Lx, Lu >= 1 serve any
+ * number of steps.  Values are rounded to fp32 once, here, as set_x_ref rounds; a window is a copy of those floats.
+ * A newly installed trajectory starts at cursor 0.  tinympc_solve uses the window at c and leaves c; tinympc_mpc_rollout(steps)
+ * uses the windows at c .. c + steps - 1 and leaves c + steps, so two loops in a row continue the trajectory as they continue
+ * the fp64 plant state; tinympc_set_ref_cursor moves it (a negative cursor is refused), tinympc_ref_cursor reads it.
+ * Routes: while a trajectory is installed the reference arrays are device-owned in its mode (shared or per instance, as after
+ * tinympc_set_ref_mode) and one small kernel cuts the window out of the device-resident trajectory whenever the window there
+ * is not the one the next launch needs — before a plain solve, and per step in the loop: nothing is uploaded per step.  Such a
+ * solver takes tinympc_mpc_rollout as the chain of tinympc_set_plant (above) — per step its ordinary kept-workspace launch,
+ * then the plant step — against the model (A, B, the affine term; a family solver's own A_b, B_b), or against the installed
+ * plant and disturbance: every kernel family, every precision, no environment switch; TINYMPC_HIP_LEAN_WS / _LEAN_LOOP /
+ * _STREAM_MPC / _STREAM_LOOP leave it on that chain (`steps` launches, tmpc_last_rollout_launches).
+ * x_traj = NULL drops the trajectory: the window at the cursor stays installed as the solver's ordinary references, shared or
+ * per instance, and the solver returns to the routes that serve those.  tinympc_set_x_ref / _set_u_ref do the same and then
+ * replace their side; tinympc_set_ref_sequence with steps > 0 and tinympc_set_ref_mode replace the trajectory outright;
+ * tinympc_set_ref_trajectory drops a sequence: the later call wins.  tinympc_set_precision keeps the trajectory, re-batching
+ * (set_batch_size) drops it as it drops every per-instance input.
+ * Refused here: Lx < 1, Lu < 1 with a u_traj, per_instance other than 0 / 1 (one flag: x_traj and u_traj are both shared or
+ * both per instance; the global form below also checks row counts and that per-instance widths are L * batch).  Refused by
+ * tinympc_mpc_rollout, the error naming the condition: adaptive rho, no persistent workspace (set_warm_start(0)), per-instance
+ * bounds without TINYMPC_HIP_STREAM_MPC, a disturbance with fewer rows than steps (it is read from row 0 whatever the cursor).
+ * A sharded solver (set_gpus / tinympc_sharded_*) has no mpc_rollout and takes no trajectory. */
+int tinympc_set_ref_trajectory(tinympc_solver *s, const double *x_traj, int Lx, const double *u_traj, int Lu, int per_instance);
+int tinympc_set_ref_cursor(tinympc_solver *s, int cursor);
+int tinympc_ref_cursor(tinympc_solver *s);
+/* 0 none, 1 shared, 2 per instance */
+int tinympc_ref_trajectory_mode(tinympc_solver *s);
 /* Tolerance-terminated solves of big batches: with chunk_iters > 0 (rounded up to a multiple of check_termination)
  * a solve runs in chunks of that many iterations and, between chunks, gathers the instances still iterating into
  * a dense list, so that wavefronts do not idle behind their slowest instance.  Iterates, iteration counts and

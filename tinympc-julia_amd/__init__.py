@@ -103,6 +103,10 @@ from .tinympc import (  # noqa: E402,F401
     set_plant,
     set_disturbance,
     plant_mode,
+    set_ref_trajectory,
+    set_ref_cursor,
+    ref_cursor,
+    ref_window,
     mpc_rollout,
     set_batch_size,
     set_bound_constraints,

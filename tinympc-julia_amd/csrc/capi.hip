@@ -373,6 +373,26 @@ int tinympc_set_disturbance(tinympc_solver *s, const double *w, int steps, int p
     return guarded("set_disturbance", [&] { return s->s.set_disturbance(w, steps, per_instance); });
 }
 int tinympc_plant_mode(tinympc_solver *s) { return s ? s->s.plant_mode() : -1; }
+int tinympc_set_ref_trajectory(tinympc_solver *s, const double *x_traj, int Lx, const double *u_traj, int Lu, int per_instance) {
+    if (!s) return -1;
+    if (x_traj && (Lx < 1 || (u_traj && Lu < 1) || (per_instance != 0 && per_instance != 1))) {
+        set_error("set_ref_trajectory: expected Lx >= 1 rows of x_traj, Lu >= 1 rows of u_traj where one is given, and per_instance 0 "
+                  "(x_traj [Lx][nx], u_traj [Lu][nu]) or 1 (x_traj [batch][Lx][nx], u_traj [batch][Lu][nu])");
+        return -1;
+    }
+    return guarded("set_ref_trajectory", [&] { return s->s.set_ref_trajectory(x_traj, Lx, u_traj, Lu, per_instance); });
+}
+int tinympc_set_ref_cursor(tinympc_solver *s, int cursor) {
+    if (!s) return -1;
+    if (cursor < 0) {
+        set_error("set_ref_cursor: the cursor is a row of the reference trajectory, 0 or more (rows past the end read the last one)");
+        return -1;
+    }
+    s->s.ref_cursor = cursor;
+    return 0;
+}
+int tinympc_ref_cursor(tinympc_solver *s) { return s ? s->s.ref_cursor : -1; }
+int tinympc_ref_trajectory_mode(tinympc_solver *s) { return s ? s->s.traj_kind : -1; }
 int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter) {
     if (!s) return -1;
     return guarded("get_mpc_log", [&] { return s->s.get_mpc_log(x, u, iter); });
@@ -462,6 +482,7 @@ int tinympc_set_ref_mode(tinympc_solver *s, int ref_mode) {
     if (!s || ref_mode < 0 || ref_mode > 2) return -1;
     return guarded("set_ref_mode", [&]() -> int {
         tmpc::Solver &v = s->s;
+        if (v.traj_kind && v.drop_ref_trajectory(false)) return -1;   // (a reference trajectory goes: the caller writes the arrays now)
         // make the device buffers large enough for the mode, then hand them to the caller
         v.xref_kind = v.uref_kind = ref_mode;
         v.h_xref.assign(ref_mode == 2 ? (size_t)v.batch * v.ex() : (ref_mode == 1 ? v.ex() : 0), 0.f);
@@ -995,6 +1016,42 @@ int plant_mode(void) {
         return -1;
     }
     return tinympc_plant_mode(g_solver.get());
+}
+// ... and along a reference trajectory (tinympc_set_ref_trajectory): x nx x Lx and u nu x Lu column-major (shared), or
+// nx x (Lx batch) and nu x (Lu batch), instance after instance — the batch rides on the column count; shapes checked here
+int set_ref_trajectory(double *x_data, int x_rows, int x_cols, double *u_data, int u_rows, int u_cols, int per_instance, int verbose) {
+    (void)verbose;
+    if (need_global("set_ref_trajectory")) return -1;
+    if (g_sharded) {
+        set_error("set_ref_trajectory: not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    const tmpc::Solver &v = g_solver->s;
+    if (!x_data) return tinympc_set_ref_trajectory(g_solver.get(), nullptr, 0, nullptr, 0, 0);
+    const int n = per_instance ? v.batch : 1;
+    if ((per_instance != 0 && per_instance != 1) || x_rows != v.nx || x_cols < 1 || x_cols % n != 0 ||
+        (u_data && (u_rows != v.nu || u_cols < 1 || u_cols % n != 0))) {
+        set_error("set_ref_trajectory: expected x_traj nx x Lx and u_traj nu x Lu (shared), or nx x (Lx batch) and nu x (Lu batch) (per instance), Lx, Lu >= 1; here nx = " +
+                  std::to_string(v.nx) + ", nu = " + std::to_string(v.nu) + ", batch = " + std::to_string(v.batch));
+        return -1;
+    }
+    return tinympc_set_ref_trajectory(g_solver.get(), x_data, x_cols / n, u_data, u_data ? u_cols / n : 0, per_instance);
+}
+int set_ref_cursor(int cursor) {
+    if (need_global("set_ref_cursor")) return -1;
+    if (g_sharded) {
+        set_error("set_ref_cursor: not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    return tinympc_set_ref_cursor(g_solver.get(), cursor);
+}
+int ref_cursor(void) {
+    if (need_global("ref_cursor")) return -1;
+    if (g_sharded) {
+        set_error("ref_cursor: not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    return tinympc_ref_cursor(g_solver.get());
 }
 int mpc_rollout(int steps, double *x_log, double *u_log, int *iter_log) {
     if (need_global("mpc_rollout")) return -1;

@@ -407,7 +407,8 @@ struct Solver {
     //   Chain       per step one workspace-carrying launch and the plant step, stream-ordered, the plant state kept in fp64 on
     //               the device between steps (mfma; the lean kernel under TINYMPC_HIP_LEAN_WS; the stream / generic kernels
     //               under TINYMPC_HIP_STREAM_MPC, stream_plant: f and per-instance families in the plant, the state resumed;
-    //               an own-plant solver on whatever kernel a kept-workspace solve of it takes, no switch: rollout_chain_own)
+    //               an own-plant solver, or one with a reference trajectory, on whatever kernel a kept-workspace solve of it
+    //               takes, no switch: rollout_chain_own)
     //   LeanLoop    ONE launch of the lean kernel's in-kernel loop (TINYMPC_HIP_LEAN_LOOP)
     //   StreamLoop  ONE launch of the stream kernel's (TINYMPC_HIP_STREAM_LOOP)
     //   Refused     the reason is the last error
@@ -415,7 +416,7 @@ struct Solver {
     struct RolloutPlan {
         Rollout route = Rollout::Refused;
         bool stream_plant = false;
-        bool own_plant = false;   // the chain on the plain-solve kernel, stepped by plant_step_own_kernel
+        bool own_plant = false;   // the chain on the plain-solve kernel, stepped by plant_step_own_kernel (a trajectory solver's too)
     };
     RolloutPlan plan_rollout(int mpc_steps);
     int rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant);
@@ -446,6 +447,21 @@ struct Solver {
     int set_disturbance(const double *w, int steps, int per_instance);
     void drop_own_plant();   // both pieces (a re-batch)
     int ensure_own_plant();
+    // A reference trajectory (tinympc_set_ref_trajectory): x_traj Lx rows of nx and optionally u_traj Lu rows of nu, shared or
+    // [batch][L][n] per instance, rounded to fp32 once when set; the references of a solve are its window at the cursor,
+    // x_ref[k] = x_traj[min(c + k, Lx - 1)], u_ref[k] = u_traj[min(c + k, Lu - 1)] (no u_traj: zero).  traj_kind 0: none, 1: shared,
+    // 2: per instance.  While one is installed the references are device-owned in the trajectory's mode (refs_device_owned with
+    // ref_mode, what every route already keys on) and ref_window_kernel cuts the window into d_xref / d_uref whenever the one
+    // there (traj_dev_cursor, -1: none) is not the one the next launch needs: before a plain solve's launch, and per step in
+    // the chain — such a solver's mpc_rollout is the own-plant chain against the model (or the installed plant), and leaves the
+    // cursor steps further on.  The host copies serve the drop, which installs the window at the cursor as ordinary references.
+    int traj_kind = 0, traj_Lx = 0, traj_Lu = 0;   // traj_Lu 0: no u_traj
+    int ref_cursor = 0, traj_dev_cursor = -1;
+    std::vector<float> h_xtraj, h_utraj;
+    float *d_xtraj = nullptr, *d_utraj = nullptr;
+    int set_ref_trajectory(const double *x_traj, int Lx, const double *u_traj, int Lu, int per_instance);
+    int drop_ref_trajectory(bool install_window);   // install_window: the window at the cursor becomes the ordinary references
+    int ensure_ref_window(hipStream_t stream, int cursor);
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};
     int *d_count = nullptr;

@@ -2,6 +2,7 @@
 #include "solver.h"
 #include "admm_generic.hip.h"   // Ws64 (layout of the precision-2 workspace)
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -149,6 +150,8 @@ Solver::~Solver() {
     dev_free(d_plant_het);
     dev_free(d_own_plant);
     dev_free(d_dist);
+    dev_free(d_xtraj);
+    dev_free(d_utraj);
     if (h_gstat) (void)hipHostFree(h_gstat);
     h_gstat = nullptr;
     for (hipEvent_t e : ev_ring)
@@ -568,6 +571,7 @@ int Solver::alloc_batch(int batch_) {
     free_batch();
     drop_instance_bounds();   // (per-instance inputs do not survive a re-batch: back to the shared bounds)
     drop_own_plant();         // (... and back to the model plant)
+    (void)drop_ref_trajectory(false);   // (... and to the references set below)
     batch = batch_;
     if (select_kernel()) return -1;
     const size_t Bn = (size_t)batch, EX = (size_t)ex(), EU = (size_t)eu();
@@ -752,6 +756,8 @@ int Solver::set_ref(bool is_x, const double *ref, int cols) {
                        : "set_u_ref: expected nu x (N-1) or nu x ((N-1)*batch)");
         return -1;
     }
+    // (a reference trajectory goes: its window at the cursor stays as the ordinary references, of which this call replaces one)
+    if (traj_kind && drop_ref_trajectory(true)) return -1;
     std::vector<float> &h = is_x ? h_xref : h_uref;
     const size_t n = (size_t)rows * cols;
     h.resize(n);
@@ -787,6 +793,7 @@ int Solver::set_ref_sequence(const double *x_seq, const double *u_seq, int steps
     }
     HIP_TRY(hipSetDevice(device));
     if (wait_last_launch()) return -1;
+    if (traj_kind && drop_ref_trajectory(false)) return -1;   // (the sequence replaces a reference trajectory: the later call wins)
     const size_t EX = (size_t)ex(), EU = (size_t)eu();
     std::vector<float> hx(EX * steps), hu(EU * steps);
     for (size_t i = 0; i < hx.size(); ++i) hx[i] = (float)x_seq[i];
@@ -1156,8 +1163,9 @@ __global__ void residual_max_kernel(const float *res, long batch, uint32_t *gsta
 // with; select_kernel's own; a selection without a closed loop — the stream / generic kernels have none unless
 // TINYMPC_HIP_STREAM_MPC is set, and none with adaptive rho; a solver without the persistent workspace.  Then, in order of
 // preference:
-//   an own-plant solver (set_plant / set_disturbance): the chain on whatever kernel a plain kept-workspace solve of it takes,
-//     selected as for a plain solve, every family and precision, no switch (rollout_chain_own); not with adaptive rho;
+//   an own-plant solver (set_plant / set_disturbance) or one with a reference trajectory (set_ref_trajectory): the chain on
+//     whatever kernel a plain kept-workspace solve of it takes, selected as for a plain solve, every family and precision, no
+//     switch (rollout_chain_own); not with adaptive rho;
 //   the matrix-core kernel of the box-only shapes (mfma): the chain — per step one workspace-carrying launch and the plant
 //     step, stream-ordered, the plant state in fp64 on the device between them;
 //   TINYMPC_HIP_LEAN_WS, where lean_plan takes a warm whole-batch launch (the calling pattern, whatever the iteration count):
@@ -1189,14 +1197,20 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
     }
     if (bounds_mode && !sw.stream_mpc)
         return refuse("mpc_rollout: per-instance bounds have no closed loop by default (TINYMPC_HIP_STREAM_MPC=1 gives one as a chain of launches; or step it from the host)");
-    if (own_plant()) {
+    if (own_plant() || traj_kind) {
         // a plant of its own or a disturbance: the chain on the kernel a plain kept-workspace solve takes (its launches ARE plain
-        // solves, every kernel family and precision has them), stepped by plant_step_own_kernel — ahead of the kernels' own routes
+        // solves, every kernel family and precision has them), stepped by plant_step_own_kernel — ahead of the kernels' own routes.
+        // A reference trajectory takes the same chain, against the model where no plant is installed: every launch is handed
+        // its step's window by ref_window_kernel, which no loop inside a kernel could be without an edit of that kernel
         if (dist_kind && dist_steps < mpc_steps)
             return refuse("mpc_rollout: the disturbance holds " + std::to_string(dist_steps) + " steps, the loop asks for " + std::to_string(mpc_steps) +
                           " (one row per step, read from row 0)");
-        if (st.adaptive_rho) return refuse("mpc_rollout: a plant of its own / a disturbance is not available with adaptive rho");
+        if (st.adaptive_rho)
+            return refuse(own_plant() ? "mpc_rollout: a plant of its own / a disturbance is not available with adaptive rho"
+                                      : "mpc_rollout: a reference trajectory is not available with adaptive rho");
         if (!warm_start) return refuse("mpc_rollout needs the persistent workspace (set_warm_start(1))");
+        if (traj_kind && ref_cursor > INT_MAX - mpc_steps)
+            return refuse("mpc_rollout: the reference cursor would pass the largest int (set_ref_cursor: every cursor from the longer trajectory's last row on gives the same window)");
         if (select_kernel(false) || ensure_extension_buffers()) return rp;
         if ((packs_dirty && upload_packs()) || upload_refs()) return rp;
         rp.route = Rollout::Chain, rp.own_plant = true;
@@ -1233,6 +1247,7 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     layout_final = true;
     if (mpc_steps <= 0) {
         if (select_kernel() || ensure_extension_buffers()) return -1;
+        if (traj_kind && ensure_ref_window(stream, ref_cursor)) return -1;   // (a reference trajectory: its window at the cursor)
         const bool chunkable = chunk_iters > 0 && !hetero && (ke || se || (ce && ce->ws)) && st.check_termination > 0 &&
                                st.abs_pri_tol > 0.0 && st.abs_dua_tol > 0.0 && st.max_iter > chunk_iters;
         return chunkable ? solve_chunked(stream) : launch_pass(stream, whole_batch(!warm_start, warm_start));
@@ -1764,6 +1779,8 @@ int Solver::ensure_own_plant() {
 
 // An own-plant solver's chain: per step the solver's ordinary kept-workspace launch — from the fp32 rounding in d_x0, Pass::x0d
 // null, what a host-stepped loop launches — and plant_step_own_kernel, stream-ordered; the fp64 state resumed as the stream chain's
+// With a reference trajectory every launch is handed its step's window first (ref_window_kernel, where the window on the device
+// is another), and the cursor is left mpc_steps further on.
 int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
     if (ensure_own_plant() || plant_start(stream, true)) return -1;
     const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
@@ -1771,6 +1788,7 @@ int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
     Pass pass = whole_batch(false, true);
     for (int step = 0; step < mpc_steps; ++step) {
         if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
+        if (traj_kind && ensure_ref_window(stream, ref_cursor + step)) return -1;
         if (launch_pass(stream, pass)) return -1;
         plant_step_own_kernel<<<(unsigned)((batch + per_block - 1) / per_block), 256, 0, stream>>>(
             d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L,
@@ -1778,7 +1796,153 @@ int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
             (long)batch, mpc_steps, step);
     }
     HIP_TRY(hipGetLastError());
+    if (traj_kind) ref_cursor += mpc_steps;   // (plan_rollout checked the sum)
     return record_done(stream);
+}
+
+// The references of one solve cut out of a reference trajectory (tinympc_set_ref_trajectory): the window at `cursor`,
+// xref[b][k][r] = xtraj[b][min(cursor + k, Lx - 1)][r] for the N knots, uref[b][k][a] = utraj[b][min(cursor + k, Lu - 1)][a] for the
+// N - 1 (utraj null: zero) — the last row held beyond the end.  A flat index over the output, the x part (nxo floats, the first
+// ceil(nxo / REF_WINDOW_SPAN) workgroups) then the u part (nuo floats): a workgroup takes REF_WINDOW_SPAN consecutive floats, a
+// lane those blockDim.x apart, so at every one of its REF_WINDOW_PER_LANE steps consecutive lanes write consecutive floats and,
+// within a row and from one unclamped row to the next, read consecutive floats.  A lane splits its first index into (instance,
+// knot, row) by division once (32-bit where the part is indexed in 32 bits) and then steps it by the workgroup-uniform split of
+// blockDim.x — the divisions cost as much issue time as the traffic takes when every float pays them.  Instance b's trajectory
+// starts at xtraj + b * x_stride / utraj + b * u_stride; the shared form is one "instance" (nxo = N nx, strides 0) written to
+// the shared [N][nx] / [N-1][nu] arrays.  Copies only: a window holds the trajectory's own floats.
+constexpr int REF_WINDOW_THREADS = 256, REF_WINDOW_PER_LANE = 4, REF_WINDOW_SPAN = REF_WINDOW_THREADS * REF_WINDOW_PER_LANE;
+__global__ void ref_window_kernel(float *xref, float *uref, const float *xtraj, const float *utraj, long x_stride, long u_stride,
+                                  int Lx, int Lu, int nx, int nu, int N, long nxo, long nuo, int cursor) {
+    const long groups_x = (nxo + REF_WINDOW_SPAN - 1) / REF_WINDOW_SPAN;
+    const bool is_x = (long)blockIdx.x < groups_x;
+    const long count = is_x ? nxo : nuo, j0 = ((long)blockIdx.x - (is_x ? 0 : groups_x)) * REF_WINDOW_SPAN + threadIdx.x;
+    if (j0 >= count) return;
+    const int n = is_x ? nx : nu, knots = is_x ? N : N - 1, per = n * knots;   // floats per row; per instance
+    const float *traj = is_x ? xtraj : utraj;
+    float *out = is_x ? xref : uref;
+    const long stride = is_x ? x_stride : u_stride, last = (is_x ? Lx : Lu) - 1;
+    long b;
+    int rem;
+    if (count <= 0x7fffffffL) {
+        b = (unsigned)j0 / (unsigned)per;
+        rem = (int)((unsigned)j0 - (unsigned)b * (unsigned)per);
+    } else {
+        b = j0 / per;
+        rem = (int)(j0 - b * per);
+    }
+    int k = rem / n, r = rem - k * n;
+    // blockDim.x floats further on: sb instances, sk knots and sr rows, each below its radix, so one carry per digit
+    const int sb = REF_WINDOW_THREADS / per, sk = (REF_WINDOW_THREADS - sb * per) / n, sr = REF_WINDOW_THREADS - sb * per - sk * n;
+    for (int e = 0; e < REF_WINDOW_PER_LANE; ++e) {
+        const long j = j0 + (long)e * REF_WINDOW_THREADS;
+        if (j >= count) return;
+        const long at = (long)cursor + k, row = at < last ? at : last;
+        out[j] = traj ? traj[b * stride + row * n + r] : 0.f;
+        r += sr;
+        if (r >= n) r -= n, ++k;
+        k += sk;
+        if (k >= knots) k -= knots, ++b;
+        b += sb;
+    }
+}
+
+// x_traj: Lx rows of nx, u_traj (or null: zero input references): Lu rows of nu, row after row — the columns of an nx x Lx /
+// nu x Lu column-major matrix — shared, or instance after instance ([batch][L][n], the layout of get_mpc_log's x / u).  Rounded
+// to fp32 here, as set_ref rounds.  x_traj null drops the trajectory and leaves its window at the cursor as the ordinary
+// references.  A newly installed trajectory starts at cursor 0 (set_ref_cursor moves it, mpc_rollout advances it).
+int Solver::set_ref_trajectory(const double *x_traj, int Lx, const double *u_traj, int Lu, int per_instance) {
+    if (!x_traj) return traj_kind ? drop_ref_trajectory(true) : 0;
+    if (Lx < 1 || (u_traj && Lu < 1)) {
+        set_error("set_ref_trajectory: expected Lx >= 1 rows of x_traj, and Lu >= 1 rows of u_traj where one is given");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;   // (a chain still running reads the trajectory and the reference arrays)
+    const size_t n = per_instance ? (size_t)batch : 1, EX = (size_t)ex(), EU = (size_t)eu();
+    const size_t nxf = n * (size_t)Lx * nx, nuf = u_traj ? n * (size_t)Lu * nu : 0;
+    std::vector<float> hx(nxf), hu(nuf);
+    for (size_t i = 0; i < nxf; ++i) hx[i] = (float)x_traj[i];
+    for (size_t i = 0; i < nuf; ++i) hu[i] = (float)u_traj[i];
+    if (dev_alloc(d_xtraj, nxf)) return -1;
+    HIP_TRY(hipMemcpy(d_xtraj, hx.data(), nxf * sizeof(float), hipMemcpyHostToDevice));
+    if (nuf) {
+        if (dev_alloc(d_utraj, nuf)) return -1;
+        HIP_TRY(hipMemcpy(d_utraj, hu.data(), nuf * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        dev_free(d_utraj);
+    }
+    // the reference arrays in the trajectory's mode, handed to the window kernel: the device-owned path (tinympc_set_ref_mode)
+    if (xref_cap < n * EX) {
+        if (dev_alloc(d_xref, n * EX)) return -1;
+        xref_cap = n * EX;
+    }
+    if (uref_cap < n * EU) {
+        if (dev_alloc(d_uref, n * EU)) return -1;
+        uref_cap = n * EU;
+    }
+    h_xtraj.swap(hx), h_utraj.swap(hu);
+    traj_kind = per_instance ? 2 : 1, traj_Lx = Lx, traj_Lu = u_traj ? Lu : 0;
+    ref_cursor = 0, traj_dev_cursor = -1;
+    h_xref.clear(), h_uref.clear();
+    xref_kind = uref_kind = ref_mode = traj_kind;
+    refs_dirty = false;
+    refs_device_owned = true;
+    ref_seq_steps = 0;   // (a reference sequence goes: the later call wins)
+    return 0;
+}
+
+// The trajectory goes.  install_window: its window at the cursor stays, as references set by set_x_ref / set_u_ref would be —
+// the same floats, shared or per instance, an all-zero side in the zero mode as there — and the solver returns to the routes
+// that serve those.  Otherwise (the caller installs references of its own next) zero references.
+int Solver::drop_ref_trajectory(bool install_window) {
+    if (!traj_kind) return 0;
+    if (wait_last_launch()) return -1;
+    h_xref.clear(), h_uref.clear();
+    xref_kind = uref_kind = 0;
+    if (install_window) {
+        const size_t n = traj_kind == 2 ? (size_t)batch : 1;
+        auto cut = [&](std::vector<float> &h, int &kind, const std::vector<float> &traj, int L, int rows, int knots) {
+            if (L < 1) return;
+            h.resize(n * knots * rows);
+            bool all_zero = true;
+            for (size_t b = 0; b < n; ++b)
+                for (int k = 0; k < knots; ++k) {
+                    const size_t row = (size_t)std::min<long>((long)ref_cursor + k, L - 1);
+                    for (int r = 0; r < rows; ++r) {
+                        const float v = traj[(b * L + row) * rows + r];
+                        h[(b * knots + k) * rows + r] = v;
+                        all_zero = all_zero && v == 0.f;
+                    }
+                }
+            if (all_zero)
+                h.clear();
+            else
+                kind = traj_kind;
+        };
+        cut(h_xref, xref_kind, h_xtraj, traj_Lx, nx, N);
+        cut(h_uref, uref_kind, h_utraj, traj_Lu, nu, N - 1);
+    }
+    traj_kind = traj_Lx = traj_Lu = 0;
+    traj_dev_cursor = -1;
+    h_xtraj.clear(), h_utraj.clear();
+    dev_free(d_xtraj);
+    dev_free(d_utraj);
+    refs_device_owned = false;
+    refs_dirty = true;
+    return 0;
+}
+
+// the window at `cursor` into d_xref / d_uref, stream-ordered, unless it is the one there
+int Solver::ensure_ref_window(hipStream_t stream, int cursor) {
+    if (traj_dev_cursor == cursor) return 0;
+    const long n = traj_kind == 2 ? (long)batch : 1, nxo = n * ex(), nuo = n * eu();
+    const long groups = (nxo + REF_WINDOW_SPAN - 1) / REF_WINDOW_SPAN + (nuo + REF_WINDOW_SPAN - 1) / REF_WINDOW_SPAN;
+    ref_window_kernel<<<(unsigned)groups, REF_WINDOW_THREADS, 0, stream>>>(
+        d_xref, d_uref, d_xtraj, d_utraj, traj_kind == 2 ? (long)traj_Lx * nx : 0L, traj_kind == 2 ? (long)traj_Lu * nu : 0L, traj_Lx,
+        traj_Lu, nx, nu, N, nxo, nuo, cursor);
+    HIP_TRY(hipGetLastError());
+    traj_dev_cursor = cursor;
+    return 0;
 }
 
 // The closed loop as ONE launch of the lean or the stream kernel's in-kernel loop (plan_rollout found the kernel): the fp64

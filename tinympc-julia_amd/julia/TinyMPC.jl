@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_instance_bounds,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_instance_bounds,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -290,6 +290,46 @@ function plant_mode(solver::TinyMPCSolver)
     m = ccall((:plant_mode, _lib_path()), Int32, ())
     m < 0 && error("plant_mode failed ($(_last_error()))")
     return Int(m)
+end
+
+# A reference trajectory, windowed on the device: every instance tracks a moving target of its own through mpc_rollout, and nothing
+# is uploaded per step.  x_traj (nx, Lx) and u_traj (nu, Lu) shared by the batch, or (nx, Lx, batch) and (nu, Lu, batch) one
+# trajectory per instance (the shapes of mpc_rollout's x and u: one run's log can be another run's trajectory), both shared or both
+# per instance; u_traj = nothing is zero input references; set_ref_trajectory(solver, nothing) drops it and leaves the window at the
+# cursor as ordinary references.  With the cursor c (0-based) the references of a solve are the rows min(c + k, L - 1) of the
+# trajectory, k = 0 .. N-1 (N-2 for u): the pattern of examples/rocket_landing_constraints.jl:107-115, which shifts x_ref by one
+# knot per step, with the last row held beyond the end.  solve reads the window at the cursor; mpc_rollout(steps) the windows at
+# c .. c+steps-1, as a chain of `steps` ordinary kept-workspace launches (every shape and precision, no environment switch), and
+# leaves c + steps.  set_x_ref / set_u_ref / set_ref_sequence replace it; it replaces a sequence.  Not with adaptive rho, not on a
+# sharded solver (set_gpus > 1).  (Written against the C-ABI like the rest of this file, not executed here.)
+function set_ref_trajectory(solver::TinyMPCSolver, x_traj::Union{Array{Float64},Nothing}, u_traj::Union{Array{Float64},Nothing}=nothing;
+                            verbose::Bool=false)
+    _need(solver)
+    sig = (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32)
+    x_traj === nothing && return _ok(ccall((:set_ref_trajectory, _lib_path()), Int32, sig, C_NULL, 0, 0, C_NULL, 0, 0, 0, verbose ? 1 : 0),
+                                     "Failed to drop the reference trajectory")
+    (u_traj === nothing || ndims(u_traj) == ndims(x_traj)) ||
+        error("set_ref_trajectory: x_traj and u_traj are both shared (nx, Lx) / (nu, Lu) or both per instance (nx, Lx, batch) / (nu, Lu, batch)")
+    per = ndims(x_traj) == 3 ? 1 : 0
+    _ok(ccall((:set_ref_trajectory, _lib_path()), Int32, sig,
+              x_traj, size(x_traj, 1), div(length(x_traj), max(1, size(x_traj, 1))),
+              u_traj === nothing ? C_NULL : u_traj, u_traj === nothing ? 0 : size(u_traj, 1),
+              u_traj === nothing ? 0 : div(length(u_traj), max(1, size(u_traj, 1))), per, verbose ? 1 : 0),
+        "Failed to set the reference trajectory")
+end
+
+# the cursor (0-based row of the trajectory the next window starts at): 0 for a new trajectory, `steps` further on after every
+# mpc_rollout; a negative cursor is refused
+function set_ref_cursor(solver::TinyMPCSolver, cursor::Integer)
+    _need(solver)
+    _ok(ccall((:set_ref_cursor, _lib_path()), Int32, (Int32,), cursor), "Failed to set the reference cursor")
+end
+
+function ref_cursor(solver::TinyMPCSolver)
+    _need(solver)
+    c = ccall((:ref_cursor, _lib_path()), Int32, ())
+    c < 0 && error("ref_cursor failed ($(_last_error()))")
+    return Int(c)
 end
 
 function reset_workspace(solver::TinyMPCSolver)

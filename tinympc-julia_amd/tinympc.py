@@ -121,6 +121,13 @@ SIGNATURES = {
     "set_plant": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_int, c_dp, c_int, c_int]),
     "set_disturbance": (c_int, [c_dp, c_int, c_int, c_int]),
     "plant_mode": (c_int, []),
+    "tinympc_set_ref_trajectory": (c_int, [c_vp, c_dp, c_int, c_dp, c_int, c_int]),
+    "tinympc_set_ref_cursor": (c_int, [c_vp, c_int]),
+    "tinympc_ref_cursor": (c_int, [c_vp]),
+    "tinympc_ref_trajectory_mode": (c_int, [c_vp]),
+    "set_ref_trajectory": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_int, c_int, c_int]),
+    "set_ref_cursor": (c_int, [c_int]),
+    "ref_cursor": (c_int, []),
     "tinympc_set_profiling": (c_int, [c_vp, c_int]),
     "tinympc_set_compaction": (c_int, [c_vp, c_int]),
     "tinympc_set_adaptive_rho": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_int]),
@@ -375,7 +382,8 @@ def get_status(solver):
 
 def set_ref_sequence(solver, x_ref_seq, u_ref_seq):
     """shared references of every step of the next closed loops, (nx, N, steps) / (nu, N-1, steps).  Supported wherever
-    mpc_rollout is (see BatchSolver.set_ref_sequence); not on a sharded solver"""
+    mpc_rollout is (see BatchSolver.set_ref_sequence); replaces a reference trajectory (set_ref_trajectory, which serves windows of
+    ONE trajectory, per instance too, without the N-fold blow-up); not on a sharded solver"""
     _need_setup(solver)
     xs = np.asfortranarray(np.asarray(x_ref_seq, dtype=np.float64))
     us = np.asfortranarray(np.asarray(u_ref_seq, dtype=np.float64))
@@ -432,9 +440,68 @@ def plant_mode(solver):
     return m
 
 
+def ref_window(traj, cursor, knots):
+    """THE WINDOW RULE of a reference trajectory, in numpy: the references of a solve with the cursor at `cursor` are the `knots`
+    rows  traj[min(cursor + k, L - 1)], k = 0 .. knots-1  — a sliding window, the last row held beyond the end, so any L >= 1
+    serves any cursor.  traj is (rows, L) or (rows, L, B) (rows: nx with knots = N for x_ref, nu with knots = N - 1 for u_ref);
+    returns (rows, knots) or (rows, knots, B), a copy, in traj's dtype: what set_x_ref / set_u_ref take, and what the library's
+    window kernel writes on the device (there in the fp32 rounding set_ref_trajectory made)."""
+    traj = np.asarray(traj)
+    if traj.ndim not in (2, 3) or traj.shape[1] < 1 or cursor < 0 or knots < 0:
+        raise ValueError(f"ref_window: expected traj (rows, L) or (rows, L, B) with L >= 1, cursor >= 0, knots >= 0; got {traj.shape}, {cursor}, {knots}")
+    rows = np.minimum(int(cursor) + np.arange(int(knots)), traj.shape[1] - 1)
+    return np.array(traj[:, rows], order="F")
+
+
+def _traj_args(x_traj, u_traj):
+    """(x flat, x rows, x cols, u flat | None, u rows, u cols, per_instance) of a trajectory pair, the batch on the columns"""
+    x = np.asarray(x_traj, dtype=np.float64)
+    u = None if u_traj is None else np.asarray(u_traj, dtype=np.float64)
+    if x.ndim not in (2, 3) or (u is not None and u.ndim not in (2, 3)):
+        raise TinyMPCError("set_ref_trajectory: expected x_traj (nx, Lx) or (nx, Lx, batch), u_traj (nu, Lu) or (nu, Lu, batch)")
+    if u is not None and u.ndim != x.ndim:
+        raise TinyMPCError(f"set_ref_trajectory: x_traj and u_traj are both shared or both per instance; got x_traj {x.shape}, u_traj {u.shape} "
+                           "(a shared one beside a per-instance one: tile it over the batch)")
+    xf, uf = _flat_f(x), None if u is None else _flat_f(u)
+    return (xf, x.shape[0], xf.size // max(1, x.shape[0]), uf, 0 if u is None else u.shape[0],
+            0 if u is None else uf.size // max(1, u.shape[0]), 1 if x.ndim == 3 else 0)
+
+
+def set_ref_trajectory(solver, x_traj, u_traj=None, *, verbose=False):
+    """a reference trajectory for the global solver, windowed on the device (see BatchSolver.set_ref_trajectory): x_traj (nx, Lx)
+    and u_traj (nu, Lu) shared, or (nx, Lx, B) and (nu, Lu, B) per instance; u_traj None: zero input references; x_traj None drops
+    it.  The library checks row counts and widths; not on a set_gpus solver"""
+    _need_setup(solver)
+    lib = load_library()
+    if x_traj is None:
+        rc = lib.set_ref_trajectory(None, 0, 0, None, 0, 0, 0, 1 if verbose else 0)
+    else:
+        xf, xr, xc, uf, ur, uc, per = _traj_args(x_traj, u_traj)
+        rc = lib.set_ref_trajectory(_dp(xf), xr, xc, None if uf is None else _dp(uf), ur, uc, per, 1 if verbose else 0)
+    if rc != 0:
+        raise TinyMPCError(f"Failed to set the reference trajectory ({_err()})")
+
+
+def set_ref_cursor(solver, cursor):
+    """move the global solver's reference cursor (>= 0): the next solve reads the window there, the next mpc_rollout starts there"""
+    _need_setup(solver)
+    if load_library().set_ref_cursor(int(cursor)) != 0:
+        raise TinyMPCError(f"Failed to set the reference cursor ({_err()})")
+
+
+def ref_cursor(solver):
+    """the global solver's reference cursor: 0 for a new trajectory, `steps` further on after every mpc_rollout"""
+    _need_setup(solver)
+    c = int(load_library().ref_cursor())
+    if c < 0:
+        raise TinyMPCError(f"ref_cursor failed ({_err()})")
+    return c
+
+
 def mpc_rollout(solver, steps):
     """`steps` closed-loop steps on the global solver — solve, then the plant step x+ = f + A x + B u0 of the model, or of the plant
-    set_plant installed, plus the disturbance of set_disturbance: dict(status, x (nx, steps, B), u (nu, steps, B), iter, solved)"""
+    set_plant installed, plus the disturbance of set_disturbance; with set_ref_trajectory every step against its own window of the
+    trajectory, the cursor left `steps` further on: dict(status, x (nx, steps, B), u (nu, steps, B), iter, solved)"""
     _need_setup(solver)
     nx, nu, B = solver.nx, solver.nu, solver.batch
     x, u = np.zeros(nx * steps * B), np.zeros(nu * steps * B)
@@ -870,7 +937,9 @@ class BatchSolver:
         (set after the sequence — a later SHARED set_x_ref / set_u_ref drops the sequence instead), with adaptive rho, at
         precision 2, on a quad entry with a horizon above 20, and on shapes without a closed loop (stream / generic kernels) —
         the last two unless TINYMPC_HIP_STREAM_MPC=1 (see mpc_rollout) gives those solvers their chained loop, which takes the
-        sequence launch by launch"""
+        sequence launch by launch.  A sequence is shared by the batch and N-fold redundant where the steps' references are
+        shifted windows of one trajectory: set_ref_trajectory takes that trajectory itself, per instance too.  A sequence
+        (steps > 0) replaces an installed trajectory, and a trajectory drops the sequence: the later call wins"""
         if x_ref_seq is None:
             self._chk(self.lib.tinympc_set_ref_sequence(self.h, None, 0, 0, None, 0, 0, 0), "set_ref_sequence")
             return
@@ -919,6 +988,44 @@ class BatchSolver:
         """0 model, 1 shared plant, 2 per-instance plant; | 4 shared disturbance, | 8 per-instance disturbance"""
         return int(self.lib.tinympc_plant_mode(self.h))
 
+    def set_ref_trajectory(self, x_traj, u_traj=None):
+        """a reference trajectory, windowed on the device: every instance tracks a moving target of its own through a closed
+        loop, and nothing is uploaded per step.  The dimensions decide: x_traj (nx, Lx) and u_traj (nu, Lu) shared by the batch,
+        or (nx, Lx, B) and (nu, Lu, B) one trajectory per instance (the shapes of mpc_rollout's x and u: one run's log can be
+        another run's trajectory); both shared or both per instance; u_traj None: zero input references.  With the cursor c the
+        references of a solve are ref_window(x_traj, c, N) and ref_window(u_traj, c, N - 1): rows c, c+1, ... with the last
+        row held beyond the end, so any Lx, Lu >= 1 serve any number of steps.  Values are rounded to fp32 once, here.
+        A new trajectory starts at cursor 0; solve() reads the window at the cursor and leaves it; mpc_rollout(steps) reads the
+        windows at c .. c+steps-1 and leaves c+steps (see there for its route); set_ref_cursor moves it.
+        set_ref_trajectory(None) drops the trajectory: the window at the cursor stays installed as ordinary references, shared
+        or per instance, and the solver returns to the routes that serve those.  set_x_ref / set_u_ref do the same and then
+        replace their side; set_ref_sequence and set_ref_mode replace it outright; a trajectory drops a sequence.  set_precision
+        keeps the trajectory; re-batching the global solver (set_batch_size, set_gpus) drops it."""
+        if x_traj is None:
+            self._chk(self.lib.tinympc_set_ref_trajectory(self.h, None, 0, None, 0, 0), "set_ref_trajectory")
+            return
+        xf, xr, xc, uf, ur, uc, per = _traj_args(x_traj, u_traj)
+        n = self.batch if per else 1
+        if xr != self.nx or xc < 1 or xc % n != 0 or (uf is not None and (ur != self.nu or uc < 1 or uc % n != 0)) or \
+                (per and (np.shape(x_traj)[2] != n or (uf is not None and np.shape(u_traj)[2] != n))):
+            raise TinyMPCError(f"set_ref_trajectory: expected x_traj (nx, Lx) = ({self.nx}, Lx) and u_traj (nu, Lu) = ({self.nu}, Lu), or "
+                               f"(nx, Lx, batch) = ({self.nx}, Lx, {self.batch}) and (nu, Lu, batch) = ({self.nu}, Lu, {self.batch}), Lx, Lu >= 1; "
+                               f"got x_traj {np.shape(x_traj)}" + ("" if u_traj is None else f", u_traj {np.shape(u_traj)}"))
+        self._chk(self.lib.tinympc_set_ref_trajectory(self.h, _dp(xf), xc // n, None if uf is None else _dp(uf), uc // n, per),
+                  "set_ref_trajectory")
+
+    def set_ref_cursor(self, cursor):
+        """move the reference cursor (>= 0): the next solve reads the window there, the next mpc_rollout starts there"""
+        self._chk(self.lib.tinympc_set_ref_cursor(self.h, int(cursor)), "set_ref_cursor")
+
+    def ref_cursor(self):
+        """the reference cursor: 0 for a new trajectory, `steps` further on after every mpc_rollout"""
+        return int(self.lib.tinympc_ref_cursor(self.h))
+
+    def ref_trajectory_mode(self):
+        """0 no reference trajectory, 1 shared, 2 per instance"""
+        return int(self.lib.tinympc_ref_trajectory_mode(self.h))
+
     def mpc_rollout(self, steps, stream=None):
         """`steps` closed-loop MPC steps without the host in between: solve, apply u0 to the plant, solve again.  By default
         the plant is the family's own model, x+ = f + A x + B u0, and the loop is fused into one launch where the kernel has one.
@@ -927,7 +1034,12 @@ class BatchSolver:
         them — on whatever kernel such a solve takes, every kernel family, shape and precision, no switch, reference sequences
         included; two loops in a row continue the fp64 state unless x0 was set in between.  Refused there: fewer disturbance
         rows than steps, adaptive rho, set_warm_start(0), per-instance bounds without TINYMPC_HIP_STREAM_MPC.
-        With the model plant:
+        With set_ref_trajectory every step solves against its own window of the trajectory — step t of the loop against the
+        window at cursor + t, cut out on the device by one small kernel before the step's launch — and the cursor is left
+        `steps` further on, so two loops in a row continue the trajectory as they continue the state.  Such a solver takes the
+        same chain, against the model where no plant is installed, under the environment switches below too (`steps`
+        launches), with the same refusals.
+        With the model plant and no trajectory:
         (TINYMPC_HIP_LEAN_WS=1 when the solver is created: cartpole-class shapes on the lean kernel, as a chain of `steps`
         launches; with TINYMPC_HIP_LEAN_LOOP=1 beside it as one launch of its in-kernel loop — the same results.)
         Solvers on the stream / generic kernels (a horizon without a built-in entry, linear rows, cones or the affine term
