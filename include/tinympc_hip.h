@@ -147,6 +147,17 @@ int plant_mode(void);
 int set_ref_trajectory(double *x_data, int x_rows, int x_cols, double *u_data, int u_rows, int u_cols, int per_instance, int verbose);
 int set_ref_cursor(int cursor);
 int ref_cursor(void);
+/* ... and under seeded process / measurement noise drawn on the device (tinympc_set_process_noise below, which describes it):
+ * G_data nx x nx column-major, or with per_instance = 1 nx x (nx batch), instance after instance; row and column counts are
+ * checked.  G_data = NULL drops that kind.  set_noise_cursor (refused when negative) / noise_cursor move and read the one cursor
+ * both kinds share; noise_mode, get_noise and get_mpc_measured are the handle calls' forms.  Not on a set_gpus solver. */
+int set_process_noise(double *G_data, int G_rows, int G_cols, int per_instance, unsigned long long seed);
+int set_measurement_noise(double *G_data, int G_rows, int G_cols, int per_instance, unsigned long long seed);
+int set_noise_cursor(int t);
+int noise_cursor(void);
+int noise_mode(void);
+int get_noise(int which, int t0, int steps, double *buf);
+int get_mpc_measured(double *y);
 
 /* ------------------------------------------------------------------------- */
 /* (2) handle API                                                            */
@@ -360,6 +371,49 @@ int tinympc_set_ref_cursor(tinympc_solver *s, int cursor);
 int tinympc_ref_cursor(tinympc_solver *s);
 /* 0 none, 1 shared, 2 per instance */
 int tinympc_ref_trajectory_mode(tinympc_solver *s);
+/* Seeded process and measurement noise, drawn on the device: Monte-Carlo sweeps of a closed loop with nothing drawn on the host,
+ * uploaded or stored.  A draw is a pure function of (seed, kind, instance b, step t):
+ *   standard normals xi[which][b][t][i], which 0 process / 1 measurement, i < nx: Philox4x32-10 (multipliers 0xD2511F53 and
+ *   0xCD9E8D57, Weyl increments 0x9E3779B9 and 0xBB67AE85), key (seed low 32, seed high 32), counter (b low 32, b high 32, t,
+ *   (which << 16) | j) with j = i / 2; from its words w0..w3  u1 = (((w1:w0) >> 11) + 1) 2^-53 in (0, 1],
+ *   u2 = ((w3:w2) >> 11) 2^-53 in [0, 1), r = sqrt(-2 ln u1), xi[2j] = r cos(2 pi u2), xi[2j+1] = r sin(2 pi u2), all fp64 (an odd
+ *   nx drops the last sine);
+ *   the noise vector n = G xi, G nx x nx column-major fp64 — any matrix, the covariance is G G' — row r: acc = 0, then
+ *   acc = fma(G[r + i nx], xi[i], acc) for i ascending.
+ * G is shared (per_instance = 0) or [batch][nx*nx] (1); G = NULL drops that kind.  The loop: a solver with either noise is an
+ * own-plant solver (tinympc_set_plant above): tinympc_mpc_rollout is the chain of `steps` kept-workspace launches on every
+ * kernel family and precision, no environment switch, against the model or the installed plant.  With the noise cursor c and loop
+ * step s, t = c + s:
+ *   measurement noise: the solve of step s starts from (float)(x_t + G_v xi_v[b][t]), x_t the fp64 plant state, which the
+ *     measurement never contaminates;
+ *   process noise: the plant step is x+ = f_p + A_p x + B_p u0, then the uploaded disturbance if any, then one fp64 add of the
+ *     draw, last: acc = (acc + w[r]) + (G_w xi_w[b][t])[r];
+ *   the x log, the fp64 state and x0 hold the true state and its fp32 rounding: between loops x0 is the rounding of the true
+ *     state, so two loops in a row continue the state as before;
+ *   after the loop the cursor is c + steps: two loops in a row continue the noise streams.  One cursor serves both kinds; a newly
+ *     installed noise leaves it alone; a new solver has cursor 0; tinympc_set_noise_cursor moves it (t < 0 is refused).
+ *   What each step's solve started from is logged, [batch][steps][nx], while measurement noise is installed:
+ *     tinympc_get_mpc_measured (after a loop with it).
+ * tinympc_noise_mode: 1 shared / 2 per-instance process factor;  | 4 shared / | 8 per-instance measurement factor.
+ * tinympc_plant_mode is unchanged by noise.  tinympc_set_precision keeps the noise, re-batching (set_batch_size) drops it as it
+ * drops every per-instance input.  A solver without noise launches exactly what it launched before.
+ * tinympc_get_noise: the realised G xi of the steps t0 .. t0 + steps - 1 of an installed kind, [batch][steps][nx] fp64, computed
+ * on the device by the loop's own device function — as a disturbance (tinympc_set_disturbance) it reproduces the process noise
+ * bit for bit.  tinympc_host_noise: the same rule on the host, no device needed (G NULL = identity, out nx doubles);
+ * tmpc_philox4x32_10: the block function alone, on the host, for known-answer tests.
+ * Refused here: per_instance other than 0 / 1, a negative cursor.  Refused by tinympc_mpc_rollout, the error naming the
+ * condition: adaptive rho, no persistent workspace (set_warm_start(0)), per-instance bounds without TINYMPC_HIP_STREAM_MPC, a
+ * cursor that would pass INT_MAX.  The uploaded disturbance is still read from row 0 whatever the cursor.
+ * A sharded solver (set_gpus / tinympc_sharded_*) has no mpc_rollout and takes none of it. */
+int tinympc_set_process_noise(tinympc_solver *s, const double *G, int per_instance, unsigned long long seed);
+int tinympc_set_measurement_noise(tinympc_solver *s, const double *G, int per_instance, unsigned long long seed);
+int tinympc_set_noise_cursor(tinympc_solver *s, int t);
+int tinympc_noise_cursor(tinympc_solver *s);
+int tinympc_noise_mode(tinympc_solver *s);
+int tinympc_get_noise(tinympc_solver *s, int which, int t0, int steps, double *buf);
+int tinympc_get_mpc_measured(tinympc_solver *s, double *y);
+int tinympc_host_noise(unsigned long long seed, int which, long long b, int t, int nx, const double *G, double *out);
+int tmpc_philox4x32_10(const unsigned *ctr4, const unsigned *key2, unsigned *out4);
 /* Tolerance-terminated solves of big batches: with chunk_iters > 0 (rounded up to a multiple of check_termination)
  * a solve runs in chunks of that many iterations and, between chunks, gathers the instances still iterating into
  * a dense list, so that wavefronts do not idle behind their slowest instance.  Iterates, iteration counts and

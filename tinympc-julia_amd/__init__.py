@@ -107,6 +107,13 @@ from .tinympc import (  # noqa: E402,F401
     set_ref_cursor,
     ref_cursor,
     ref_window,
+    set_process_noise,
+    set_measurement_noise,
+    set_noise_cursor,
+    noise_cursor,
+    noise_mode,
+    get_noise,
+    host_noise,
     mpc_rollout,
     set_batch_size,
     set_bound_constraints,

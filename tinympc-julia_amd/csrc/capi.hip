@@ -11,6 +11,7 @@
 
 #include "../../include/tinympc_hip.h"
 #include "solver.h"
+#include "noise.h"
 
 using tmpc::set_error;
 
@@ -393,6 +394,55 @@ int tinympc_set_ref_cursor(tinympc_solver *s, int cursor) {
 }
 int tinympc_ref_cursor(tinympc_solver *s) { return s ? s->s.ref_cursor : -1; }
 int tinympc_ref_trajectory_mode(tinympc_solver *s) { return s ? s->s.traj_kind : -1; }
+static int set_noise_checked(tinympc_solver *s, const char *name, int which, const double *G, int per_instance, unsigned long long seed) {
+    if (!s) return -1;
+    if (G && per_instance != 0 && per_instance != 1) {
+        set_error(std::string(name) + ": per_instance is 0 (G nx x nx column-major, shared) or 1 (G [batch][nx*nx])");
+        return -1;
+    }
+    return guarded(name, [&] { return s->s.set_noise(which, G, per_instance, seed); });
+}
+int tinympc_set_process_noise(tinympc_solver *s, const double *G, int per_instance, unsigned long long seed) {
+    return set_noise_checked(s, "set_process_noise", tmpc::NOISE_PROCESS, G, per_instance, seed);
+}
+int tinympc_set_measurement_noise(tinympc_solver *s, const double *G, int per_instance, unsigned long long seed) {
+    return set_noise_checked(s, "set_measurement_noise", tmpc::NOISE_MEASUREMENT, G, per_instance, seed);
+}
+int tinympc_set_noise_cursor(tinympc_solver *s, int t) {
+    if (!s) return -1;
+    if (t < 0) {
+        set_error("set_noise_cursor: the cursor is the step index of the next loop's first draw, 0 or more; a negative one is refused");
+        return -1;
+    }
+    s->s.noise_cursor = t;
+    return 0;
+}
+int tinympc_noise_cursor(tinympc_solver *s) { return s ? s->s.noise_cursor : -1; }
+int tinympc_noise_mode(tinympc_solver *s) { return s ? s->s.noise_mode() : -1; }
+int tinympc_get_noise(tinympc_solver *s, int which, int t0, int steps, double *buf) {
+    if (!s) return -1;
+    return guarded("get_noise", [&] { return s->s.get_noise(which, t0, steps, buf); });
+}
+int tinympc_get_mpc_measured(tinympc_solver *s, double *y) {
+    if (!s) return -1;
+    return guarded("get_mpc_measured", [&] { return s->s.get_mpc_measured(y); });
+}
+// the draw rule on the host: csrc/noise.h, the text the device kernels compile; touches no device
+int tinympc_host_noise(unsigned long long seed, int which, long long b, int t, int nx, const double *G, double *out) {
+    if (which < 0 || which > 1 || b < 0 || t < 0 || nx < 1 || !out) {
+        set_error("host_noise: expected which 0 (process) or 1 (measurement), b >= 0, t >= 0, nx >= 1 and nx doubles of output");
+        return -1;
+    }
+    std::vector<double> xi((size_t)nx + 1);
+    for (int j = 0; 2 * j < nx; ++j) tmpc::noise_pair(seed, which, (uint64_t)b, (uint32_t)t, (uint32_t)j, xi[2 * j], xi[2 * j + 1]);
+    for (int r = 0; r < nx; ++r) out[r] = G ? tmpc::noise_row(G, nx, r, xi.data()) : xi[r];
+    return 0;
+}
+int tmpc_philox4x32_10(const unsigned *ctr4, const unsigned *key2, unsigned *out4) {
+    if (!ctr4 || !key2 || !out4) return -1;
+    tmpc::philox4x32_10(ctr4, key2, out4);
+    return 0;
+}
 int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter) {
     if (!s) return -1;
     return guarded("get_mpc_log", [&] { return s->s.get_mpc_log(x, u, iter); });
@@ -1017,6 +1067,38 @@ int plant_mode(void) {
     }
     return tinympc_plant_mode(g_solver.get());
 }
+// ... and under noise drawn on the device (tinympc_set_process_noise / _set_measurement_noise): G nx x nx column-major (shared) or
+// nx x (nx batch), instance after instance; shapes checked here.  A sharded solver takes none of it.
+static int need_unsharded(const char *what) {
+    if (need_global(what)) return -1;
+    if (g_sharded) {
+        set_error(std::string(what) + ": not available on a sharded solver (which has no mpc_rollout)");
+        return -1;
+    }
+    return 0;
+}
+static int set_noise_global(const char *what, int which, double *G_data, int G_rows, int G_cols, int per_instance, unsigned long long seed) {
+    if (need_unsharded(what)) return -1;
+    const tmpc::Solver &v = g_solver->s;
+    if (G_data && ((per_instance != 0 && per_instance != 1) || G_rows != v.nx || (long)G_cols != (long)v.nx * (per_instance ? v.batch : 1))) {
+        set_error(std::string(what) + ": expected G nx x nx (per_instance 0) or nx x (nx batch) (per_instance 1); here nx = " + std::to_string(v.nx) +
+                  ", batch = " + std::to_string(v.batch));
+        return -1;
+    }
+    return which == tmpc::NOISE_PROCESS ? tinympc_set_process_noise(g_solver.get(), G_data, per_instance, seed)
+                                        : tinympc_set_measurement_noise(g_solver.get(), G_data, per_instance, seed);
+}
+int set_process_noise(double *G_data, int G_rows, int G_cols, int per_instance, unsigned long long seed) {
+    return set_noise_global("set_process_noise", tmpc::NOISE_PROCESS, G_data, G_rows, G_cols, per_instance, seed);
+}
+int set_measurement_noise(double *G_data, int G_rows, int G_cols, int per_instance, unsigned long long seed) {
+    return set_noise_global("set_measurement_noise", tmpc::NOISE_MEASUREMENT, G_data, G_rows, G_cols, per_instance, seed);
+}
+int set_noise_cursor(int t) { return need_unsharded("set_noise_cursor") ? -1 : tinympc_set_noise_cursor(g_solver.get(), t); }
+int noise_cursor(void) { return need_unsharded("noise_cursor") ? -1 : tinympc_noise_cursor(g_solver.get()); }
+int noise_mode(void) { return need_unsharded("noise_mode") ? -1 : tinympc_noise_mode(g_solver.get()); }
+int get_noise(int which, int t0, int steps, double *buf) { return need_unsharded("get_noise") ? -1 : tinympc_get_noise(g_solver.get(), which, t0, steps, buf); }
+int get_mpc_measured(double *y) { return need_unsharded("get_mpc_measured") ? -1 : tinympc_get_mpc_measured(g_solver.get(), y); }
 // ... and along a reference trajectory (tinympc_set_ref_trajectory): x nx x Lx and u nu x Lu column-major (shared), or
 // nx x (Lx batch) and nu x (Lu batch), instance after instance — the batch rides on the column count; shapes checked here
 int set_ref_trajectory(double *x_data, int x_rows, int x_cols, double *u_data, int u_rows, int u_cols, int per_instance, int verbose) {

@@ -177,7 +177,8 @@ struct Switches {
          stream_f64 = false,                                // TINYMPC_HIP_STREAM_F64: precision 2 on the stream kernel's fp64-state form where it is built
          stream_mpc = false,                                // TINYMPC_HIP_STREAM_MPC: mpc_rollout on the stream and generic kernels (every precision), as the chain of launches
          stream_loop = false,                               // TINYMPC_HIP_STREAM_LOOP: with stream_mpc, one launch of the stream kernel's in-kernel loop where it is built
-         event_markers = false;                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
+         event_markers = false,                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
+         noise_split = false;                               // TINYMPC_HIP_NOISE_SPLIT: measurement noise by a kernel of its own ahead of every launch (timing aid)
     int mfmac_debug = 0;    // timing probe builds only
     int fold_slots = -1;    // TINYMPC_HIP_FOLD_SLOTS = n: the status fold's records for the first n workgroups only (at most
                             // GSLOT_DEFAULT_CAP; 0: none, the accumulator path for all — the A/B switch); unset: all of them
@@ -440,13 +441,33 @@ struct Solver {
     std::vector<double> own_A, own_B, own_f, dist_w;
     double *d_own_plant = nullptr, *d_dist = nullptr;
     bool own_plant_dirty = true;
-    bool own_plant() const { return plant_kind != 0 || dist_kind != 0; }
+    bool own_plant() const { return plant_kind != 0 || dist_kind != 0 || noisy(); }
     bool own_plant_per_instance() const { return plant_kind == 2 || (plant_kind == 0 && hetero); }
     int plant_mode() const { return plant_kind | (dist_kind == 1 ? 4 : (dist_kind == 2 ? 8 : 0)); }
     int set_plant(const double *A_, const double *B_, const double *f_, int per_instance);
     int set_disturbance(const double *w, int steps, int per_instance);
     void drop_own_plant();   // both pieces (a re-batch)
     int ensure_own_plant();
+    // Seeded process and measurement noise drawn on the device (tinympc_set_process_noise / _set_measurement_noise; the draw rule:
+    // noise.h).  Index 0 process, 1 measurement; noise_kind 0: none, 1: a shared factor, 2: one per instance.  The factors G (nx x nx
+    // column-major fp64, or [batch][nx*nx]) are kept as given on the host and the device; a draw is a pure function of (seed, kind,
+    // instance, step t), t = noise_cursor + loop step, so nothing else is stored.  Either kind makes the solver an own-plant solver:
+    // the solve of step t starts from (float)(x_t + G_v xi_v[b][t]) — logged in d_mpc_y [batch][steps][nx], allocated only while
+    // measurement noise is installed — and the plant step ends with (acc + w) + (G_w xi_w[b][t]) (plant_step_noise_kernel); x0d, the
+    // x log and x0 after the loop hold the true state.  One cursor serves both kinds; a loop leaves it steps further on.
+    int noise_kind[2] = {0, 0};
+    unsigned long long noise_seed[2] = {0, 0};
+    int noise_cursor = 0;
+    std::vector<double> noise_G[2];
+    double *d_noise_G[2] = {nullptr, nullptr};
+    float *d_mpc_y = nullptr;
+    int mpc_y_cap = 0, mpc_y_steps = 0;   // steps allocated; steps of the loop that wrote it (0: none)
+    bool noisy() const { return noise_kind[0] != 0 || noise_kind[1] != 0; }
+    int noise_mode() const { return noise_kind[0] | (noise_kind[1] == 1 ? 4 : (noise_kind[1] == 2 ? 8 : 0)); }
+    int set_noise(int which, const double *G, int per_instance, unsigned long long seed);
+    void drop_noise();   // both kinds (a re-batch)
+    int get_noise(int which, int t0, int steps, double *buf);
+    int get_mpc_measured(double *y);
     // A reference trajectory (tinympc_set_ref_trajectory): x_traj Lx rows of nx and optionally u_traj Lu rows of nu, shared or
     // [batch][L][n] per instance, rounded to fp32 once when set; the references of a solve are its window at the cursor,
     // x_ref[k] = x_traj[min(c + k, Lx - 1)], u_ref[k] = u_traj[min(c + k, Lu - 1)] (no u_traj: zero).  traj_kind 0: none, 1: shared,

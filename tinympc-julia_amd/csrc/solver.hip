@@ -1,6 +1,7 @@
 // Host side of the batched solver: device memory, pack uploads, launches.
 #include "solver.h"
 #include "admm_generic.hip.h"   // Ws64 (layout of the precision-2 workspace)
+#include "noise.h"              // the draw rule of the closed loop's noise (host and device)
 
 #include <climits>
 #include <cmath>
@@ -152,6 +153,8 @@ Solver::~Solver() {
     dev_free(d_dist);
     dev_free(d_xtraj);
     dev_free(d_utraj);
+    dev_free(d_noise_G[0]);
+    dev_free(d_noise_G[1]);
     if (h_gstat) (void)hipHostFree(h_gstat);
     h_gstat = nullptr;
     for (hipEvent_t e : ev_ring)
@@ -241,6 +244,8 @@ void Solver::free_batch() {
     dev_free(d_mpc_x);
     dev_free(d_mpc_u);
     dev_free(d_mpc_iter);
+    dev_free(d_mpc_y);
+    mpc_y_steps = 0;
     dev_free(d_xref_seq);
     dev_free(d_uref_seq);
     ref_seq_steps = 0;
@@ -367,6 +372,7 @@ Switches read_switches() {
     w.stream_mpc = on("TINYMPC_HIP_STREAM_MPC");
     w.stream_loop = on("TINYMPC_HIP_STREAM_LOOP");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
+    w.noise_split = on("TINYMPC_HIP_NOISE_SPLIT");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     if (const char *f = std::getenv("TINYMPC_HIP_FOLD_SLOTS")) w.fold_slots = std::max(0, std::atoi(f));
     return w;
@@ -572,6 +578,7 @@ int Solver::alloc_batch(int batch_) {
     drop_instance_bounds();   // (per-instance inputs do not survive a re-batch: back to the shared bounds)
     drop_own_plant();         // (... and back to the model plant)
     (void)drop_ref_trajectory(false);   // (... and to the references set below)
+    drop_noise();             // (... and no noise: a factor may be per instance)
     batch = batch_;
     if (select_kernel()) return -1;
     const size_t Bn = (size_t)batch, EX = (size_t)ex(), EU = (size_t)eu();
@@ -1206,9 +1213,13 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
             return refuse("mpc_rollout: the disturbance holds " + std::to_string(dist_steps) + " steps, the loop asks for " + std::to_string(mpc_steps) +
                           " (one row per step, read from row 0)");
         if (st.adaptive_rho)
-            return refuse(own_plant() ? "mpc_rollout: a plant of its own / a disturbance is not available with adaptive rho"
-                                      : "mpc_rollout: a reference trajectory is not available with adaptive rho");
+            return refuse(noisy() ? "mpc_rollout: process / measurement noise is not available with adaptive rho"
+                                  : (own_plant() ? "mpc_rollout: a plant of its own / a disturbance is not available with adaptive rho"
+                                                 : "mpc_rollout: a reference trajectory is not available with adaptive rho"));
         if (!warm_start) return refuse("mpc_rollout needs the persistent workspace (set_warm_start(1))");
+        if (noisy() && noise_cursor > INT_MAX - mpc_steps)
+            return refuse("mpc_rollout: the noise cursor would pass the largest int (the step index is one 32-bit word of the generator's counter; "
+                          "set_noise_cursor, or another seed, starts a fresh stream)");
         if (traj_kind && ref_cursor > INT_MAX - mpc_steps)
             return refuse("mpc_rollout: the reference cursor would pass the largest int (set_ref_cursor: every cursor from the longer trajectory's last row on gives the same window)");
         if (select_kernel(false) || ensure_extension_buffers()) return rp;
@@ -1777,27 +1788,205 @@ int Solver::ensure_own_plant() {
     return 0;
 }
 
+// ---- noise drawn on the device (tinympc_set_process_noise / _set_measurement_noise; the rule: noise.h) ----
+// The three kernels share plant_step_own_kernel's layout — 256 / nx instances per workgroup, lane (instance, r) owns row r — and
+// one way to the noise vector: the lanes r < ceil(nx / 2) of an instance draw its pair r (one Philox block and one Box-Muller
+// each, nothing drawn twice) into the workgroup's LDS, and after the barrier every lane takes its row of G xi (noise_row).
+// G: instance b's factor at G + b * g_stride (0: shared).  Every lane of the workgroup reaches the barrier.
+__device__ inline double noise_block_row(double *xi, const double *G, long g_stride, unsigned long long seed, int which, long b, unsigned t,
+                                         int nx, int r, bool on) {
+    double *mine = xi + ((int)threadIdx.x / nx) * nx;
+    if (on && 2 * r < nx) {
+        double even, odd;
+        noise_pair(seed, which, (uint64_t)b, t, (uint32_t)r, even, odd);
+        mine[2 * r] = even;
+        if (2 * r + 1 < nx) mine[2 * r + 1] = odd;
+    }
+    __syncthreads();
+    return on ? noise_row(G + b * g_stride, nx, r, mine) : 0.0;
+}
+
+// tinympc_get_noise: out[b][s][r] = (G xi[which][b][t0 + s])[r]; workgroup = (step s, 256 / nx instances)
+__global__ void noise_fill_kernel(double *out, const double *G, long g_stride, unsigned long long seed, int which, int nx, long batch, int steps,
+                                  int t0) {
+    __shared__ double xi[256];
+    const int per_block = (int)blockDim.x / nx, t = (int)threadIdx.x, r = t % nx;
+    const long groups = (batch + per_block - 1) / per_block, s = (long)blockIdx.x / groups;
+    const long b = ((long)blockIdx.x - s * groups) * per_block + t / nx;
+    const bool on = t < per_block * nx && b < batch;
+    const double n = noise_block_row(xi, G, g_stride, seed, which, b, (unsigned)(t0 + (int)s), nx, r, on);
+    if (on) out[(b * steps + s) * nx + r] = n;
+}
+
+// The measurement a step's solve starts from: x0 = ylog[b][step] = (float)(x0d + G_v xi_v[b][t]); x0d, the true state, is read only
+__global__ void measure_kernel(float *x0, float *ylog, const double *x0d, const double *G, long g_stride, unsigned long long seed, int nx, long batch,
+                               int steps, int step, int t) {
+    __shared__ double xi[256];
+    const int per_block = (int)blockDim.x / nx, lane = (int)threadIdx.x, r = lane % nx;
+    const long b = (long)blockIdx.x * per_block + lane / nx;
+    const bool on = lane < per_block * nx && b < batch;
+    const double n = noise_block_row(xi, G, g_stride, seed, NOISE_MEASUREMENT, b, (unsigned)t, nx, r, on);
+    if (!on) return;
+    const float y = (float)(x0d[b * nx + r] + n);
+    x0[b * nx + r] = y;
+    ylog[(b * steps + step) * nx + r] = y;
+}
+
+// plant_step_own_kernel's rule with noise: row r is acc = f_p[r], A_p's row, B_p's row (one fma each), then the uploaded
+// disturbance if any, then the process draw last — acc = (acc + w[r]) + (G_w xi_w[b][t])[r] (Gw null: none); x0d = acc and
+// mpc_x = (float)acc, the true state.  x0 = (float)acc too, unless Gv is given: then x0 and ylog[b][step + 1] take the NEXT
+// step's measurement (float)(acc + (G_v xi_v[b][t + 1])[r]), what measure_kernel would write ahead of that step's launch.
+__global__ void plant_step_noise_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved, const double *plant,
+                                        long plant_stride, const double *w, long w_stride, float *mpc_x, float *mpc_u, int *mpc_iter,
+                                        const double *Gw, long gw_stride, unsigned long long seed_w, const double *Gv, long gv_stride,
+                                        unsigned long long seed_v, float *ylog, int nx, int nu, int N, long batch, int steps, int step, int t) {
+    __shared__ double xi_w[256], xi_v[256];
+    const int per_block = (int)blockDim.x / nx, lane = (int)threadIdx.x, r = lane % nx;
+    const long b = (long)blockIdx.x * per_block + lane / nx;
+    const bool on = lane < per_block * nx && b < batch;
+    double acc = 0.0;
+    if (on) {
+        const double *A = plant + b * plant_stride, *Bm = A + nx * nx;
+        const float *u0 = uout + b * (long)nu * (N - 1);
+        acc = Bm[nx * nu + r];
+        for (int j = 0; j < nx; ++j) acc = fma(A[r + j * nx], x0d[b * nx + j], acc);
+        for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
+        if (w) acc = acc + w[b * w_stride + r];
+    }
+    if (Gw) acc = acc + noise_block_row(xi_w, Gw, gw_stride, seed_w, NOISE_PROCESS, b, (unsigned)t, nx, r, on);
+    double next = acc;
+    if (Gv) next = acc + noise_block_row(xi_v, Gv, gv_stride, seed_v, NOISE_MEASUREMENT, b, (unsigned)t + 1u, nx, r, on);
+    __syncthreads();   // (every row has read x0d)
+    if (!on) return;
+    const long so = b * steps + step;
+    x0d[b * nx + r] = acc;
+    x0[b * nx + r] = (float)next;
+    mpc_x[so * nx + r] = (float)acc;
+    if (Gv) ylog[(so + 1) * nx + r] = (float)next;
+    for (int a = r; a < nu; a += nx) mpc_u[so * nu + a] = uout[b * (long)nu * (N - 1) + a];
+    if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
+}
+
 // An own-plant solver's chain: per step the solver's ordinary kept-workspace launch — from the fp32 rounding in d_x0, Pass::x0d
 // null, what a host-stepped loop launches — and plant_step_own_kernel, stream-ordered; the fp64 state resumed as the stream chain's
 // With a reference trajectory every launch is handed its step's window first (ref_window_kernel, where the window on the device
 // is another), and the cursor is left mpc_steps further on.
+// With noise (tinympc_set_process_noise / _set_measurement_noise) the step is plant_step_noise_kernel instead, t = noise cursor +
+// step: it adds the process draw last, and — measurement noise — also writes the NEXT step's measurement into x0 (and the y log),
+// so only step 0's comes from measure_kernel ahead of the first launch; the last step leaves the true state's rounding in x0.
+// TINYMPC_HIP_NOISE_SPLIT (timing aid): measure_kernel ahead of every launch, the same values.  The noise cursor is left
+// mpc_steps further on.  Without noise: exactly the launches above.
 int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
     if (ensure_own_plant() || plant_start(stream, true)) return -1;
     const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
     const long blk = (long)nx * nx + (long)nx * nu + nx;
+    const unsigned step_groups = (unsigned)((batch + per_block - 1) / per_block);
+    const bool measured = noise_kind[NOISE_MEASUREMENT] != 0;
+    const long gw_stride = noise_kind[NOISE_PROCESS] == 2 ? (long)nx * nx : 0L, gv_stride = noise_kind[NOISE_MEASUREMENT] == 2 ? (long)nx * nx : 0L;
+    if (measured) {
+        if (mpc_y_cap < mpc_steps) {
+            if (dev_alloc(d_mpc_y, (size_t)batch * mpc_steps * nx)) return -1;
+            mpc_y_cap = mpc_steps;
+        }
+        mpc_y_steps = mpc_steps;
+    }
     Pass pass = whole_batch(false, true);
     for (int step = 0; step < mpc_steps; ++step) {
         if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
         if (traj_kind && ensure_ref_window(stream, ref_cursor + step)) return -1;
+        if (measured && (step == 0 || sw.noise_split))
+            measure_kernel<<<step_groups, 256, 0, stream>>>(d_x0, d_mpc_y, d_x0d, d_noise_G[NOISE_MEASUREMENT], gv_stride, noise_seed[NOISE_MEASUREMENT], nx,
+                                                            (long)batch, mpc_steps, step, noise_cursor + step);
         if (launch_pass(stream, pass)) return -1;
-        plant_step_own_kernel<<<(unsigned)((batch + per_block - 1) / per_block), 256, 0, stream>>>(
-            d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L,
-            dist_kind ? d_dist + (size_t)step * nx : nullptr, dist_kind == 2 ? (long)dist_steps * nx : 0L, d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N,
-            (long)batch, mpc_steps, step);
+        const double *w = dist_kind ? d_dist + (size_t)step * nx : nullptr;
+        const long w_stride = dist_kind == 2 ? (long)dist_steps * nx : 0L;
+        if (!noisy())
+            plant_step_own_kernel<<<step_groups, 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L,
+                                                                   w, w_stride, d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N, (long)batch, mpc_steps, step);
+        else
+            plant_step_noise_kernel<<<step_groups, 256, 0, stream>>>(
+                d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L, w, w_stride, d_mpc_x, d_mpc_u, d_mpc_iter,
+                d_noise_G[NOISE_PROCESS], gw_stride, noise_seed[NOISE_PROCESS], measured && !sw.noise_split && step + 1 < mpc_steps ? d_noise_G[NOISE_MEASUREMENT] : nullptr,
+                gv_stride, noise_seed[NOISE_MEASUREMENT], d_mpc_y, nx, nu, N, (long)batch, mpc_steps, step, noise_cursor + step);
     }
     HIP_TRY(hipGetLastError());
     if (traj_kind) ref_cursor += mpc_steps;   // (plan_rollout checked the sum)
+    if (noisy()) noise_cursor += mpc_steps;   // (likewise)
     return record_done(stream);
+}
+
+// ---- noise: set, drop, read back (the kernels are above the chain) ----
+// G: nx x nx column-major fp64, or [batch][nx*nx]; null drops that kind.  The cursor stays where it is.
+int Solver::set_noise(int which, const double *G, int per_instance, unsigned long long seed) {
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;   // (a chain still running reads the factor)
+    if (!G) {
+        noise_kind[which] = 0;
+        noise_G[which].clear();
+        dev_free(d_noise_G[which]);
+        if (which == NOISE_MEASUREMENT) {
+            dev_free(d_mpc_y);
+            mpc_y_cap = mpc_y_steps = 0;
+        }
+        if (!own_plant()) dev_free(d_own_plant), own_plant_dirty = true;
+        return 0;
+    }
+    const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)nx * nx;
+    noise_G[which].assign(G, G + n);
+    if (dev_alloc(d_noise_G[which], n)) return -1;
+    HIP_TRY(hipMemcpy(d_noise_G[which], noise_G[which].data(), n * sizeof(double), hipMemcpyHostToDevice));
+    noise_kind[which] = per_instance ? 2 : 1;
+    noise_seed[which] = seed;
+    return 0;
+}
+
+void Solver::drop_noise() {
+    if (!noisy()) return;
+    (void)wait_last_launch();
+    for (int k = 0; k < 2; ++k) {
+        noise_kind[k] = 0;
+        noise_G[k].clear();
+        dev_free(d_noise_G[k]);
+    }
+    dev_free(d_mpc_y);
+    mpc_y_cap = mpc_y_steps = 0;
+    if (!own_plant()) dev_free(d_own_plant), own_plant_dirty = true;
+}
+
+// the realised G xi of the steps t0 .. t0 + steps - 1, [batch][steps][nx] fp64, by noise_fill_kernel: the device function of the loop
+int Solver::get_noise(int which, int t0, int steps, double *buf) {
+    if (which < 0 || which > 1 || !noise_kind[which]) {
+        set_error("get_noise: which is 0 (process) or 1 (measurement), and that kind has to be installed (set_process_noise / set_measurement_noise)");
+        return -1;
+    }
+    const size_t per_block = 256 / nx, groups = (batch + per_block - 1) / per_block;
+    if (t0 < 0 || steps < 1 || t0 > INT_MAX - steps || !buf || groups * (size_t)steps > 0x7fffffffu) {
+        set_error("get_noise: expected t0 >= 0, steps >= 1, t0 + steps within an int, and a buffer of batch * steps * nx doubles");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;
+    double *d_out = nullptr;
+    const size_t n = (size_t)batch * steps * nx;
+    if (dev_alloc(d_out, n)) return -1;
+    noise_fill_kernel<<<(unsigned)(groups * steps), 256>>>(d_out, d_noise_G[which], noise_kind[which] == 2 ? (long)nx * nx : 0L, noise_seed[which], which, nx,
+                                                           (long)batch, steps, t0);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(buf, d_out, n * sizeof(double), hipMemcpyDeviceToHost);
+    dev_free(d_out);
+    HIP_TRY(e);
+    return 0;
+}
+
+// what every step's solve of the last loop started from, [batch][steps][nx] (measurement noise installed)
+int Solver::get_mpc_measured(double *y) {
+    if (!noise_kind[NOISE_MEASUREMENT] || mpc_steps_last <= 0 || mpc_y_steps != mpc_steps_last || !y) {
+        set_error("get_mpc_measured: no mpc_rollout with measurement noise has run (set_measurement_noise, then mpc_rollout)");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;
+    return d2h_double(d_mpc_y, y, (size_t)batch * mpc_steps_last * nx);
 }
 
 // The references of one solve cut out of a reference trajectory (tinympc_set_ref_trajectory): the window at `cursor`,

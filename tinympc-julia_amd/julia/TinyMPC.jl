@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_instance_bounds,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_instance_bounds,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -249,6 +249,11 @@ function mpc_rollout(solver::TinyMPCSolver, steps::Integer)
     x, u, it = zeros(nx, steps, B), zeros(nu, steps, B), zeros(Int32, steps, B)
     st = ccall((:mpc_rollout, _lib_path()), Int32, (Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), steps, x, u, it)
     st < 0 && error("mpc_rollout failed ($(_last_error()))")
+    if ccall((:noise_mode, _lib_path()), Int32, ()) >= 4      # measurement noise installed: what every step's solve started from
+        y = zeros(nx, steps, B)
+        _ok(ccall((:get_mpc_measured, _lib_path()), Int32, (Ptr{Float64},), y), "Failed to get the measured states")
+        return (status=st, x=x, u=u, iter=it, y=y)
+    end
     return (status=st, x=x, u=u, iter=it)
 end
 
@@ -290,6 +295,76 @@ function plant_mode(solver::TinyMPCSolver)
     m = ccall((:plant_mode, _lib_path()), Int32, ())
     m < 0 && error("plant_mode failed ($(_last_error()))")
     return Int(m)
+end
+
+# Seeded process and measurement noise, drawn on the device: Monte-Carlo sweeps of mpc_rollout with nothing drawn on the host or
+# uploaded.  A draw is a pure function of (seed, kind, instance, step): Philox4x32-10 and Box-Muller give nx standard normals xi, the
+# noise vector is G xi (include/tinympc_hip.h states the rule; the covariance is G G').  G (nx, nx) shared, (nx, nx, batch) one
+# factor per instance, a vector (nx,) is diag(sigma); nothing drops that kind.  With the noise cursor c (0-based) and loop step s,
+# t = c + s: measurement noise — the solve of step s starts from Float32(x_t + G_v xi_v[b][t]), the fp64 plant state x_t is never
+# contaminated; process noise — the plant step ends with + G_w xi_w[b][t], after the uploaded disturbance if any.  mpc_rollout
+# then runs as the chain of `steps` kept-workspace launches (every shape and precision, no environment switch), leaves the cursor
+# at c + steps, and returns y (nx, steps, batch), what every solve started from, while measurement noise is installed.  One cursor
+# serves both kinds; a newly installed noise leaves it alone.  Not with adaptive rho, not on a sharded solver (set_gpus > 1).
+# (Written against the C-ABI like the rest of this file, not executed here.)
+_noise_factor(G::Array{Float64}) = ndims(G) == 1 ? [i == j ? G[i] : 0.0 for i in eachindex(G), j in eachindex(G)] : G
+
+function set_process_noise(solver::TinyMPCSolver, G::Union{Array{Float64},Nothing}, seed::Integer=0)
+    _need(solver)
+    G === nothing && return _ok(ccall((:set_process_noise, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Int32, UInt64), C_NULL, 0, 0, 0, 0),
+                                "Failed to drop the process noise")
+    M = _noise_factor(G)
+    _ok(ccall((:set_process_noise, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Int32, UInt64),
+              M, size(M, 1), div(length(M), size(M, 1)), ndims(M) == 3 ? 1 : 0, UInt64(seed)), "Failed to set the process noise")
+end
+
+function set_measurement_noise(solver::TinyMPCSolver, G::Union{Array{Float64},Nothing}, seed::Integer=0)
+    _need(solver)
+    G === nothing && return _ok(ccall((:set_measurement_noise, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Int32, UInt64), C_NULL, 0, 0, 0, 0),
+                                "Failed to drop the measurement noise")
+    M = _noise_factor(G)
+    _ok(ccall((:set_measurement_noise, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Int32, UInt64),
+              M, size(M, 1), div(length(M), size(M, 1)), ndims(M) == 3 ? 1 : 0, UInt64(seed)), "Failed to set the measurement noise")
+end
+
+# the noise cursor (0-based step index of the next loop's first draw): 0 for a new solver, `steps` further on after every
+# mpc_rollout of a solver with noise; a negative cursor is refused
+function set_noise_cursor(solver::TinyMPCSolver, t::Integer)
+    _need(solver)
+    _ok(ccall((:set_noise_cursor, _lib_path()), Int32, (Int32,), t), "Failed to set the noise cursor")
+end
+
+function noise_cursor(solver::TinyMPCSolver)
+    _need(solver)
+    c = ccall((:noise_cursor, _lib_path()), Int32, ())
+    c < 0 && error("noise_cursor failed ($(_last_error()))")
+    return Int(c)
+end
+
+# 1 shared / 2 per-instance process factor; + 4 shared / + 8 per-instance measurement factor
+function noise_mode(solver::TinyMPCSolver)
+    _need(solver)
+    m = ccall((:noise_mode, _lib_path()), Int32, ())
+    m < 0 && error("noise_mode failed ($(_last_error()))")
+    return Int(m)
+end
+
+# the realised noise vectors G xi of kind `which` (0 process, 1 measurement) at the steps t0 .. t0 + steps - 1, computed on the
+# device by the loop's own device function: (nx, steps, batch)
+function get_noise(solver::TinyMPCSolver, which::Integer, t0::Integer, steps::Integer)
+    _need(solver)
+    buf = zeros(solver.nx, steps, solver.batch)
+    _ok(ccall((:get_noise, _lib_path()), Int32, (Int32, Int32, Int32, Ptr{Float64}), which, t0, steps, buf), "Failed to get the noise")
+    return buf
+end
+
+# the draw rule on the host (no device needed): G (nx, nx), or nothing for the identity; b and t 0-based
+function host_noise(seed::Integer, which::Integer, b::Integer, t::Integer, nx::Integer, G::Union{Matrix{Float64},Nothing}=nothing)
+    out = zeros(nx)
+    rc = ccall((:tinympc_host_noise, _lib_path()), Int32, (UInt64, Int32, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+               UInt64(seed), which, b, t, nx, G === nothing ? C_NULL : G, out)
+    rc != 0 && error("host_noise failed ($(_last_error()))")
+    return out
 end
 
 # A reference trajectory, windowed on the device: every instance tracks a moving target of its own through mpc_rollout, and nothing

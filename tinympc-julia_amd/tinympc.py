@@ -30,6 +30,8 @@ c_ip = ctypes.POINTER(ctypes.c_int)
 c_int = ctypes.c_int
 c_dbl = ctypes.c_double
 c_vp = ctypes.c_void_p
+c_ull = ctypes.c_ulonglong
+c_up = ctypes.POINTER(ctypes.c_uint)
 
 
 class TinyMPCError(RuntimeError):
@@ -128,6 +130,22 @@ SIGNATURES = {
     "set_ref_trajectory": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_int, c_int, c_int]),
     "set_ref_cursor": (c_int, [c_int]),
     "ref_cursor": (c_int, []),
+    "tinympc_set_process_noise": (c_int, [c_vp, c_dp, c_int, c_ull]),
+    "tinympc_set_measurement_noise": (c_int, [c_vp, c_dp, c_int, c_ull]),
+    "tinympc_set_noise_cursor": (c_int, [c_vp, c_int]),
+    "tinympc_noise_cursor": (c_int, [c_vp]),
+    "tinympc_noise_mode": (c_int, [c_vp]),
+    "tinympc_get_noise": (c_int, [c_vp, c_int, c_int, c_int, c_dp]),
+    "tinympc_get_mpc_measured": (c_int, [c_vp, c_dp]),
+    "tinympc_host_noise": (c_int, [c_ull, c_int, ctypes.c_longlong, c_int, c_int, c_dp, c_dp]),
+    "tmpc_philox4x32_10": (c_int, [c_up, c_up, c_up]),
+    "set_process_noise": (c_int, [c_dp, c_int, c_int, c_int, c_ull]),
+    "set_measurement_noise": (c_int, [c_dp, c_int, c_int, c_int, c_ull]),
+    "set_noise_cursor": (c_int, [c_int]),
+    "noise_cursor": (c_int, []),
+    "noise_mode": (c_int, []),
+    "get_noise": (c_int, [c_int, c_int, c_int, c_dp]),
+    "get_mpc_measured": (c_int, [c_dp]),
     "tinympc_set_profiling": (c_int, [c_vp, c_int]),
     "tinympc_set_compaction": (c_int, [c_vp, c_int]),
     "tinympc_set_adaptive_rho": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_int]),
@@ -440,6 +458,95 @@ def plant_mode(solver):
     return m
 
 
+NOISE_PROCESS, NOISE_MEASUREMENT = 0, 1
+
+
+def _noise_factor(G, what):
+    """(flat column-major G, rows, columns, per_instance) of a noise factor: (nx, nx), (nx, nx, B), or (nx,) = diag(sigma)"""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim == 1:
+        G = np.diag(G)
+    if G.ndim not in (2, 3) or G.shape[0] < 1 or G.shape[0] != G.shape[1]:
+        raise TinyMPCError(f"{what}: expected G (nx, nx), (nx, nx, batch) or sigma (nx,) for diag(sigma); got {G.shape}")
+    Gf = _flat_f(G)
+    return Gf, G.shape[0], Gf.size // G.shape[0], 1 if G.ndim == 3 else 0
+
+
+def _set_noise_global(solver, which, G, seed):
+    _need_setup(solver)
+    lib = load_library()
+    name = "set_process_noise" if which == NOISE_PROCESS else "set_measurement_noise"
+    fn = getattr(lib, name)
+    if G is None:
+        rc = fn(None, 0, 0, 0, 0)
+    else:
+        Gf, rows, cols, per = _noise_factor(G, name)
+        rc = fn(_dp(Gf), rows, cols, per, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    if rc != 0:
+        raise TinyMPCError(f"{name} failed ({_err()})")
+
+
+def set_process_noise(solver, G, seed=0):
+    """seeded process noise of the global solver's closed loops, drawn on the device (see BatchSolver.set_process_noise): G (nx, nx)
+    shared, (nx, nx, B) per instance, (nx,) = diag(sigma); None drops it.  Not on a set_gpus solver"""
+    _set_noise_global(solver, NOISE_PROCESS, G, seed)
+
+
+def set_measurement_noise(solver, G, seed=0):
+    """seeded measurement noise of the global solver's closed loops (see BatchSolver.set_measurement_noise); None drops it"""
+    _set_noise_global(solver, NOISE_MEASUREMENT, G, seed)
+
+
+def set_noise_cursor(solver, t):
+    """move the global solver's noise cursor (>= 0): the step index the next mpc_rollout's first draw carries"""
+    _need_setup(solver)
+    if load_library().set_noise_cursor(int(t)) != 0:
+        raise TinyMPCError(f"Failed to set the noise cursor ({_err()})")
+
+
+def noise_cursor(solver):
+    """the global solver's noise cursor: 0 for a new solver, `steps` further on after every mpc_rollout of a solver with noise"""
+    _need_setup(solver)
+    c = int(load_library().noise_cursor())
+    if c < 0:
+        raise TinyMPCError(f"noise_cursor failed ({_err()})")
+    return c
+
+
+def noise_mode(solver):
+    """1 shared / 2 per-instance process factor; | 4 shared / | 8 per-instance measurement factor"""
+    _need_setup(solver)
+    m = int(load_library().noise_mode())
+    if m < 0:
+        raise TinyMPCError(f"noise_mode failed ({_err()})")
+    return m
+
+
+def get_noise(solver, which, t0, steps):
+    """the realised noise vectors G xi of the global solver's steps t0 .. t0 + steps - 1, computed on the device: (nx, steps, B)"""
+    _need_setup(solver)
+    buf = np.zeros(solver.nx * int(steps) * solver.batch)
+    if load_library().get_noise(int(which), int(t0), int(steps), _dp(buf)) != 0:
+        raise TinyMPCError(f"get_noise failed ({_err()})")
+    return buf.reshape((solver.nx, int(steps), solver.batch), order="F")
+
+
+def host_noise(seed, which, b, t, nx, G=None):
+    """THE DRAW RULE on the host (csrc/noise.h, the text the device kernels compile; no device needed): the noise vector G xi of
+    kind `which` (0 process, 1 measurement), instance b, step t — xi the nx standard normals Philox4x32-10 and Box-Muller give for
+    (seed, which, b, t); G (nx, nx), or (nx,) = diag(sigma), or None = identity.  Returns (nx,) fp64."""
+    out = np.zeros(int(nx))
+    Gf = None
+    if G is not None:
+        Gf, rows, cols, per = _noise_factor(G, "host_noise")
+        if rows != nx or cols != nx or per:
+            raise TinyMPCError(f"host_noise: expected G ({nx}, {nx}) or sigma ({nx},); got {np.shape(G)}")
+    rc = load_library().tinympc_host_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(which), int(b), int(t), int(nx), None if Gf is None else _dp(Gf), _dp(out))
+    if rc != 0:
+        raise TinyMPCError(f"host_noise failed ({_err()})")
+    return out
+
+
 def ref_window(traj, cursor, knots):
     """THE WINDOW RULE of a reference trajectory, in numpy: the references of a solve with the cursor at `cursor` are the `knots`
     rows  traj[min(cursor + k, L - 1)], k = 0 .. knots-1  — a sliding window, the last row held beyond the end, so any L >= 1
@@ -501,17 +608,26 @@ def ref_cursor(solver):
 def mpc_rollout(solver, steps):
     """`steps` closed-loop steps on the global solver — solve, then the plant step x+ = f + A x + B u0 of the model, or of the plant
     set_plant installed, plus the disturbance of set_disturbance; with set_ref_trajectory every step against its own window of the
-    trajectory, the cursor left `steps` further on: dict(status, x (nx, steps, B), u (nu, steps, B), iter, solved)"""
+    trajectory, the cursor left `steps` further on; with set_process_noise / set_measurement_noise under noise drawn on the device:
+    dict(status, x (nx, steps, B), u (nu, steps, B), iter, solved), and y (nx, steps, B) — what every step's solve started from —
+    only while measurement noise is installed"""
     _need_setup(solver)
     nx, nu, B = solver.nx, solver.nu, solver.batch
     x, u = np.zeros(nx * steps * B), np.zeros(nu * steps * B)
     it = np.zeros(steps * B, dtype=np.int32)
-    st = int(load_library().mpc_rollout(int(steps), _dp(x), _dp(u), it.ctypes.data_as(c_ip)))
+    lib = load_library()
+    st = int(lib.mpc_rollout(int(steps), _dp(x), _dp(u), it.ctypes.data_as(c_ip)))
     if st < 0:
         raise TinyMPCError(f"mpc_rollout failed ({_err()})")
     it = it.reshape((steps, B), order="F")
-    return dict(status=st, x=x.reshape((nx, steps, B), order="F"), u=u.reshape((nu, steps, B), order="F"),
-                iter=np.abs(it), solved=(it > 0).astype(np.int32))
+    out = dict(status=st, x=x.reshape((nx, steps, B), order="F"), u=u.reshape((nu, steps, B), order="F"),
+               iter=np.abs(it), solved=(it > 0).astype(np.int32))
+    if max(0, int(lib.noise_mode())) & 12:
+        y = np.zeros(nx * steps * B)
+        if lib.get_mpc_measured(_dp(y)) != 0:
+            raise TinyMPCError(f"get_mpc_measured failed ({_err()})")
+        out["y"] = y.reshape((nx, steps, B), order="F")
+    return out
 
 
 def reset_workspace(solver):
@@ -1039,7 +1155,11 @@ class BatchSolver:
         `steps` further on, so two loops in a row continue the trajectory as they continue the state.  Such a solver takes the
         same chain, against the model where no plant is installed, under the environment switches below too (`steps`
         launches), with the same refusals.
-        With the model plant and no trajectory:
+        With set_process_noise / set_measurement_noise the same chain again, with noise drawn on the device: the solve of step t
+        starts from float32(x_t + G_v xi_v[b][t]) and the plant step ends with + G_w xi_w[b][t], t = noise cursor + loop step;
+        the cursor is left `steps` further on, and the dict gains y (nx, steps, B), what every solve started from, while
+        measurement noise is installed.  Refused there too: a cursor that would pass the largest int.
+        With the model plant, no trajectory and no noise:
         (TINYMPC_HIP_LEAN_WS=1 when the solver is created: cartpole-class shapes on the lean kernel, as a chain of `steps`
         launches; with TINYMPC_HIP_LEAN_LOOP=1 beside it as one launch of its in-kernel loop — the same results.)
         Solvers on the stream / generic kernels (a horizon without a built-in entry, linear rows, cones or the affine term
@@ -1057,8 +1177,64 @@ class BatchSolver:
         it = np.zeros(steps * B, dtype=np.int32)
         self._chk(self.lib.tinympc_get_mpc_log(self.h, _dp(x), _dp(u), it.ctypes.data_as(c_ip)), "get_mpc_log")
         it = it.reshape((steps, B), order="F")
-        return dict(status=st, x=x.reshape((nx, steps, B), order="F"), u=u.reshape((nu, steps, B), order="F"),
-                    iter=np.abs(it), solved=(it > 0).astype(np.int32))
+        out = dict(status=st, x=x.reshape((nx, steps, B), order="F"), u=u.reshape((nu, steps, B), order="F"),
+                   iter=np.abs(it), solved=(it > 0).astype(np.int32))
+        if self.noise_mode() & 12:
+            y = np.zeros(nx * steps * B)
+            self._chk(self.lib.tinympc_get_mpc_measured(self.h, _dp(y)), "get_mpc_measured")
+            out["y"] = y.reshape((nx, steps, B), order="F")
+        return out
+
+    def _set_noise(self, which, G, seed):
+        name = "set_process_noise" if which == NOISE_PROCESS else "set_measurement_noise"
+        fn = getattr(self.lib, "tinympc_" + name)
+        if G is None:
+            self._chk(fn(self.h, None, 0, 0), name)
+            return
+        Gf, rows, cols, per = _noise_factor(G, name)
+        if rows != self.nx or cols != self.nx * (self.batch if per else 1):
+            raise TinyMPCError(f"{name}: expected G (nx, nx) = ({self.nx}, {self.nx}), (nx, nx, batch) = ({self.nx}, {self.nx}, {self.batch}) "
+                               f"or sigma (nx,) = ({self.nx},); got {np.shape(G)}")
+        self._chk(fn(self.h, _dp(Gf), per, int(seed) & 0xFFFFFFFFFFFFFFFF), name)
+
+    def set_process_noise(self, G, seed=0):
+        """seeded process noise, drawn on the device: every plant step of mpc_rollout ends with one fp64 add of G xi_w[b][t], after
+        the uploaded disturbance if there is one, x+ = ((f_p + A_p x + B_p u0) + w) + G xi.  xi are standard normals that are a
+        pure function of (seed, kind, instance b, step t) — Philox4x32-10 and Box-Muller, host_noise states the rule — so
+        nothing is stored or uploaded, and t = noise cursor + loop step: two loops in a row continue the noise stream as they
+        continue the state.  The dimensions decide: G (nx, nx) shared, (nx, nx, B) one factor per instance, a 1-D (nx,) array
+        is diag(sigma); the covariance is G G'.  None drops it.  A solver with either noise is an own-plant solver (see
+        mpc_rollout): the chain of `steps` launches, every kernel family and precision.  A newly installed noise leaves the
+        cursor alone; set_precision keeps the noise, re-batching drops it."""
+        self._set_noise(NOISE_PROCESS, G, seed)
+
+    def set_measurement_noise(self, G, seed=0):
+        """seeded measurement noise, drawn on the device: the solve of step t starts from float32(x_t + G xi_v[b][t]), x_t the fp64
+        plant state, which the measurement never contaminates — the x log, x0d and x0 after the loop hold the true state.  What
+        every solve started from comes back as mpc_rollout's `y`.  G, seed, None: as set_process_noise; one cursor serves both."""
+        self._set_noise(NOISE_MEASUREMENT, G, seed)
+
+    def set_noise_cursor(self, t):
+        """move the noise cursor (>= 0): the step index the next mpc_rollout's first draw carries"""
+        self._chk(self.lib.tinympc_set_noise_cursor(self.h, int(t)), "set_noise_cursor")
+
+    def noise_cursor(self):
+        """the noise cursor: 0 for a new solver, `steps` further on after every mpc_rollout of a solver with noise"""
+        return int(self.lib.tinympc_noise_cursor(self.h))
+
+    def noise_mode(self):
+        """1 shared / 2 per-instance process factor; | 4 shared / | 8 per-instance measurement factor"""
+        return int(self.lib.tinympc_noise_mode(self.h))
+
+    def get_noise(self, which, t0, steps):
+        """the realised noise vectors G xi of kind `which` (0 process, 1 measurement) at the steps t0 .. t0 + steps - 1, computed
+        on the device by the loop's own device function: (nx, steps, B) fp64 — as a disturbance, set_disturbance(get_noise(0, c,
+        steps)) reproduces the process noise of a loop from cursor c bit for bit"""
+        buf = np.zeros(self.nx * int(steps) * self.batch)
+        self._chk(self.lib.tinympc_get_noise(self.h, int(which), int(t0), int(steps), _dp(buf)), "get_noise")
+        return buf.reshape((self.nx, int(steps), self.batch), order="F")
+
+    host_noise = staticmethod(host_noise)
 
     def set_profiling(self, on):
         self._chk(self.lib.tinympc_set_profiling(self.h, 1 if on else 0), "set_profiling")
