@@ -3,20 +3,24 @@ admm_lean_kernel<4,1,20, LIVE=false, UBK=true, ONE=true, XB=false, REFS=zero> â€
 the knots, one wavefront per SIMD) â€” its innermost loop (the iterations that do not form residuals: 99 of 100), counted by class,
 next to round 3's census of quad<4,1,20,g1>.  From r06 on the benchmark runs the sparse kernel of the cartpole pattern (SP != 0); the
 dense (controller-Hessenberg, SP = 0) instantiation that TINYMPC_HIP_LEAN_DENSE=1 runs is counted beside it.  TMPC_CENSUS_ASM: an
-existing hipcc -S output of the unit to count instead of compiling it.  Output: profiles/<tag>_cartpole_isa_census.json"""
+existing hipcc -S output of the unit to count instead of compiling it.  From r21 on the benchmark runs the scaled sparse kernel
+(csrc/linst_4_1_20_scaled.hip, the scaled cartpole pattern): that unit is compiled and counted, with the unscaled sparse kernel's
+committed census (profiles/r16_cartpole_isa_census.json) beside it.  Output: profiles/<tag>_cartpole_isa_census.json"""
 import collections, json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
 asm = os.environ.get("TMPC_CENSUS_ASM") or os.path.join(os.environ.get("TMPDIR", "/tmp"), "lean20_census.s")
 if not os.environ.get("TMPC_CENSUS_ASM"):
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-honor-nans", "-fno-slp-vectorize", "--cuda-device-only",
-                "-I" + os.path.join(ROOT, "tinympc-julia_amd/csrc"), "-S", os.path.join(ROOT, "tinympc-julia_amd/csrc/linst_4_1_20.hip"), "-o", asm], check=True,
+                "-I" + os.path.join(ROOT, "tinympc-julia_amd/csrc"), "-S", os.path.join(ROOT, "tinympc-julia_amd/csrc", "linst_4_1_20_scaled.hip" if tag >= "r21" else "linst_4_1_20.hip"), "-o", asm], check=True,
                stderr=subprocess.DEVNULL)
 lines = open(asm).read().splitlines()
 # (the trailing template argument is the (A, B) pattern: 0x1000a0021cc63 = 281517928598627, the cartpole model's; 0 the dense form)
 # (WS = MPC = false behind the pattern since the workspace-keeping forms exist)
 KERNELS = {"sparse": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm281517928598627ELb0ELb0EEEvNS_10AdmmParamsE:",
            "dense": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm0ELb0ELb0EEEvNS_10AdmmParamsE:"}
+if tag >= "r21":   # (0x4f000a0863cc63 = 22236566250572899: lean_pattern_scaled of the cartpole pattern)
+    KERNELS = {"scaled": "_ZN4tmpc16admm_lean_kernelILi4ELi1ELi20ELb0ELb1ELb1ELb0ELi0EfLm22236566250572899ELb0ELb0EEEvNS_10AdmmParamsE:"}
 if tag < "r08":
     KERNELS = {k: v.replace("ELb0ELb0EEEv", "EEEv") for k, v in KERNELS.items()}
 if tag < "r06":
@@ -77,7 +81,16 @@ def census_of(start):
 
 
 res = {k: census(w) for k, w in KERNELS.items()}
-out = res.get("sparse", res["dense"])
+out = res.get("scaled") or res.get("sparse", res["dense"])
+if "scaled" in res:
+    out["kernel"] = ("lean<4,1,20> = admm_lean_kernel<4,1,20, LIVE=false, UBK=true, ONE=true, XB=false, REFS=zero, SP=scaled cartpole pattern> "
+                     "(the benchmark's instantiation)")
+    out["coordinates"] = ("diagonally scaled, x^ = S x: sparse sweeps on S A S^-1 and S B with units at A01, A12, A23, B3 "
+                          "(u = -K^ x^ - d, x^+ = A^ x^ + B^ u; p^ = W x^ + A^' p^ - K^' t)")
+    prev = json.load(open(os.path.join(ROOT, "profiles", "r16_cartpole_isa_census.json")))
+    out["unscaled_sparse_r16"] = {k: prev[k] for k in ("instructions_per_iteration", "valu_instructions", "necessary_fp64_fma", "by_class")}
+    for k in ("round3_quad_g1", "round4_lean_dense"):
+        out.pop(k, None)
 if "sparse" in res:
     out["kernel"] = ("lean<4,1,20> = admm_lean_kernel<4,1,20, LIVE=false, UBK=true, ONE=true, XB=false, REFS=zero, SP=cartpole pattern> "
                      "(the benchmark's instantiation)")

@@ -77,6 +77,7 @@ struct LeanPack {
     static constexpr LeanLayout LL = lean_layout(NX, NU);
     static constexpr int O_M = LL.oM, O_K = LL.oK, O_B = LL.oB, O_C = LL.oC, O_H = LL.oH, O_S = LL.oS, O_P = LL.oP, O_T = LL.oT, LEN = LL.len;
     static constexpr int NLOADS = LL.padded / 8;     // s_load_dwordx16 per 8 doubles
+    static constexpr int O_Z = LL.oZ, O_W = LL.oW, O_SC = LL.oSc, O_SI = LL.oSi, NLOADS_Z = LL.padZ / 8;   // the scaled block (SCL)
 };
 
 typedef float lean_f2 __attribute__((ext_vector_type(2)));   // a pair of knots' fp32 values (PK)
@@ -155,6 +156,15 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // AmBKt = A' - Kinf' B') — skipping the zeros of the pattern at compile time and never reading its units: a row of x+
     // starts from x_j where A[m][j] is 1, a unit of A' p~ is an add.  Cartpole: 27 fp64 FMAs per knot for 37 (HB) or 49.
     constexpr bool SPR = SP != 0;
+    // SCL (SP a scaled pattern, admm_params.h: lean_pattern_scaled; one-shot forms without a state bound): the sparse sweeps on the
+    // diagonally scaled model x^ = S x — A^ = S A S^-1 and B^ = S B have units the model's own A and B lack, so a forward row
+    // that had no free start gets one (from x^_j, or from u_a where B^'s unit sits) — cartpole: 25 fp64 per knot for 27.  The
+    // backward recursion runs on p^ = S^-1 p~: a column starts fma(w_m, x^_m, <a unit term>), w = s^-2 beside the coefficients
+    // in SGPRs.  u, d, t, r~, y, z and the clamp are input-space and unchanged; x = S^-1 x^ only at the stores, and the state
+    // dual residual is max_m (max_k |x^_prev - x^_new|)_m / |s_m| (the maximum commutes with a positive scale).
+    constexpr bool SCL = lsp_scaled(SP);
+    static_assert(!SCL || (!XB && !WS && !F64 && REFS == REF_ZERO), "scaled pattern: one-shot, no state bound, zero references, fp32 state");
+    static_assert(!SCL || L::NLOADS_Z <= 4, "scaled coefficient block too large for SGPRs");
     static_assert(!SPR || (NX <= 4 && NU <= 4), "sparse pattern: nx, nu <= 4");
     constexpr bool HB = !SPR && !LIVE && !XB && ONE;
     // PK (the headline form: one wavefront per SIMD, fixed iterations, no state bound, nothing kept, one set of input bounds,
@@ -169,6 +179,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     auto a_nz = [](int m, int j) { return !SPR || lsp_a(SP, NX, m, j); };       // SP: A[m][j] is not zero
     auto a_one = [](int m, int j) { return SPR && lsp_one(SP, NX, m, j); };     //     A[m][j] is exactly 1
     auto b_nz = [](int m, int a) { return !SPR || lsp_b(SP, NU, m, a); };       //     B[m][a] is not zero
+    auto b_one = [](int m, int a) { return SCL && lsp_b_one(SP, NU, m, a); };   // SCL: B^[m][a] is exactly 1
     constexpr int BW = 2 * NX + 2 * NU;              // the quad kernel's bounds pack, one lane per instance: [N][xmin xmax umin umax]
     static_assert(L::NLOADS <= 4, "coefficient block too large for SGPRs");
 
@@ -245,8 +256,9 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     __shared__ __attribute__((aligned(16))) float s_pv[PARK ? 256 * PVS : 4];
     __shared__ float s_pz[PARK ? 256 * PZS : 1];
 
-    const SBlock<double, L::NLOADS> blk(P.lean + (HB ? L::O_H : (SPR ? L::O_S : 0)));   // (SPR: A where M is)
+    const SBlock<double, (SCL ? L::NLOADS_Z : L::NLOADS)> blk(P.lean + (HB ? L::O_H : (SCL ? L::O_Z : (SPR ? L::O_S : 0))));   // (SPR: A where M is)
     const auto cM = blk.at(L::O_M), cK = blk.at(L::O_K), cB = blk.at(L::O_B), cC = blk.at(L::O_C);
+    const auto cW = blk.at(SCL ? L::O_W : 0);                                   // SCL: w = s^-2
 
     ST lo[NU], hi[NU];
 #pragma unroll
@@ -263,6 +275,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     for (int m = 0; m < NX; ++m) {
         if constexpr (WS) X[0][m] = !active ? 0.0 : (P.x0d ? P.x0d[b * NX + m] : (double)P.x0[b * NX + m]);
         else X[0][m] = active ? (double)P.x0[b * NX + m] : 0.0;
+        if constexpr (SCL) X[0][m] *= P.lean[L::O_SC + m];                      // x^_0 = S x0
     }
     if constexpr (HB) {                                                         // x^_0 = T' x0
         double x0[NX];
@@ -347,6 +360,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     const ST rho = F64 ? (ST)P.rho_family : (ST)P.rho;
     const ST ptol = F64 ? (ST)P.abs_pri_tol64 : (ST)P.abs_pri_tol, dtol = F64 ? (ST)P.abs_dua_tol64 : (ST)P.abs_dua_tol;
     double dua_x = 0.0;
+    double dua_xs[SCL ? NX : 1] = {};                                           // SCL: max_k |x^_prev - x^_new| per component
     ST pri_u = 0, dua_u = 0, pri_xf = 0, dua_xf = 0;                             // (XB: the state residuals in the slack's own type)
     // PARK: knot k's previous state slack into the lane's row — whole float4 where nx allows (16-byte writes at a row stride of
     // an odd number of float4: conflict-free), written as such rather than left to the compiler to merge
@@ -410,6 +424,9 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         constexpr bool RES = decltype(res_tag)::value;
         if constexpr (RES) {
             dua_x = 0.0, pri_u = 0, dua_u = 0, pri_xf = 0, dua_xf = 0;
+            if constexpr (SCL)
+#pragma unroll
+                for (int m = 0; m < NX; ++m) dua_xs[m] = 0.0;
             if constexpr (WS && !XB) {
                 // knot 0: vnew is x0; the previous slack is the workspace's v_0 in the first iteration (zero when cold) and
                 // x0 after any iteration (admm.cpp:94)
@@ -457,6 +474,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                             double Tm[NX * NX];
                             load_T(Tm);
                             dua_x = fmax(dua_x, fabs(to_x(Tm, X[0], m)));
+                        } else if constexpr (SCL) {                             // (|x0| once the component's scale is taken out, below)
+                            dua_xs[m] = fabs(X[0][m]);
                         } else {
                             dua_x = fmax(dua_x, fabs(X[0][m]));
                         }
@@ -466,7 +485,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         // HB: x^_0 is loop-invariant, and so are the products of its band rows that no b^ term starts: hoisted out of the
         // iteration loop they would stay live across it (18 registers for cartpole; SPR: A x_0 likewise — except in the
         // 256-register form without a state bound, which spills 33 registers with the opaque use and none without)
-        if constexpr (HB || (SPR && (ONE || XB)))
+        // (SCL in the 512-register form: 290 of 512 registers, the products leave the loop)
+        if constexpr (HB || (SPR && (ONE || XB) && !(SCL && ONE)))
 #pragma unroll
             for (int m = 0; m < NX; ++m) asm volatile("" : "+v"(X[0][m]));
         double xr[NX];                                                          // XB: the running x_k
@@ -505,9 +525,17 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                     }
             }
             // u = -Kinf x - d  (SPR: x_k's rows without a B term first — the others wait for the previous knot's u)
+            // SCL, 512 registers, knot 0: x^_0 does not change over the iterations, so the chains are grouped with its terms
+            // first — u_0 = (-K^ x^_0) - d_0, a row A^ x^_0 before its u terms — and those groups leave the iteration loop
+            constexpr bool K0H = SCL && ONE && k == 0;
 #pragma unroll
             for (int a = 0; a < NU; ++a) {
-                if constexpr (SPR) {
+                if constexpr (K0H) {
+                    double acc = -(cK[a * NX] * xk[0]);
+#pragma unroll
+                    for (int j = 1; j < NX; ++j) acc = fma(-cK[a * NX + j], xk[j], acc);
+                    u[a] = acc - dk[a];
+                } else if constexpr (SPR) {
                     double acc = -dk[a];
 #pragma unroll
                     for (int pass = 0; pass < 2; ++pass)
@@ -536,13 +564,17 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             if constexpr (SPR) {   // x+ = A x + B u: a row's chain starts from x_j at its first unit; the u terms last
 #pragma unroll
                 for (int m = 0; m < NX; ++m) {
-                    int s = -1;
+                    int s = -1, sb = -1;
 #pragma unroll
                     for (int j = NX - 1; j >= 0; --j)
                         if (a_one(m, j)) s = j;
-                    started[m] = s >= 0;
+#pragma unroll
+                    for (int a = NU - 1; a >= 0; --a)                           // SCL: ... or, without one, from u_a at B^'s unit
+                        if (s < 0 && b_one(m, a) && !K0H) sb = a;
+                    started[m] = s >= 0 || sb >= 0;
                     xn[m] = 0.0;                                                // (a row without terms)
                     if (s >= 0) xn[m] = xk[s];
+                    else if (sb >= 0) xn[m] = u[sb];
 #pragma unroll
                     for (int j = 0; j < NX; ++j) {
                         if (!a_nz(m, j) || j == s) continue;
@@ -551,8 +583,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                     }
 #pragma unroll
                     for (int a = 0; a < NU; ++a) {
-                        if (!b_nz(m, a)) continue;
-                        xn[m] = started[m] ? fma(cB[m * NU + a], u[a], xn[m]) : cB[m * NU + a] * u[a];
+                        if (!b_nz(m, a) || a == sb) continue;
+                        xn[m] = !started[m] ? cB[m * NU + a] * u[a] : (b_one(m, a) ? xn[m] + u[a] : fma(cB[m * NU + a], u[a], xn[m]));
                         started[m] = true;
                     }
                 }
@@ -609,7 +641,8 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 if constexpr (XB) {
                     xr[m] = xn[m];
                 } else {
-                    if constexpr (RES && !HB) dua_x = fmax(dua_x, fabs(X[k + 1][m] - xn[m]));   // v - vnew with v = the previous x  (:94)
+                    if constexpr (RES && SCL) dua_xs[m] = fmax(dua_xs[m], fabs(X[k + 1][m] - xn[m]));
+                    else if constexpr (RES && !HB) dua_x = fmax(dua_x, fabs(X[k + 1][m] - xn[m]));   // v - vnew with v = the previous x  (:94)
                     if constexpr (!(RES && HB)) X[k + 1][m] = xn[m];
                 }
             }
@@ -624,8 +657,16 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             // (the residual maxima are only read under `!conv`: left alone, the compiler sinks the whole chain into that
             // branch, behind the sweep, and keeps every knot's u, znew and previous x alive for it — 190 spilled registers)
             if constexpr (RES) asm volatile("" : "+v"(pri_u), "+v"(dua_u), "+v"(dua_x), "+v"(pri_xf), "+v"(dua_xf));
+            if constexpr (RES && SCL)
+#pragma unroll
+                for (int m = 0; m < NX; ++m) asm volatile("" : "+v"(dua_xs[m]));
             if constexpr (TMPC_LEAN_KNOT_BARRIER) __builtin_amdgcn_sched_barrier(0);
         });
+        if constexpr (RES && SCL) {                                             // the state dual residual in the original coordinates
+#pragma unroll
+            for (int m = 0; m < NX; ++m) dua_x = fmax(dua_x, dua_xs[m] * fabs(P.lean[L::O_SI + m]));
+            asm volatile("" : "+v"(dua_x));
+        }
         if constexpr (XB) {
             asm volatile("" ::: "memory");
             state_sets(res_tag, std::integral_constant<int, N - 1>{}, xr);      // the terminal knot's slack / dual
@@ -641,6 +682,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #pragma unroll
         for (int m = 0; m < NX; ++m) {                                          // p~_{N-1} = vnew_{N-1} - g_{N-1} (+ Pinf' xref / rho)  (:81-82)
             p[m] = XB ? (double)QT[N - 1][m] : X[XB ? 0 : N - 1][m];
+            if constexpr (SCL) p[m] *= cW[m];                                   // p^_{N-1} = W x^_{N-1}
             if constexpr (REFS == REF_SHARED) p[m] += s_cpt[m];
         }
         float rpk[PK ? NU : 1];                                                 // PK: the even knot's r~, formed with its partner's
@@ -665,7 +707,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
             for (int j = 0; j < NX; ++j)
 #pragma unroll
                 for (int a = 0; a < NU; ++a)
-                    if (!bh_zero(j, a) && b_nz(j, a)) t[a] = fma(cB[j * NU + a], p[j], t[a]);   // B' p~_{k+1} + r~_k
+                    if (!bh_zero(j, a) && b_nz(j, a)) t[a] = b_one(j, a) ? t[a] + p[j] : fma(cB[j * NU + a], p[j], t[a]);   // B' p~_{k+1} + r~_k
 #pragma unroll
             for (int a = 0; a < NU; ++a) {                                      // d_k = Quu_inv (B' p_{k+1} + r_k)  (:17)
                 double acc = cC[a * NU] * t[0];
@@ -679,9 +721,16 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 for (int m = 0; m < NX; ++m) {
                     double acc = XB ? (double)QT[k][m] : X[XB ? 0 : k][m];
                     if constexpr (REFS == REF_SHARED) acc += s_cq[k * NX + m];
+                    int ju = -1;                                                // SCL: the column starts fma(w_m, x^_m, p^_j) at its first unit
+                    if constexpr (SCL) {
+#pragma unroll
+                        for (int j = NX - 1; j >= 0; --j)
+                            if (a_one(j, m)) ju = j;
+                        acc = ju >= 0 ? fma(cW[m], acc, p[ju]) : cW[m] * acc;
+                    }
 #pragma unroll
                     for (int j = 0; j < NX; ++j)
-                        if (a_nz(j, m)) acc = a_one(j, m) ? acc + p[j] : fma(cM[j * NX + m], p[j], acc);
+                        if (a_nz(j, m) && j != ju) acc = a_one(j, m) ? acc + p[j] : fma(cM[j * NX + m], p[j], acc);
 #pragma unroll
                     for (int a = 0; a < NU; ++a) acc = fma(-cK[a * NX + m], t[a], acc);
                     ap[m] = acc;
@@ -716,10 +765,18 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // element (k, m) of the solution: the state slack vnew — x itself, or q~ + g brought back inside the bounds it was clamped
     // to (fp32 rounding of the sum can leave them by an ulp)
     double Ts[HB ? NX * NX : 1];                                               // HB: T, loaded at the final store
+    double Si[SCL ? NX : 1];                                                    // SCL: 1 / s, loaded at each store
+    auto load_Si = [&]() {   // (through an opaque pointer: the four values are not kept across the iteration loop)
+        const double *sp = P.lean + L::O_SI;
+        asm volatile("" : "+s"(sp));
+#pragma unroll
+        for (int m = 0; m < (SCL ? NX : 0); ++m) Si[m] = sp[m];
+    };
     auto vnew_at = [&](auto kk, auto mm) -> float {
         constexpr int k = decltype(kk)::value, m = decltype(mm)::value;
         if constexpr (XB) return (float)clamp3(QT[k][m] + G[k][m], (ST)s_xb[k * 2 * NX + m], (ST)s_xb[k * 2 * NX + NX + m]);
         else if constexpr (HB) return (float)to_x(Ts, X[k], m);
+        else if constexpr (SCL) return (float)(X[k][m] * Si[m]);               // x = S^-1 x^
         else return (float)X[XB ? 0 : k][m];
     };
     auto store = [&](bool solved_flag) {
@@ -727,6 +784,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         // addresses once, outside the iteration loop (the LIVE variant stores inside it), and spills 200 registers for them
         float *xo = P.xout + b * EX, *uo = P.uout + b * EU, *ro = P.res + b * 4;
         asm volatile("" : "+v"(xo), "+v"(uo), "+v"(ro));
+        if constexpr (SCL) load_Si();
         sfor<0, N>([&](auto kk) {
             constexpr int k = decltype(kk)::value;
             sfor<0, NX>([&](auto mm) { xo[k * NX + decltype(mm)::value] = vnew_at(kk, mm); });
@@ -1027,6 +1085,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
         if (mask) {
             if constexpr (HB) load_T(Ts);
+            if constexpr (SCL) load_Si();
             if constexpr (WS) {
                 store_ws(mask, mine, std::false_type{});                    // ... and the workspace, when the solve saves it
             } else {

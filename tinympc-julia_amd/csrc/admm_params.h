@@ -98,7 +98,7 @@ struct AdmmParams {
     // ---- lean kernel (admm_lean.hip.h): its fp64 coefficient pack (LeanPack), wave-uniform ----
     const double *lean;
     // ---- launcher-side switches (read from the environment once per solver: Switches), not read by any kernel ----
-    int host_flags;   // HF_NO_REFILL | HF_NO_UNI | HF_NO_OS
+    int host_flags;   // HF_NO_REFILL | HF_NO_UNI | HF_NO_OS | HF_LEAN_SCALED
     // ---- generic kernel, precision 2 (fp64 end to end): the workspace kept between solves (Ws64) and the tolerances in fp64 ----
     double *ws64;
     double abs_pri_tol64, abs_dua_tol64;
@@ -115,7 +115,7 @@ struct AdmmParams {
     int ib_on;        // IB_STATE | IB_INPUT: the sides the settings leave switched on (the other clamps against -+inf, unread)
 };
 enum : int { IB_STATE = 1, IB_INPUT = 2 };
-enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4 };
+enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4, HF_LEAN_SCALED = 8 };   // (HF_LEAN_SCALED: the lean pack's scaled block is valid)
 
 // Coefficient pack of the lean kernel (admm_lean.hip.h), fp64, all wave-uniform; filled by build_lean_pack (kernels.hip).
 // Three coefficient blocks of the same layout: the plain one (what the tolerance-terminated and state-bounded variants read);
@@ -134,14 +134,16 @@ struct LeanLayout {
     int oP;      // Pinf           [nx][nx] row-major, behind the padded blocks (read once, for the terminal reference term)
     int oT;      // T              [nx][nx] row-major, orthogonal (read at entry, at the residual iteration and at the store)
     int total;
+    // appended behind everything above (no earlier offset moves): the block of the diagonally scaled model x^ = S x
+    // (lean_pattern_scaled below) — [S A S^-1, Kinf S^-1, S B, C] in the layout of the others, w = diag(S)^-2 [nx] behind C at
+    // oW, padded to whole scalar loads (padZ) — then s [nx] and 1 / s [nx], read at entry, at the residuals and at the store
+    int oZ, oW, padZ, oSc, oSi;
 };
 constexpr LeanLayout lean_layout(int nx, int nu) {
-    return LeanLayout{0, nx * nx, nx * nx + nu * nx, nx * nx + 2 * nu * nx, nx * nx + 2 * nu * nx + nu * nu,
-                      (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8, (nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8,
-                      2 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8),
-                      3 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8),
-                      3 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + nx * nx,
-                      3 * ((nx * nx + 2 * nu * nx + nu * nu + 7) / 8 * 8) + 2 * nx * nx};
+    const int len = nx * nx + 2 * nu * nx + nu * nu, pad = (len + 7) / 8 * 8, padz = (len + nx + 7) / 8 * 8;
+    const int old_total = 3 * pad + 2 * nx * nx, oz = (old_total + 7) / 8 * 8;
+    return LeanLayout{0, nx * nx, nx * nx + nu * nx, nx * nx + 2 * nu * nx, len, pad, pad, 2 * pad, 3 * pad, 3 * pad + nx * nx,
+                      oz + padz + 2 * nx, oz, len, padz, oz + padz, oz + padz + nx};
 }
 
 // Zero / unit pattern of a model's (A, B), nx, nu <= 4, as a lean kernel's compile-time parameter SP: bits 0-15 the nonzeros
@@ -194,6 +196,78 @@ constexpr int lean_cost_dense(int nx, int nu) { return 2 * nx * nx + 4 * nx * nu
 constexpr bool lean_pattern_covers(uint64_t built, uint64_t model) {
     const uint64_t nz = 0xFFFFull | (0xFFFFull << LSP_B), one = 0xFFFFull << LSP_UNIT;
     return built != 0 && model != 0 && (model & nz & ~built) == 0 && ((built & one) & ~(model & one)) == 0;
+}
+
+// Pattern of a diagonally scaled model.  x^ = S x, S = diag(s), turns (A, B) into (S A S^-1, S B): the zeros and the diagonal of
+// A stay, and the nx free ratios of s make up to nx - 1 off-diagonal nonzeros of A and one nonzero of B exactly 1 — a forward
+// row may then start from a free operand where the model's own row has none.  The backward recursion keeps its form with
+// p^ = S^-1 p~: p^_k = W x^_k + A^' p^_{k+1} - K^' t_k, t_k = r~_k + B^' p^_{k+1}, W = S^-2 diagonal, K^ = Kinf S^-1; the
+// input-space u, d, t, r~, y, z and C are unchanged.  Bit 49 marks such a pattern: its unit bits (16-31) are the model's
+// DIAGONAL units and the chosen off-diagonal entries, bit 54 says that B has a unit and bits 50-53 which (i * nu + a).
+enum : int { LSP_SCALED = 49, LSP_BU = 50, LSP_BU_ON = 54 };
+constexpr bool lsp_scaled(uint64_t sp) { return (sp >> LSP_SCALED) & 1; }
+constexpr bool lsp_b_one(uint64_t sp, int nu, int i, int a) {
+    return ((sp >> LSP_BU_ON) & 1) && (int)((sp >> LSP_BU) & 15) == i * nu + a;
+}
+// fp64 instructions per knot of the scaled sparse sweeps of pattern sp^ (both sweeps, zero references): u = -K^ x^ - d costs
+// nx nu; a forward row its terms of A^ and B^, one fewer where it holds a unit of either (the chain's free start); t the
+// nonzeros of B^ (from r~; a unit is an add); d = C t costs nu^2; a backward column 1 (w x^) + its nonzeros of A^ + nu
+// (K^' t), one fewer where the column holds a unit of A^ (fma(w, x^, p^_j) starts the chain)
+constexpr int lean_cost_scaled(uint64_t sp, int nx, int nu) {
+    int c = nx * nu + nu * nu;
+    for (int i = 0; i < nx; ++i) {
+        int row = 0, col = 1 + nu;
+        bool ru = false, cu = false;
+        for (int j = 0; j < nx; ++j) {
+            row += lsp_a(sp, nx, i, j), ru = ru || lsp_one(sp, nx, i, j);
+            col += lsp_a(sp, nx, j, i), cu = cu || lsp_one(sp, nx, j, i);
+        }
+        for (int a = 0; a < nu; ++a) {
+            row += lsp_b(sp, nu, i, a), ru = ru || lsp_b_one(sp, nu, i, a);
+            c += lsp_b(sp, nu, i, a);                                    // (t)
+        }
+        c += row - (ru && row > 0 ? 1 : 0) + col - (cu ? 1 : 0);
+    }
+    return c;
+}
+// The scaled pattern of a model's pattern sp (positions only, not values): the off-diagonal nonzeros of A made units — a set
+// that is acyclic as an undirected graph on the states (a cycle's product is invariant under the scaling), so at most
+// nx - 1 of them — and at most one nonzero of B, chosen by plain enumeration (at most 12 candidates at nx <= 4) to minimise
+// lean_cost_scaled; among equal costs the choice with the most units wins (a unit is a coefficient the kernel never reads, and
+// its term an add without a product's rounding), then the lowest mask (the A bits, then the B choice: none, then by index).
+// Diagonal units of A carry over; an off-diagonal unit of the model is a candidate like any other nonzero.  0: no pattern.
+constexpr uint64_t lean_pattern_scaled(uint64_t sp, int nx, int nu) {
+    if (sp == 0 || lsp_scaled(sp) || nx < 1 || nu < 1 || nx > 4 || nu > 4) return 0;
+    uint64_t base = (sp & (0xFFFFull | (0xFFFFull << LSP_B))) | (1ull << LSP_ON) | (1ull << LSP_SCALED);
+    uint32_t cand = 0;
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < nx; ++j) {
+            if (i == j && lsp_one(sp, nx, i, i)) base |= 1ull << (LSP_UNIT + i * nx + i);
+            if (i != j && lsp_a(sp, nx, i, j)) cand |= 1u << (i * nx + j);
+        }
+    uint64_t best = 0;
+    int best_cost = 0, best_units = 0;
+    for (uint32_t m = 0, done = 0; !done; done = (m == cand), m = (m - cand) & cand) {   // the subsets of cand, ascending
+        int comp[4] = {0, 1, 2, 3};
+        bool ok = true;
+        for (int e = 0; e < nx * nx && ok; ++e) {
+            if (!((m >> e) & 1)) continue;
+            const int ci = comp[e / nx], cj = comp[e % nx];
+            if (ci == cj) ok = false;                                    // (closes a cycle; a forest has at most nx - 1 edges)
+            for (int q = 0; q < nx; ++q)
+                if (comp[q] == cj) comp[q] = ci;
+        }
+        for (int b = -1; ok && b < nx * nu; ++b) {
+            if (b >= 0 && !((sp >> (LSP_B + b)) & 1)) continue;
+            uint64_t s = base | ((uint64_t)m << LSP_UNIT);
+            if (b >= 0) s |= (1ull << LSP_BU_ON) | ((uint64_t)b << LSP_BU);
+            int units = b >= 0 ? 1 : 0;
+            for (int e = 0; e < nx * nx; ++e) units += (m >> e) & 1;
+            const int cost = lean_cost_scaled(s, nx, nu);
+            if (best == 0 || cost < best_cost || (cost == best_cost && units > best_units)) best = s, best_cost = cost, best_units = units;
+        }
+    }
+    return best;
 }
 
 #ifdef __HIPCC__

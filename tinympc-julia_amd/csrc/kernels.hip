@@ -67,8 +67,64 @@ const LeanEntry *find_lean_kernel(int nx, int nu, int N) {
     return nullptr;
 }
 
-bool build_lean_pack(const Solver &sv, std::vector<double> &out) {
+// The diagonal scaling x^ = S x under which a kernel of the scaled pattern lean_pattern_scaled(built) computes the model
+// (A [nx][nx], B [nx][nu], row-major): each chosen entry A^[i][j] = s_i A[i][j] / s_j = 1 fixes a ratio along the forest of
+// chosen entries (a component's root has s = 1), B's unit the scale of its component.  Returns the scaled pattern and fills
+// s [nx], or 0 — the launch then keeps the unscaled sparse kernel — where `built` does not cover the model, a chosen entry is
+// zero in it (the ratio does not exist), or the scaled sweeps cost no less than the sparse ones.
+uint64_t lean_scale_model(uint64_t built, int nx, int nu, const double *A, const double *B, double *s) {
+    const uint64_t sz = lean_pattern_scaled(built, nx, nu);
+    if (!sz || !lean_pattern_covers(built, lean_pattern_rm(nx, nu, A, B))) return 0;
+    if (lean_cost_scaled(sz, nx, nu) >= lean_cost_sparse(built, nx, nu)) return 0;
+    bool known[4] = {false, false, false, false};
+    int comp[4] = {0, 1, 2, 3};
+    for (int i = 0; i < nx; ++i)
+        for (int j = 0; j < nx; ++j)
+            if (i != j && lsp_one(sz, nx, i, j)) {
+                if (A[i * nx + j] == 0.0) return 0;
+                const int ci = comp[i], cj = comp[j];
+                for (int q = 0; q < nx; ++q)
+                    if (comp[q] == cj) comp[q] = ci;
+            }
+    for (int r = 0; r < nx; ++r) {
+        if (known[r]) continue;
+        s[r] = 1.0, known[r] = true;                                     // the root of a component not reached yet
+        for (int pass = 0; pass < nx; ++pass)
+            for (int i = 0; i < nx; ++i)
+                for (int j = 0; j < nx; ++j) {
+                    if (i == j || !lsp_one(sz, nx, i, j)) continue;
+                    if (known[j] && !known[i]) s[i] = s[j] / A[i * nx + j], known[i] = true;
+                    else if (known[i] && !known[j]) s[j] = s[i] * A[i * nx + j], known[j] = true;
+                }
+    }
+    for (int i = 0; i < nx; ++i)
+        for (int a = 0; a < nu; ++a)
+            if (lsp_b_one(sz, nu, i, a)) {
+                if (B[i * nu + a] == 0.0) return 0;
+                const double f = 1.0 / (B[i * nu + a] * s[i]);
+                for (int q = 0; q < nx; ++q)
+                    if (comp[q] == comp[i]) s[q] *= f;
+            }
+    for (int i = 0; i < nx; ++i)
+        if (!std::isfinite(s[i]) || s[i] == 0.0 || !std::isfinite(1.0 / (s[i] * s[i]))) return 0;
+    return sz;
+}
+// ... and the scaled model's coefficients: A^ = S A S^-1 and B^ = S B with exact units where sz says so, K^ = Kinf S^-1
+void lean_scaled_coefficients(uint64_t sz, int nx, int nu, const double *A, const double *B, const double *K, const double *s,
+                              double *Ah, double *Bh, double *Kh) {
+    for (int i = 0; i < nx; ++i) {
+        for (int j = 0; j < nx; ++j)
+            Ah[i * nx + j] = i == j ? A[i * nx + j] : (lsp_one(sz, nx, i, j) ? 1.0 : s[i] * A[i * nx + j] / s[j]);
+        for (int a = 0; a < nu; ++a) Bh[i * nu + a] = lsp_b_one(sz, nu, i, a) ? 1.0 : s[i] * B[i * nu + a];
+    }
+    if (K && Kh)
+        for (int a = 0; a < nu; ++a)
+            for (int j = 0; j < nx; ++j) Kh[a * nx + j] = K[a * nx + j] / s[j];
+}
+
+bool build_lean_pack(const Solver &sv, std::vector<double> &out, bool *scaled) {
     const int nx = sv.nx, nu = sv.nu;
+    if (scaled) *scaled = false;
     const LeanLayout L = lean_layout(nx, nu);
     out.assign((size_t)L.total, 0.0);
     const Cache &c = sv.cache;
@@ -112,6 +168,23 @@ bool build_lean_pack(const Solver &sv, std::vector<double> &out) {
     for (int i = 0; i < nx; ++i)
         for (int j = 0; j < nx; ++j) out[L.oS + L.oM + i * nx + j] = sv.A(i, j);
     for (int i = L.oK; i < L.len; ++i) out[L.oS + i] = out[i];
+    // the scaled block, where the built-in entry has kernels of its scaled pattern and this model takes them
+    if (sv.le && sv.le->sp_scaled && nx <= 4 && nu <= 4) {
+        double s[4];
+        const uint64_t sz = lean_scale_model(sv.le->sp, nx, nu, out.data() + L.oS + L.oM, out.data() + L.oS + L.oB, s);
+        if (sz && sz == sv.le->sp_scaled) {
+            double *z = out.data() + L.oZ;
+            lean_scaled_coefficients(sz, nx, nu, out.data() + L.oS + L.oM, out.data() + L.oS + L.oB, out.data() + L.oS + L.oK, s,
+                                     z + L.oM, z + L.oB, z + L.oK);
+            for (int i = 0; i < nu * nu; ++i) z[L.oC + i] = out[L.oC + i];
+            for (int i = 0; i < nx; ++i) {
+                z[L.oW + i] = 1.0 / (s[i] * s[i]);
+                out[L.oSc + i] = s[i];
+                out[L.oSi + i] = 1.0 / s[i];
+            }
+            if (scaled) *scaled = true;
+        }
+    }
     return true;
 }
 
@@ -215,6 +288,21 @@ extern "C" int tmpc_lean_costs(int nx, int nu, unsigned long long sp, int *out3)
     if (nx < 1 || nu < 1 || nx > 4 || nu > 4 || !out3) return 1;
     out3[0] = tmpc::lean_cost_sparse(sp, nx, nu), out3[1] = tmpc::lean_cost_hessenberg(nx, nu), out3[2] = tmpc::lean_cost_dense(nx, nu);
     return 0;
+}
+// the scaled pattern of a pattern (admm_params.h: lean_pattern_scaled) and its per-knot fp64 cost; the scaling a kernel of
+// lean_pattern_scaled(built) takes a model under (built = 0: the model's own pattern) — returns the scaled pattern, 0 where the
+// model keeps the unscaled sweeps, and fills s [nx], A^ [nx][nx], B^ [nx][nu]
+extern "C" unsigned long long tmpc_lean_scaled_pattern(int nx, int nu, unsigned long long sp) { return tmpc::lean_pattern_scaled(sp, nx, nu); }
+extern "C" int tmpc_lean_scaled_cost(int nx, int nu, unsigned long long sz) {
+    return (nx < 1 || nu < 1 || nx > 4 || nu > 4 || !tmpc::lsp_scaled(sz)) ? -1 : tmpc::lean_cost_scaled(sz, nx, nu);
+}
+extern "C" unsigned long long tmpc_lean_scale_model(int nx, int nu, const double *A, const double *B, unsigned long long built, double *s,
+                                                    double *Ah, double *Bh) {
+    if (nx < 1 || nu < 1 || nx > 4 || nu > 4 || !A || !B || !s || !Ah || !Bh) return 0;
+    if (!built) built = tmpc::lean_pattern_rm(nx, nu, A, B);
+    const uint64_t sz = tmpc::lean_scale_model(built, nx, nu, A, B, s);
+    if (sz) tmpc::lean_scaled_coefficients(sz, nx, nu, A, B, nullptr, s, Ah, Bh, nullptr);
+    return sz;
 }
 extern "C" int tmpc_lean_covers(unsigned long long built, unsigned long long model) { return tmpc::lean_pattern_covers(built, model) ? 1 : 0; }
 extern "C" int tmpc_lean_pick_form(int nx, int nu, unsigned long long built, unsigned long long model, int one, int live, int xb) {

@@ -128,6 +128,31 @@ constexpr double kCartpoleA[16] = {1.0, 0.01, 0.0, 0.0,
                                    0.0, 0.0, 0.458, 1.002};
 constexpr double kCartpoleB[4] = {0.0, 0.02, 0.0, 0.067};
 constexpr uint64_t kCartpolePattern = lean_pattern_rm(4, 1, kCartpoleA, kCartpoleB);
+// ... and its scaled pattern (admm_params.h: lean_pattern_scaled): A01, A12, A23 and B3 become units beside A00 and A11 — the
+// forward rows 2 and 3 get a free start, 25 fp64 per knot for 27
+constexpr uint64_t kCartpolePatternScaled = lean_pattern_scaled(kCartpolePattern, 4, 1);
+static_assert(lean_cost_scaled(kCartpolePatternScaled, 4, 1) == 25 && lean_cost_sparse(kCartpolePattern, 4, 1) == 27, "cartpole: 25 for 27");
+
+// The scaled sparse kernels of a built-in entry (admm_lean.hip.h: SCL), in a translation unit of their own
+// (linst_*_scaled.hip): the cases lean_runs_scaled (solver.h) names — one-shot, no state bound, uniform input bounds
+template <int NX, int NU, int N, uint64_t SPZ>
+hipError_t launch_lean_scaled(TMPC_LEAN_ARGS) {
+    static_assert(lsp_scaled(SPZ), "a scaled pattern");
+    const int grid = (P.batch + 255) / 256;
+#define TMPC_LEAN_LAUNCH(LIVE_, ONE_) \
+    lean_dispatch(admm_lean_kernel<NX, NU, N, LIVE_, true, ONE_, false, REF_ZERO, float, SPZ>, grid, stream, ev0, ev1, P)
+    switch (variant & (LV_LIVE | LV_ONE)) {
+        case LV_LIVE | LV_ONE: TMPC_LEAN_LAUNCH(true, true); break;
+        case LV_ONE: TMPC_LEAN_LAUNCH(false, true); break;
+        default: return hipErrorNotSupported;   // (the 256-register form spills 63 registers with these sweeps: not built)
+    }
+#undef TMPC_LEAN_LAUNCH
+    return hipGetLastError();
+}
+#define TMPC_DEFINE_LEAN_SCALED(NX, NU, NN, SPZ)                                             \
+    hipError_t lean_scaled_##NX##_##NU##_##NN(TMPC_LEAN_ARGS) {                              \
+        return launch_lean_scaled<NX, NU, NN, (SPZ)>(P, variant, stream, ev0, ev1);          \
+    }
 
 // The workspace-keeping kernels (KIND ws) and the in-kernel closed loops (KIND mpc) of a built-in entry live in translation
 // units of their own, one per (XB, REFS) pair of the dense kernels and one for the sparse ones (linst_ws_*.hip,
@@ -155,20 +180,25 @@ constexpr uint64_t kCartpolePattern = lean_pattern_rm(4, 1, kCartpoleA, kCartpol
 #define TMPC_DEFINE_LEAN_MPC_PART(NX, NU, NN, TAG, XB, REFS) TMPC_DEFINE_LEAN_PART(mpc, true, true, NX, NU, NN, TAG, XB, REFS)
 #define TMPC_DEFINE_LEAN_MPC_SPARSE(NX, NU, NN, SP) TMPC_DEFINE_LEAN_PART_SPARSE(mpc, true, true, NX, NU, NN, SP)
 // an entry with the sparse kernels of pattern SP, the workspace-keeping kernels and the in-kernel closed loop of both kinds
-#define TMPC_DEFINE_LEAN_ENTRY_FULL(NX, NU, NN, SP)                                                                    \
+// ... and the scaled sparse kernels of pattern SPZ (0: none), which a one-shot sparse launch takes where lean_runs_scaled says so
+#define TMPC_DEFINE_LEAN_ENTRY_FULL(NX, NU, NN, SP, SPZ)                                                               \
     TMPC_DECLARE_LEAN_PARTS(ws, NX, NU, NN)                                                                            \
     TMPC_DECLARE_LEAN_PARTS(mpc, NX, NU, NN)                                                                           \
+    hipError_t lean_scaled_##NX##_##NU##_##NN(TMPC_LEAN_ARGS);                                                         \
+    const LeanEntry *lean_entry_##NX##_##NU##_##NN();                                                                  \
     static hipError_t lean_launch_##NX##_##NU##_##NN(TMPC_LEAN_ARGS) {                                                 \
         static constexpr LeanLaunch ws[5] = TMPC_LEAN_PARTS(ws, NX, NU, NN), mpc[5] = TMPC_LEAN_PARTS(mpc, NX, NU, NN); \
         if (variant & LV_F64) return hipErrorNotSupported;                                                             \
         const int part = (variant & LV_SPARSE) ? 4 : ((variant & LV_SHARED) ? 2 : 0) + ((variant & LV_XB) ? 1 : 0);    \
         if (variant & LV_MPC) return mpc[part](P, variant, stream, ev0, ev1);                                          \
         if (variant & LV_WS) return ws[part](P, variant, stream, ev0, ev1);                                            \
+        if (lean_runs_scaled(lean_entry_##NX##_##NU##_##NN(), variant, P.host_flags))                                  \
+            return lean_scaled_##NX##_##NU##_##NN(P, variant, stream, ev0, ev1);                                       \
         return part == 4 ? launch_lean_sparse<NX, NU, NN, (SP)>(P, variant, stream, ev0, ev1)                          \
                          : launch_lean<NX, NU, NN>(P, variant, stream, ev0, ev1);                                      \
     }                                                                                                                  \
     const LeanEntry *lean_entry_##NX##_##NU##_##NN() {                                                                 \
-        static const LeanEntry e = {NX, NU, NN, "lean<" #NX "," #NU "," #NN ">", (SP), LK_ALL, &lean_launch_##NX##_##NU##_##NN}; \
+        static const LeanEntry e = {NX, NU, NN, "lean<" #NX "," #NU "," #NN ">", (SP), LK_ALL, &lean_launch_##NX##_##NU##_##NN, (SPZ)}; \
         return &e;                                                                                                     \
     }
 

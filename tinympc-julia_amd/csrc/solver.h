@@ -59,7 +59,19 @@ struct LeanEntry {
     // runs the kernel of `variant`; hipErrorNotSupported: the entry has no such kernel (lean_plan sends none).  ev0 / ev1:
     // timing events carried by the kernel's own dispatch packet (its start and its end); null: none
     LeanLaunch launch;
+    // the scaled pattern (admm_params.h: lean_pattern_scaled) its scaled sparse kernels are built for, 0: it has none.  A launch
+    // runs them where P.host_flags carries HF_LEAN_SCALED and the (LIVE, ONE, XB) case has one (lean_entry.hip.h)
+    uint64_t sp_scaled = 0;
 };
+// The (LIVE, ONE, XB) cases of the one-shot sparse kernels that exist in the scaled form: without a state bound, the
+// 512-register kernels, fixed-iteration and tolerance-terminated (they must agree bit for bit).  The 256-register
+// fixed-iteration kernel is not built: at 246 of 256 registers today, it spills 63 with the scaled sweeps.  THE rule: the
+// built-in entry's launcher (lean_entry.hip.h) and the test hook tmpc_lean_last_scaled both ask it.
+inline bool lean_runs_scaled(const LeanEntry *e, int variant, int host_flags) {
+    if (!e || !e->sp_scaled || !(host_flags & HF_LEAN_SCALED)) return false;
+    if ((variant & (LV_SPARSE | LV_UBK | LV_SHARED | LV_F64 | LV_WS | LV_MPC | LV_XB)) != (LV_SPARSE | LV_UBK)) return false;
+    return (variant & LV_ONE) != 0;
+}
 const LeanEntry *find_lean_kernel(int nx, int nu, int N);
 // ... or ONE variant of it specialised at the first launch that needs it (jit.cpp; nullptr: the shape does not fit the kernel);
 // sp: the model's own pattern with LV_SPARSE, else 0
@@ -114,7 +126,11 @@ LeanPlan lean_plan(const LeanPlanIn &);
 // the (A, B) pattern of a solver's model (0: nx or nu above 4)
 uint64_t lean_pattern(const Mat &A, const Mat &B);
 // the lean kernel's fp64 pack (lean_layout); false when the family does not qualify (cache.AmBKt is not (A - B Kinf)')
-bool build_lean_pack(const Solver &, std::vector<double> &);
+// scaled (may be null): whether the pack's scaled block is valid for this model (lean_scale_model)
+bool build_lean_pack(const Solver &, std::vector<double> &, bool *scaled = nullptr);
+uint64_t lean_scale_model(uint64_t built, int nx, int nu, const double *A, const double *B, double *s);
+void lean_scaled_coefficients(uint64_t sz, int nx, int nu, const double *A, const double *B, const double *K, const double *s,
+                              double *Ah, double *Bh, double *Kh);
 // ... and the one-lane-per-instance bound pack appended to it, for a solver whose selected entry keeps another layout
 void append_lean_bounds(const Solver &, std::vector<double> &);
 // One (nx, nu) instantiation of the run-time-horizon stream kernel (admm_streamg.hip.h).
@@ -172,6 +188,7 @@ struct Switches {
          no_uni = false, no_os = false, lean_one = false,   // lean_one: TINYMPC_HIP_LEAN_ONE — the lean kernel's 512-register variant at any batch
          no_jit = false,                                    // TINYMPC_HIP_NO_JIT: no unit specialised at setup, loaded or not
          lean_dense = false,                                // TINYMPC_HIP_LEAN_DENSE: the lean kernel's dense sweeps only (no sparse form)
+         lean_unscaled = false,                             // TINYMPC_HIP_LEAN_UNSCALED: the lean kernel's sparse sweeps on the model as given, never the diagonally scaled one (the A/B switch)
          lean_ws = false,                                   // TINYMPC_HIP_LEAN_WS: warm / kept-workspace solves and mpc_rollout on the lean kernel
          lean_loop = false,                                 // TINYMPC_HIP_LEAN_LOOP: with lean_ws, mpc_rollout as one launch of the lean kernel's in-kernel loop
          stream_f64 = false,                                // TINYMPC_HIP_STREAM_F64: precision 2 on the stream kernel's fp64-state form where it is built
@@ -281,6 +298,8 @@ struct Solver {
     bool lean_ok = false, lean_knot_bounds = false;
     bool lean_enabled = true;             // TINYMPC_HIP_NO_LEAN, read once at creation
     uint64_t lean_sp = 0;                 // the (A, B) pattern of the model (lean_pattern), set with the pack
+    bool lean_scaled_ok = false;          // the pack's scaled block is valid for this model (build_lean_pack)
+    bool last_lean_scaled = false;        // the most recent launch ran a scaled sparse kernel
     int last_lean_form = LF_NONE;         // the sweeps of the most recent launch (LF_*), and the per-knot fp64 costs it
     int last_lean_cost[2] = {0, 0};       // weighed: the sparse form's (its pattern's), the form it replaces
     std::string last_launch_name;         // the kernel the most recent launch actually ran (family or its lean variant)

@@ -366,6 +366,7 @@ Switches read_switches() {
     w.no_os = on("TINYMPC_HIP_NO_OS");
     w.lean_one = on("TINYMPC_HIP_LEAN_ONE");
     w.lean_dense = on("TINYMPC_HIP_LEAN_DENSE");
+    w.lean_unscaled = on("TINYMPC_HIP_LEAN_UNSCALED");
     w.lean_ws = on("TINYMPC_HIP_LEAN_WS");
     w.lean_loop = on("TINYMPC_HIP_LEAN_LOOP");
     w.stream_f64 = on("TINYMPC_HIP_STREAM_F64");
@@ -717,10 +718,11 @@ int Solver::upload_packs() {
     if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise && !bounds_mode) lean_jit = true;
     std::fill(le_var_tried, le_var_tried + LV_COUNT, false);
     lean_ok = false;
+    lean_scaled_ok = false;
     lean_sp = lean_pattern(A, B);
     if (le || lean_jit) {
         std::vector<double> lp;
-        if (build_lean_pack(*this, lp)) {
+        if (build_lean_pack(*this, lp, &lean_scaled_ok)) {
             if (!le && (!ke || ke->G != 1)) append_lean_bounds(*this, lp);   // (the selected entry's bound pack is not the one-lane one)
             if (dev_alloc(d_lean, lp.size())) return -1;
             HIP_TRY(hipMemcpy(d_lean, lp.data(), lp.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1445,7 +1447,8 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
         P.ib_hx = (long)batch * nx * (bounds_mode == 2 ? N : 1), P.ib_hu = (long)batch * nu * (bounds_mode == 2 ? N - 1 : 1);
         P.ib_on = (st.en_state_bound ? IB_STATE : 0) | (st.en_input_bound ? IB_INPUT : 0);
     }
-    P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0);
+    P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0) |
+                   (lean_ok && lean_scaled_ok && !sw.lean_unscaled ? HF_LEAN_SCALED : 0);
 }
 
 int Solver::ensure_mpc_log(int mpc_steps) {
@@ -1543,6 +1546,7 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
     }
     last_launch_name = lean ? lk->name : kernel_name;
     last_lean_form = lean ? plan.form : LF_NONE;
+    last_lean_scaled = lean && lean_runs_scaled(lk, plan.variant, P.host_flags);
     last_lean_cost[0] = lean ? plan.cost_sparse : 0;
     last_lean_cost[1] = lean ? plan.cost_dense : 0;
     // the status block stays on the device; solve_status() fetches it when asked (nothing but the kernel and the
@@ -2340,6 +2344,10 @@ extern "C" int tmpc_lean_last_form(tinympc_solver *s, unsigned long long *patter
     if (form) *form = s->s.last_lean_form;
     return 0;
 }
+
+// (test hook like the one above) whether the solver's most recent launch ran a scaled sparse kernel of the lean family
+// (admm_params.h: lean_pattern_scaled): 1 / 0, -1 without a solver
+extern "C" int tmpc_lean_last_scaled(tinympc_solver *s) { return s ? (s->s.last_lean_scaled ? 1 : 0) : -1; }
 
 // (test hook like the one above) the number of solve-kernel launches the solver's last mpc_rollout took: `steps` for the
 // chains of launches, 1 for any in-kernel loop, -1 before any rollout
