@@ -5,7 +5,8 @@ next to round 3's census of quad<4,1,20,g1>.  From r06 on the benchmark runs the
 dense (controller-Hessenberg, SP = 0) instantiation that TINYMPC_HIP_LEAN_DENSE=1 runs is counted beside it.  TMPC_CENSUS_ASM: an
 existing hipcc -S output of the unit to count instead of compiling it.  From r21 on the benchmark runs the scaled sparse kernel
 (csrc/linst_4_1_20_scaled.hip, the scaled cartpole pattern): that unit is compiled and counted, with the unscaled sparse kernel's
-committed census (profiles/r16_cartpole_isa_census.json) beside it.  Output: profiles/<tag>_cartpole_isa_census.json"""
+committed census (profiles/r16_cartpole_isa_census.json) beside it; from r22 on that kernel folds C into the costate's scale and
+r21's census stands beside it too.  Output: profiles/<tag>_cartpole_isa_census.json"""
 import collections, json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
@@ -91,6 +92,13 @@ if "scaled" in res:
     out["unscaled_sparse_r16"] = {k: prev[k] for k in ("instructions_per_iteration", "valu_instructions", "necessary_fp64_fma", "by_class")}
     for k in ("round3_quad_g1", "round4_lean_dense"):
         out.pop(k, None)
+    if tag >= "r22":   # C folded into the costate's scale (admm_lean.hip.h: FOLD): the same kernel symbol, r21's census beside it
+        out["coordinates"] = ("diagonally scaled, x^ = S x, the costate carried as pv = c p^ with the scalar c = C = -rho Quu_inv: "
+                              "u = -K^ x^ - d, x^+ = A^ x^ + B^ u; d = c r~ + B^' pv (no product by C), pv = c W x^ + A^' pv - K^' d; "
+                              "24 fp64 per knot for 25")
+        prev = json.load(open(os.path.join(ROOT, "profiles", "r21_cartpole_isa_census.json")))
+        out["scaled_unfolded_r21"] = {k: prev[k] for k in ("instructions_per_iteration", "valu_instructions", "necessary_fp64_fma", "by_class")}
+        out["predicted_share_of_loop_removed"] = 1.0 - out["valu_instructions"] / prev["valu_instructions"]
 if "sparse" in res:
     out["kernel"] = ("lean<4,1,20> = admm_lean_kernel<4,1,20, LIVE=false, UBK=true, ONE=true, XB=false, REFS=zero, SP=cartpole pattern> "
                      "(the benchmark's instantiation)")

@@ -162,7 +162,14 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
     // backward recursion runs on p^ = S^-1 p~: a column starts fma(w_m, x^_m, <a unit term>), w = s^-2 beside the coefficients
     // in SGPRs.  u, d, t, r~, y, z and the clamp are input-space and unchanged; x = S^-1 x^ only at the stores, and the state
     // dual residual is max_m (max_k |x^_prev - x^_new|)_m / |s_m| (the maximum commutes with a positive scale).
+    // FOLD (SCL with one input): C = -rho Quu_inv is then a scalar c, and the costate's scale relative to x^ — which the diagonal
+    // scaling left free — takes it in: the recursion carries pv = c p^.  d_k = c r~_k + B^' pv_{k+1} needs no product by C (the
+    // one chain of the iteration that had no free start), pv_k = Wv x^_k + A^' pv_{k+1} - K^' d_k keeps the chains of p^_k with
+    // d_k where t_k stood, pv_{N-1} = Wv x^_{N-1}, and the pack's w holds Wv = c S^-2 (kernels.hip: build_lean_pack) —
+    // cartpole: 24 fp64 per knot for 25.  Only the costate, which is never stored, changes its scale: d, u, x^ and every
+    // fp32 quantity are what they were up to fp64 rounding.
     constexpr bool SCL = lsp_scaled(SP);
+    constexpr bool FOLD = SCL && NU == 1;
     static_assert(!SCL || (!XB && !WS && !F64 && REFS == REF_ZERO), "scaled pattern: one-shot, no state bound, zero references, fp32 state");
     static_assert(!SCL || L::NLOADS_Z <= 4, "scaled coefficient block too large for SGPRs");
     static_assert(!SPR || (NX <= 4 && NU <= 4), "sparse pattern: nx, nu <= 4");
@@ -258,7 +265,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 
     const SBlock<double, (SCL ? L::NLOADS_Z : L::NLOADS)> blk(P.lean + (HB ? L::O_H : (SCL ? L::O_Z : (SPR ? L::O_S : 0))));   // (SPR: A where M is)
     const auto cM = blk.at(L::O_M), cK = blk.at(L::O_K), cB = blk.at(L::O_B), cC = blk.at(L::O_C);
-    const auto cW = blk.at(SCL ? L::O_W : 0);                                   // SCL: w = s^-2
+    const auto cW = blk.at(SCL ? L::O_W : 0);                                   // SCL: w = s^-2 (FOLD: c s^-2)
 
     ST lo[NU], hi[NU];
 #pragma unroll
@@ -703,6 +710,22 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
                 if constexpr (REFS == REF_SHARED) r[a] += s_cr[k * NU + a];     //      + R~ uref / rho
                 t[a] = r[a];
             }
+            if constexpr (FOLD) {
+                // d_k = c r~_k + B^' pv_{k+1}, two operations for cartpole.  r~_k has been in registers since the forward
+                // sweep and every pv_{k+1}[j] ends in the product by d_{k+1}, so the costates are what the chain waits for:
+                // the one at B^'s unit enters first, as the addend of the product c r~ — fma(c, r~, pv_j), nothing is
+                // multiplied by C afterwards — and the one with a coefficient of its own enters LAST (cartpole: pv_3 then
+                // B^_1 pv_1; the other order, fma(c, r~, fma(B^_1, pv_1, pv_3)), needs both costates at its first operation)
+                bool begun = false;
+#pragma unroll
+                for (int j = 0; j < NX; ++j)
+                    if (b_nz(j, 0) && b_one(j, 0)) t[0] = fma(cC[0], r[0], p[j]), begun = true;
+                if (!begun) t[0] = cC[0] * r[0];
+#pragma unroll
+                for (int j = 0; j < NX; ++j)
+                    if (b_nz(j, 0) && !b_one(j, 0)) t[0] = fma(cB[j * NU], p[j], t[0]);
+                D[k][0] = (DT)t[0];                                             // (t is d from here on: K^' d = c K^' t below)
+            } else {
 #pragma unroll
             for (int j = 0; j < NX; ++j)
 #pragma unroll
@@ -714,6 +737,7 @@ __global__ __launch_bounds__(256, (ONE ? 1 : 2)) void admm_lean_kernel(const Adm
 #pragma unroll
                 for (int c = 1; c < NU; ++c) acc = fma(cC[a * NU + c], t[c], acc);
                 D[k][a] = (DT)acc;
+            }
             }
             if constexpr (k > 0 && SPR) {                                       // p~_k = q~_k + A' p~_{k+1} - Kinf' t_k
                 double ap[NX];

@@ -136,7 +136,8 @@ struct LeanLayout {
     int total;
     // appended behind everything above (no earlier offset moves): the block of the diagonally scaled model x^ = S x
     // (lean_pattern_scaled below) — [S A S^-1, Kinf S^-1, S B, C] in the layout of the others, w = diag(S)^-2 [nx] behind C at
-    // oW, padded to whole scalar loads (padZ) — then s [nx] and 1 / s [nx], read at entry, at the residuals and at the store
+    // oW (nu = 1: c diag(S)^-2 with the scalar c = C, which the costate's scale takes in — admm_lean.hip.h: FOLD), padded to whole
+    // scalar loads (padZ) — then s [nx] and 1 / s [nx], read at entry, at the residuals and at the store
     int oZ, oW, padZ, oSc, oSi;
 };
 constexpr LeanLayout lean_layout(int nx, int nu) {
@@ -230,6 +231,10 @@ constexpr int lean_cost_scaled(uint64_t sp, int nx, int nu) {
     }
     return c;
 }
+// ... and of the form the kernel runs at nu = 1, where C is a scalar c folded into the costate's scale (admm_lean.hip.h: FOLD;
+// the pack's w is then c s^-2): d = c r~ + B^' pv starts from a product it needed anyway, so the product by C goes.  The choice of
+// the pattern (lean_pattern_scaled, lean_scale_model) stays on lean_cost_scaled: the two differ by a constant per nu
+constexpr int lean_cost_folded(uint64_t sp, int nx, int nu) { return lean_cost_scaled(sp, nx, nu) - (nu == 1 ? 1 : 0); }
 // The scaled pattern of a model's pattern sp (positions only, not values): the off-diagonal nonzeros of A made units — a set
 // that is acyclic as an undirected graph on the states (a cycle's product is invariant under the scaling), so at most
 // nx - 1 of them — and at most one nonzero of B, chosen by plain enumeration (at most 12 candidates at nx <= 4) to minimise

@@ -121,6 +121,21 @@ void lean_scaled_coefficients(uint64_t sz, int nx, int nu, const double *A, cons
         for (int a = 0; a < nu; ++a)
             for (int j = 0; j < nx; ++j) Kh[a * nx + j] = K[a * nx + j] / s[j];
 }
+// ... and the pack's scaled block z = [A^, K^, B^, C, w] (admm_params.h: LeanLayout, oM .. oW relative to it) of the model's
+// A, B, Kinf and C = -rho Quu_inv.  w = diag(S)^-2 — and, at nu = 1, c diag(S)^-2 with the scalar c = C: the kernel then carries
+// the costate as c p^ and never multiplies by C (admm_lean.hip.h: FOLD; C itself stays in the block, the product c r~ reads it).
+// false — the launch keeps the unscaled kernel — where a w is not finite, or at nu = 1 zero (c = 0: no such scale)
+bool lean_scaled_block(uint64_t sz, int nx, int nu, const double *A, const double *B, const double *K, const double *C, const double *s,
+                       double *z) {
+    const LeanLayout L = lean_layout(nx, nu);
+    lean_scaled_coefficients(sz, nx, nu, A, B, K, s, z + L.oM, z + L.oB, z + L.oK);
+    for (int i = 0; i < nu * nu; ++i) z[L.oC + i] = C[i];
+    for (int i = 0; i < nx; ++i) {
+        z[L.oW + i] = nu == 1 ? C[0] / (s[i] * s[i]) : 1.0 / (s[i] * s[i]);
+        if (!std::isfinite(z[L.oW + i]) || (nu == 1 && z[L.oW + i] == 0.0)) return false;
+    }
+    return true;
+}
 
 bool build_lean_pack(const Solver &sv, std::vector<double> &out, bool *scaled) {
     const int nx = sv.nx, nu = sv.nu;
@@ -173,16 +188,13 @@ bool build_lean_pack(const Solver &sv, std::vector<double> &out, bool *scaled) {
         double s[4];
         const uint64_t sz = lean_scale_model(sv.le->sp, nx, nu, out.data() + L.oS + L.oM, out.data() + L.oS + L.oB, s);
         if (sz && sz == sv.le->sp_scaled) {
-            double *z = out.data() + L.oZ;
-            lean_scaled_coefficients(sz, nx, nu, out.data() + L.oS + L.oM, out.data() + L.oS + L.oB, out.data() + L.oS + L.oK, s,
-                                     z + L.oM, z + L.oB, z + L.oK);
-            for (int i = 0; i < nu * nu; ++i) z[L.oC + i] = out[L.oC + i];
+            const bool ok = lean_scaled_block(sz, nx, nu, out.data() + L.oS + L.oM, out.data() + L.oS + L.oB, out.data() + L.oS + L.oK,
+                                              out.data() + L.oC, s, out.data() + L.oZ);
             for (int i = 0; i < nx; ++i) {
-                z[L.oW + i] = 1.0 / (s[i] * s[i]);
                 out[L.oSc + i] = s[i];
                 out[L.oSi + i] = 1.0 / s[i];
             }
-            if (scaled) *scaled = true;
+            if (scaled) *scaled = ok;
         }
     }
     return true;
@@ -303,6 +315,24 @@ extern "C" unsigned long long tmpc_lean_scale_model(int nx, int nu, const double
     const uint64_t sz = tmpc::lean_scale_model(built, nx, nu, A, B, s);
     if (sz) tmpc::lean_scaled_coefficients(sz, nx, nu, A, B, nullptr, s, Ah, Bh, nullptr);
     return sz;
+}
+// the per-knot fp64 cost of the form the scaled kernels run (admm_params.h: lean_cost_folded); the scaled block [A^, K^, B^, C, w]
+// build_lean_pack writes for a model — row-major A, B, Kinf [nu][nx], C = -rho Quu_inv [nu][nu] — under the kernel of
+// lean_pattern_scaled(built) (built = 0: the model's own pattern): returns its length nx nx + 2 nu nx + nu nu + nx and fills
+// out, 0 where the model keeps the unscaled sweeps, -1 on bad arguments or cap too small
+extern "C" int tmpc_lean_folded_cost(int nx, int nu, unsigned long long sz) {
+    return (nx < 1 || nu < 1 || nx > 4 || nu > 4 || !tmpc::lsp_scaled(sz)) ? -1 : tmpc::lean_cost_folded(sz, nx, nu);
+}
+extern "C" int tmpc_lean_scaled_block(int nx, int nu, const double *A, const double *B, const double *K, const double *C,
+                                      unsigned long long built, double *out, int cap) {
+    if (nx < 1 || nu < 1 || nx > 4 || nu > 4 || !A || !B || !K || !C || !out) return -1;
+    const tmpc::LeanLayout L = tmpc::lean_layout(nx, nu);
+    if (cap < L.len + nx) return -1;
+    if (!built) built = tmpc::lean_pattern_rm(nx, nu, A, B);
+    double s[4];
+    const uint64_t sz = tmpc::lean_scale_model(built, nx, nu, A, B, s);
+    if (!sz || !tmpc::lean_scaled_block(sz, nx, nu, A, B, K, C, s, out)) return 0;
+    return L.len + nx;
 }
 extern "C" int tmpc_lean_covers(unsigned long long built, unsigned long long model) { return tmpc::lean_pattern_covers(built, model) ? 1 : 0; }
 extern "C" int tmpc_lean_pick_form(int nx, int nu, unsigned long long built, unsigned long long model, int one, int live, int xb) {
