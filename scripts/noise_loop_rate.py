@@ -3,7 +3,7 @@
 
   hostdrawn  the only way before set_process_noise: rng.standard_normal . G in numpy, [batch][steps][nx] doubles, set_disturbance,
              mpc_rollout; timed from the draw to the end of the loop
-  device     set_process_noise once, then mpc_rollout: plant_step_noise_kernel draws on the device; timed from the setter's call
+  device     set_process_noise once, then mpc_rollout: plant_step_kernel<true> draws on the device; timed from the setter's call
              (a seed per loop, as a sweep would set one) to the end of the loop
   resident   the rollout alone with the disturbance already resident (set before the clock starts): device - resident per step
              is what the generator costs over reading an uploaded row

@@ -4,7 +4,7 @@ three arms:
 
   host    the loop a caller steps itself: set_x0_f32 -> solve -> get_controls_f32 per step, the per-instance plant and the
           disturbance applied in numpy (batched matmul, fp64)
-  own     set_plant + set_disturbance, then mpc_rollout: the chain of kept-workspace launches with plant_step_own_kernel
+  own     set_plant + set_disturbance, then mpc_rollout: the chain of kept-workspace launches with plant_step_kernel
   model   for context only: mpc_rollout on the model plant, the loop the shape takes today (no plant, no disturbance)
 
 on two workloads, warm started, tolerance 1e-3, max_iter 10, check_termination 1 (those of profiles/r10_tracking_loop.txt):

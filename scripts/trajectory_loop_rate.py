@@ -6,7 +6,7 @@ arms:
           per-instance window (tinympc.ref_window, [batch][N][nx] floats uploaded), set_x0_f32 -> solve -> get_controls_f32, the
           model plant in numpy (fp64)
   traj    set_ref_trajectory, then mpc_rollout: the chain of kept-workspace launches with ref_window_kernel before and
-          plant_step_own_kernel after every launch; nothing uploaded per step
+          plant_step_kernel after every launch; nothing uploaded per step
   const   the same chain with CONSTANT per-instance references (set_x_ref / set_u_ref of window 0, an all-zero disturbance to
           take the own-plant chain): traj - const per step is what the window kernel and its launch cost
 

@@ -1,5 +1,5 @@
 """mpc_rollout under seeded process and measurement noise drawn on the device (BatchSolver.set_process_noise /
-set_measurement_noise; csrc/noise.h, csrc/solver.hip: noise_fill_kernel, measure_kernel, plant_step_noise_kernel).
+set_measurement_noise; csrc/noise.h, csrc/solver.hip: noise_fill_kernel, measure_kernel, plant_step_kernel<true>).
 
 The rule, with the noise cursor c and loop step s, t = c + s: the solve of step s starts from float32(x_t + G_v xi_v[b][t]), x_t
 the fp64 plant state; the plant step is x+ = ((f_p + A_p x + B_p u0) + w) + G_w xi_w[b][t]; the x log, x0d and x0 hold the true

@@ -1,5 +1,5 @@
 """mpc_rollout against a plant of its own (BatchSolver.set_plant) and under an additive disturbance (set_disturbance): the chain
-of `steps` ordinary kept-workspace launches with plant_step_own_kernel between them (csrc/solver.hip, rollout_chain_own), on
+of `steps` ordinary kept-workspace launches with plant_step_kernel between them (csrc/solver.hip, rollout_chain), on
 whatever kernel such a solve takes — no environment switch.
 
 The step rule: the plant state is carried in fp64, the applied control is the fp32 value the solution holds,
@@ -25,9 +25,13 @@ states are asserted finite and bounded (row by row at most twice the excursion o
      launches) and its results
  (i) mpc_rollout(3) twice with the disturbance re-set to rows 3..5 in between is mpc_rollout(6), bit for bit
  (j) refusals, by a word of their message, each followed by a plain solve
+ (k) the step rule to the bit: the chain against the same launches stepped from the host, the plant step in libm's fma in the
+     documented order — every log, the status and x0 equal element for element
 
 Batch 70 (one full stream workgroup and a ragged wavefront), 5 steps.  Every test fails without the feature: set_plant does not
 exist there."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -578,3 +582,87 @@ def test_global_forms(hip_lib, monkeypatch):
         assert t.solve(s) in (0, 1)
     finally:
         t.cleanup()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# (k) the step rule, to the bit
+# ---------------------------------------------------------------------------------------------------------------------------
+_LIBM_FMA = ctypes.CDLL("libm.so.6").fma
+_LIBM_FMA.restype = ctypes.c_double
+_LIBM_FMA.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double]
+
+
+def _rule_row(A, Bm, f, x, u0, r):
+    """row r of f + A x + B u0 as plant_step_kernel sums it: from f[r], A's row by ascending column, then B's, one fma each"""
+    acc = float(f[r])
+    for j in range(x.size):
+        acc = _LIBM_FMA(A[r, j], x[j], acc)
+    for a in range(u0.size):
+        acc = _LIBM_FMA(Bm[r, a], u0[a], acc)
+    return acc
+
+
+def _bits_case(name):
+    """(case, under TINYMPC_HIP_STREAM_MPC): the builders above; the noise factors are tests/test_noise_loop_gpu.py's"""
+    if name == "rocket12_model":
+        return {k: v for k, v in _case("rocket12").items() if k != "plant"}, True
+    if name == "cartpole17_plant_noise":
+        from tests.test_noise_loop_gpu import _ncase
+        return _ncase("cartpole17_plant"), False
+    return _case(name), False
+
+
+@pytest.mark.parametrize("name", ["cartpole17_plant", "rocket12_model", "cartpole_families", "cartpole17_plant_noise"])
+def test_step_rule_bits(hip_lib, monkeypatch, name):
+    """mpc_rollout(STEPS) on the stream kernel (precision 0, every launch from the fp32 d_x0) against the same loop stepped from
+    the host on a second, identical solver — set_x0 of the fp32 state, solve, the fp32 controls[:, 0, :] — advanced by the rule in
+    fp64 on the host: acc = f[r], A's row by ascending column, B's row, one libm fma each, + w[r], + (G_w xi_w)[r] last; the next
+    solve from (float)(acc + (G_v xi_v[t + 1])[r]).  The realised G xi are get_noise's, the device's own function.  Everything is
+    equal element for element.  Batch 70: at nx = 4 one full 64-instance workgroup of the step kernel and a ragged one, at
+    nx = 6 42 instances per workgroup and 4 idle lanes.
+      cartpole17_plant        per-instance plant and per-instance disturbance
+      rocket12_model          no plant installed, TINYMPC_HIP_STREAM_MPC=1: the model with f != 0, cones
+      cartpole_families       a disturbance alone: every instance's own model block
+      cartpole17_plant_noise  process (shared G_w) and measurement (per-instance G_v) noise; the measured log too"""
+    case, mpc = _bits_case(name)
+    prob = case["prob"]
+    _env(monkeypatch, case, mpc=mpc)
+    bs = _solver(case)
+    if "gw" in case:
+        from tests.test_noise_loop_gpu import _install_noise
+        _install_noise(bs, case)
+    bs.set_x0(case["x0"])
+    log = bs.mpc_rollout(STEPS)
+    assert bs.last_launch_name == case["name"] and _launches(bs) == STEPS and bs.effective_precision == 0
+    got = _collect(bs, log)
+    nw, nv = (bs.get_noise(0, 0, STEPS), bs.get_noise(1, 0, STEPS)) if "gw" in case else (None, None)
+    bs.close()
+
+    hs = _solver(case, own=False)
+    x = np.array(_f32(case["x0"]), dtype=np.float64)
+    plants = [_plant_of(case, b) for b in range(B)]
+    for k in range(STEPS):
+        y = _f32(x if nv is None else x + nv[:, k, :])
+        hs.set_x0(y)
+        hs.solve()
+        u0, st = hs.get_solution()["controls"][:, 0, :], hs.get_status()
+        nxt = np.zeros_like(x)
+        for b in range(B):
+            A, Bm, f = plants[b]
+            for r in range(prob.nx):
+                acc = _rule_row(A, Bm, f, x[:, b], u0[:, b], r)
+                if "w" in case:
+                    acc = acc + float(_w_of(case, b, k)[r])
+                if nw is not None:
+                    acc = acc + float(nw[r, k, b])
+                nxt[r, b] = acc
+        x = nxt
+        if nv is not None:
+            assert np.array_equal(log["y"][:, k, :], y), f"{name}: step {k}, measured state"
+        assert np.array_equal(log["u"][:, k, :], u0), f"{name}: step {k}, u log"
+        assert np.array_equal(log["x"][:, k, :], _f32(x)), f"{name}: step {k}, x log"
+        assert np.array_equal(log["iter"][k], st["iter"]) and np.array_equal(log["solved"][k], st["solved"]), f"{name}: step {k}, iter / solved"
+    assert hs.last_launch_name == case["name"]
+    hs.close()
+    assert np.array_equal(got["x0"], _f32(x).T.astype(np.float32)), f"{name}: x0 after the loop"
+    assert np.abs(log["u"]).max() > 0.0 and len(np.unique(log["x"][:, -1, :])) > B

@@ -1,7 +1,7 @@
 """Reference trajectories windowed on the device (BatchSolver.set_ref_trajectory): with the cursor c the references of a solve
 are x_ref[k] = x_traj[min(c + k, Lx - 1)], u_ref[k] = u_traj[min(c + k, Lu - 1)] (tinympc.ref_window), cut out of the
 device-resident trajectory by ref_window_kernel (csrc/solver.hip) before a plain solve and before every step of mpc_rollout,
-which such a solver runs as the own-plant chain (rollout_chain_own) and which leaves the cursor `steps` further on.
+which such a solver runs as the own-plant chain (rollout_chain) and which leaves the cursor `steps` further on.
 
 The reference is orc64, one persistent oracle per instance, stepped in numpy fp64 by the chain's rule: set_x0(f32(x)),
 set_x_ref(ref_window(x_traj, c + t, N)), set_u_ref(ref_window(u_traj, c + t, N - 1)), solve, x+ = f_p + A_p x + B_p f32(u0) (+ w).

@@ -1,6 +1,6 @@
 """mpc_rollout on the stream and generic kernels (csrc/admm_streamg.hip.h, csrc/admm_generic.hip.h) behind
 TINYMPC_HIP_STREAM_MPC=1 — the chain of `steps` workspace-carrying launches with the generalised plant step between them
-(Solver::rollout_steps, plant_step_affine_kernel) — and, with TINYMPC_HIP_STREAM_LOOP=1 beside it, ONE launch of the stream
+(Solver::rollout_chain, plant_step_kernel) — and, with TINYMPC_HIP_STREAM_LOOP=1 beside it, ONE launch of the stream
 kernel's in-kernel loop (admm_streamg_mpc_kernel) where one is built.
 
 The step rule at every precision: the plant state is carried in fp64, the applied control is the fp32 value the solution

@@ -288,7 +288,7 @@ namespace tmpc {
 //
 // MPC: the closed loop inside the launch (TINYMPC_HIP_STREAM_LOOP; workspace-keeping form, fixed rho, four lanes, fp64
 // recurrences).  P.mpc_steps warm solves, each followed by the plant step the chain of launches takes between two of them
-// (Solver::rollout_steps, plant_step_affine_kernel): u0 = the fp32 control of knot 0, x+ = f + A x + B u0 in fp64 — f, then
+// (Solver::rollout_chain, plant_step_kernel): u0 = the fp32 control of knot 0, x+ = f + A x + B u0 in fp64 — f, then
 // A's row by ascending column, then B's, one fma each — on the fp64 plant state in P.x0d, each lane its own rows, the other
 // lanes' x_j and u_a by quad broadcasts; the next solve starts from (float)x+ with the workspace as the scratch block
 // already holds it (what saving and reloading it would give: the kept arrays stay, the work arrays are zeroed), with the
@@ -1216,7 +1216,7 @@ __global__ __launch_bounds__(256)
 #if TMPC_STREAMG_MPC
     {
         // ---- one closed-loop step behind the solve (every lane of the wavefront is here: the loop above ends wave-wide) ----
-        double *const xplant = const_cast<double *>(P.x0d);   // the launch owns the plant state, as plant_step_affine_kernel does in the chain
+        double *const xplant = const_cast<double *>(P.x0d);   // the launch owns the plant state, as plant_step_kernel does in the chain
         float u0[RU];
         double xd[RX], u0d[RU], xn[RX];
 #pragma unroll

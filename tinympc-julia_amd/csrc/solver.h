@@ -424,55 +424,53 @@ struct Solver {
     // mpc_rollout.  plan_rollout decides the route, once and before anything is launched — every condition and every refusal
     // of a closed loop is there (solver.hip) — and solve_async launches it:
     //   Fused       the loop inside the selected kernel (the lanes-per-instance kernels, mfmat): one launch_pass
-    //   Chain       per step one workspace-carrying launch and the plant step, stream-ordered, the plant state kept in fp64 on
-    //               the device between steps (mfma; the lean kernel under TINYMPC_HIP_LEAN_WS; the stream / generic kernels
-    //               under TINYMPC_HIP_STREAM_MPC, stream_plant: f and per-instance families in the plant, the state resumed;
-    //               an own-plant solver, or one with a reference trajectory, on whatever kernel a kept-workspace solve of it
-    //               takes, no switch: rollout_chain_own)
+    //   Chain       per step one workspace-carrying launch and the plant step (plant_step_kernel), stream-ordered, the plant
+    //               state kept in fp64 on the device between steps: rollout_chain.  mfma and the lean kernel under
+    //               TINYMPC_HIP_LEAN_WS, whose launches read the fp64 state; from_x0 — the stream / generic kernels under
+    //               TINYMPC_HIP_STREAM_MPC, and an own-plant solver or one with a reference trajectory on whatever kernel a
+    //               kept-workspace solve of it takes, no switch — every launch from the fp32 state, the fp64 state resumed
     //   LeanLoop    ONE launch of the lean kernel's in-kernel loop (TINYMPC_HIP_LEAN_LOOP)
     //   StreamLoop  ONE launch of the stream kernel's (TINYMPC_HIP_STREAM_LOOP)
     //   Refused     the reason is the last error
     enum class Rollout { Refused, Fused, Chain, LeanLoop, StreamLoop };
     struct RolloutPlan {
         Rollout route = Rollout::Refused;
-        bool stream_plant = false;
-        bool own_plant = false;   // the chain on the plain-solve kernel, stepped by plant_step_own_kernel (a trajectory solver's too)
+        bool from_x0 = false;   // Chain: the launches start from the fp32 d_x0 (Pass::x0d null) and the fp64 plant state resumes (plant_start)
     };
     RolloutPlan plan_rollout(int mpc_steps);
-    int rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant);
-    int rollout_chain_own(hipStream_t stream, int mpc_steps);   // an own-plant solver's
+    int rollout_chain(hipStream_t stream, int mpc_steps, bool from_x0);
     int rollout_loop(hipStream_t stream, int mpc_steps, Rollout route);   // LeanLoop | StreamLoop
     int stream_ext() const { return lin_active() ? 2 : ((has_fdyn || cones_active()) ? 1 : 0); }   // the stream kernel's EXT of this solver
     int last_rollout_launches = -1;               // solve-kernel launches of the last mpc_rollout enqueued (-1: none has run)
-    double *d_plant = nullptr, *d_x0d = nullptr;  // [A | B | f] column-major fp64 (f: the affine term, follows set_fdyn); [B][nx] plant state
-    double *d_plant_het = nullptr;                // a per-instance-family solver: [batch][A_b | B_b] column-major fp64 (het_A, het_B)
-    bool plant_dirty = true;                      // d_plant is to be (re)written before the next chain
-    bool x0d_live = false;                        // d_x0d holds the plant state a stream / generic closed loop left (plant_start)
+    // The plant of every chain, one image: d_plant is [A | B | f] column-major fp64, one block or [batch] blocks plant_stride()
+    // apart — the installed plant (set_plant), else the model's A, B and affine term (a family solver: every instance's A_b, B_b
+    // and the shared f).  plant_dirty: to be (re)written by ensure_plant before the next chain — set_plant, set_fdyn, a re-batch.
+    double *d_plant = nullptr, *d_x0d = nullptr;  // (d_x0d: [B][nx] plant state)
+    bool plant_dirty = true;
+    bool x0d_live = false;                        // d_x0d holds the plant state a from_x0 chain or the stream loop left (plant_start)
     int plant_start(hipStream_t stream, bool resume);   // x0d <- x0, or (resume, x0d_live) the state the last loop left where x0 still is its rounding
     int ensure_plant();
     // A plant of its own (tinympc_set_plant) and an additive disturbance (tinympc_set_disturbance): what mpc_rollout steps when it
     // is not the model, x+ = f_p + A_p x + B_p u0 (+ w).  plant_kind / dist_kind 0: none, 1: shared, 2: per instance.  Host copies
     // are the caller's fp64 arrays as given (own_A [batch][nx*nx] etc. when per instance; dist_w nx x steps or [batch][steps][nx]);
-    // the device copies are fp64 too: d_own_plant [A | B | f] or [batch][A | B | f] — with a disturbance alone the model's (a
-    // family solver: every instance's own A_b, B_b, and fdyn) — and d_dist as given.  Either makes the solver an own-plant
+    // on the device the plant is d_plant's content and d_dist is the disturbance as given.  Either makes the solver an own-plant
     // solver, whose closed loop is the chain on the kernel a kept-workspace solve takes (plan_rollout).
     int plant_kind = 0, dist_kind = 0, dist_steps = 0;
     std::vector<double> own_A, own_B, own_f, dist_w;
-    double *d_own_plant = nullptr, *d_dist = nullptr;
-    bool own_plant_dirty = true;
+    double *d_dist = nullptr;
     bool own_plant() const { return plant_kind != 0 || dist_kind != 0 || noisy(); }
     bool own_plant_per_instance() const { return plant_kind == 2 || (plant_kind == 0 && hetero); }
+    long plant_stride() const { return own_plant_per_instance() ? (long)nx * nx + (long)nx * nu + nx : 0L; }
     int plant_mode() const { return plant_kind | (dist_kind == 1 ? 4 : (dist_kind == 2 ? 8 : 0)); }
     int set_plant(const double *A_, const double *B_, const double *f_, int per_instance);
     int set_disturbance(const double *w, int steps, int per_instance);
     void drop_own_plant();   // both pieces (a re-batch)
-    int ensure_own_plant();
     // Seeded process and measurement noise drawn on the device (tinympc_set_process_noise / _set_measurement_noise; the draw rule:
     // noise.h).  Index 0 process, 1 measurement; noise_kind 0: none, 1: a shared factor, 2: one per instance.  The factors G (nx x nx
     // column-major fp64, or [batch][nx*nx]) are kept as given on the host and the device; a draw is a pure function of (seed, kind,
     // instance, step t), t = noise_cursor + loop step, so nothing else is stored.  Either kind makes the solver an own-plant solver:
     // the solve of step t starts from (float)(x_t + G_v xi_v[b][t]) — logged in d_mpc_y [batch][steps][nx], allocated only while
-    // measurement noise is installed — and the plant step ends with (acc + w) + (G_w xi_w[b][t]) (plant_step_noise_kernel); x0d, the
+    // measurement noise is installed — and the plant step ends with (acc + w) + (G_w xi_w[b][t]) (plant_step_kernel's noise form); x0d, the
     // x log and x0 after the loop hold the true state.  One cursor serves both kinds; a loop leaves it steps further on.
     int noise_kind[2] = {0, 0};
     unsigned long long noise_seed[2] = {0, 0};

@@ -148,8 +148,6 @@ Solver::~Solver() {
     dev_free(d_sens);
     dev_free(d_lean);
     dev_free(d_plant);
-    dev_free(d_plant_het);
-    dev_free(d_own_plant);
     dev_free(d_dist);
     dev_free(d_xtraj);
     dev_free(d_utraj);
@@ -309,7 +307,7 @@ int Solver::init_families(const double *A_, const double *B_, const double *Q_, 
                           int nx_, int nu_, int N_, int batch_, int device_, int verbose_) {
     no_specialise = true;   // (a per-instance-family solver runs on the stream kernel: nothing to specialise at setup)
     if (init(A_, B_, Q_, R_, rho_[0], nx_, nu_, N_, batch_, device_, verbose_)) return -1;
-    hetero = true;
+    hetero = true, plant_dirty = true;   // (the plant image holds every instance's A_b, B_b)
     const size_t Bn = (size_t)batch, nxx = (size_t)nx * nx, nxu = (size_t)nx * nu, nuu = (size_t)nu * nu;
     het_A.assign(A_, A_ + Bn * nxx);
     het_B.assign(B_, B_ + Bn * nxu);
@@ -947,7 +945,6 @@ int Solver::set_fdyn(const double *f) {
     has_fdyn = nz;
     packs_dirty = true;
     plant_dirty = true;   // (the chained closed loop's plant carries f)
-    own_plant_dirty = true;   // (... and a disturbed model plant)
     return select_kernel() || ensure_extension_buffers();
 }
 
@@ -1174,17 +1171,17 @@ __global__ void residual_max_kernel(const float *res, long batch, uint32_t *gsta
 // preference:
 //   an own-plant solver (set_plant / set_disturbance) or one with a reference trajectory (set_ref_trajectory): the chain on
 //     whatever kernel a plain kept-workspace solve of it takes, selected as for a plain solve, every family and precision, no
-//     switch (rollout_chain_own); not with adaptive rho;
-//   the matrix-core kernel of the box-only shapes (mfma): the chain — per step one workspace-carrying launch and the plant
-//     step, stream-ordered, the plant state in fp64 on the device between them;
+//     switch, every launch from the fp32 state (RolloutPlan::from_x0); not with adaptive rho;
+//   the matrix-core kernel of the box-only shapes (mfma): the chain (rollout_chain, the one driver of every chain) — per step
+//     one workspace-carrying launch, here handed the fp64 plant state, and the plant step, stream-ordered;
 //   TINYMPC_HIP_LEAN_WS, where lean_plan takes a warm whole-batch launch (the calling pattern, whatever the iteration count):
 //     that chain on the lean kernel; with TINYMPC_HIP_LEAN_LOOP beside it ONE launch of the lean kernel's in-kernel loop
 //     (admm_lean.hip.h, MPC) — not with a reference sequence (the kernel stages the shared references once per launch), and
 //     only where the loop kernel of the calling pattern exists: the entry has it, or its specialisation compiled;
-//   the stream / generic kernels under their switch: that chain too — every precision, the affine term (in the plant as
-//     well), cones, linear rows, per-instance references and families; with TINYMPC_HIP_STREAM_LOOP beside it ONE launch of
-//     the stream kernel's in-kernel loop where one is built (admm_streamg.hip.h, MPC; not the generic kernel, precision 1, a
-//     shape or form without a loop kernel);
+//   the stream / generic kernels under their switch: that chain too, from the fp32 state — every precision, the affine term
+//     (in the plant as well), cones, linear rows, per-instance references and families; with TINYMPC_HIP_STREAM_LOOP beside it
+//     ONE launch of the stream kernel's in-kernel loop where one is built (admm_streamg.hip.h, MPC; not the generic kernel,
+//     precision 1, a shape or form without a loop kernel);
 //   else the loop fused into the selected kernel: the lanes-per-instance kernels, mfmat.
 // A loop that runs inside one launch takes a reference sequence only as one shared reference set per step.
 Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
@@ -1208,9 +1205,9 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
         return refuse("mpc_rollout: per-instance bounds have no closed loop by default (TINYMPC_HIP_STREAM_MPC=1 gives one as a chain of launches; or step it from the host)");
     if (own_plant() || traj_kind) {
         // a plant of its own or a disturbance: the chain on the kernel a plain kept-workspace solve takes (its launches ARE plain
-        // solves, every kernel family and precision has them), stepped by plant_step_own_kernel — ahead of the kernels' own routes.
+        // solves, every kernel family and precision has them) — ahead of the kernels' own routes.
         // A reference trajectory takes the same chain, against the model where no plant is installed: every launch is handed
-        // its step's window by ref_window_kernel, which no loop inside a kernel could be without an edit of that kernel
+        // its step's window by ref_window_kernel, which no loop inside a kernel is
         if (dist_kind && dist_steps < mpc_steps)
             return refuse("mpc_rollout: the disturbance holds " + std::to_string(dist_steps) + " steps, the loop asks for " + std::to_string(mpc_steps) +
                           " (one row per step, read from row 0)");
@@ -1226,7 +1223,7 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
             return refuse("mpc_rollout: the reference cursor would pass the largest int (set_ref_cursor: every cursor from the longer trajectory's last row on gives the same window)");
         if (select_kernel(false) || ensure_extension_buffers()) return rp;
         if ((packs_dirty && upload_packs()) || upload_refs()) return rp;
-        rp.route = Rollout::Chain, rp.own_plant = true;
+        rp.route = Rollout::Chain, rp.from_x0 = true;
         return rp;
     }
     if (select_kernel(true) || ensure_extension_buffers()) return rp;
@@ -1249,7 +1246,7 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
     }
     if (route != Rollout::Chain && ref_seq_steps > 0 && ref_mode != REF_SHARED)
         return refuse("mpc_rollout: per-step references need one shared reference set per step");
-    rp.route = route, rp.stream_plant = stream;
+    rp.route = route, rp.from_x0 = stream;
     return rp;
 }
 
@@ -1270,7 +1267,7 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     int rc = -1;
     switch (rp.route) {
     case Rollout::Fused: rc = launch_pass(stream, whole_batch(false, true, mpc_steps)); break;
-    case Rollout::Chain: rc = rp.own_plant ? rollout_chain_own(stream, mpc_steps) : rollout_chain(stream, mpc_steps, rp.stream_plant); break;
+    case Rollout::Chain: rc = rollout_chain(stream, mpc_steps, rp.from_x0); break;
     default: rc = rollout_loop(stream, mpc_steps, rp.route); break;
     }
     if (rc) return rc;
@@ -1569,7 +1566,7 @@ __global__ void plant_resume_kernel(double *x0d, const float *x0, long n) {
     if (i < n && (float)x0d[i] != x0[i]) x0d[i] = (double)x0[i];
 }
 
-// the fp64 plant state a closed loop outside the selected kernel starts from.  resume: the stream / generic routes, which go on
+// the fp64 plant state a closed loop outside the selected kernel starts from.  resume: the from_x0 chains and the stream loop, which go on
 // from the state an earlier loop of theirs left (x0d_live); every other route starts from x0
 int Solver::plant_start(hipStream_t stream, bool resume) {
     if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
@@ -1580,197 +1577,13 @@ int Solver::plant_start(hipStream_t stream, bool resume) {
     return 0;
 }
 
-// One closed-loop step after a solve (cartpole_example_mpc.jl:35-51): u0 = first column of the solution,
-// x0 <- A x0 + B u0 in fp64, logged like the quad kernel's fused loop does (iteration count signed by the solved flag).
-__global__ void plant_step_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved,
-                                  const double *AB, float *mpc_x, float *mpc_u, int *mpc_iter, int nx, int nu, int N,
-                                  long batch, int steps, int step) {
-    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    const double *A = AB, *Bm = AB + nx * nx;
-    const float *u0 = uout + b * (long)nu * (N - 1);
-    const long so = b * steps + step;
-    double xn[GEN_MAX_NX];
-    for (int r = 0; r < nx; ++r) {
-        double acc = 0.0;
-        for (int j = 0; j < nx; ++j) acc = fma(A[r + j * nx], x0d[b * nx + j], acc);
-        for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
-        xn[r] = acc;
-    }
-    for (int r = 0; r < nx; ++r) {
-        x0d[b * nx + r] = xn[r];
-        x0[b * nx + r] = (float)xn[r];
-        mpc_x[so * nx + r] = (float)xn[r];
-    }
-    for (int a = 0; a < nu; ++a) mpc_u[so * nu + a] = u0[a];
-    mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
-}
-
-// The stream / generic kernels' step (TINYMPC_HIP_STREAM_MPC): the same rule with the affine term and, on a per-instance-family
-// solver, every instance's own A_b, B_b (ABb: [batch][A_b | B_b], NULL: the family's AB) — x0 <- f + A x0 + B u0, the sum
-// started at f_r, then A's row by ascending column, then B's, one fma each.  With f = 0 that is plant_step_kernel's sum.
-__global__ void plant_step_affine_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved,
-                                         const double *AB, const double *ABb, float *mpc_x, float *mpc_u, int *mpc_iter, int nx,
-                                         int nu, int N, long batch, int steps, int step) {
-    // one thread per (instance, row), an instance's rows in one workgroup: every row reads the old state, a barrier, then the writes
-    const int per_block = (int)blockDim.x / nx, t = (int)threadIdx.x, r = t % nx;
-    const long b = (long)blockIdx.x * per_block + t / nx;
-    const bool on = t < per_block * nx && b < batch;
-    double acc = 0.0;
-    if (on) {
-        const double *A = ABb ? ABb + b * (long)(nx * nx + nx * nu) : AB, *Bm = A + nx * nx;
-        const float *u0 = uout + b * (long)nu * (N - 1);
-        acc = AB[nx * nx + nx * nu + r];
-        for (int j = 0; j < nx; ++j) acc = fma(A[r + j * nx], x0d[b * nx + j], acc);
-        for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
-    }
-    __syncthreads();
-    if (!on) return;
-    const long so = b * steps + step;
-    x0d[b * nx + r] = acc;
-    x0[b * nx + r] = (float)acc;
-    mpc_x[so * nx + r] = (float)acc;
-    for (int a = r; a < nu; a += nx) mpc_u[so * nu + a] = uout[b * (long)nu * (N - 1) + a];
-    if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
-}
-
-// the plant on the device: [A | B | f] (f as set_fdyn left it, zero without an affine term), per-instance families' [A_b | B_b]
+// The plant every chained closed loop steps, on the device: [A | B | f] column-major fp64, one block or — plant_stride() != 0 —
+// [batch] of them.  The installed plant (set_plant) where there is one; else the model: A, B and the affine term as set_fdyn
+// left it (zero without one), on a per-instance-family solver every instance's own A_b, B_b beside the shared f.  Whether a
+// disturbance, noise or a trajectory is installed does not enter.
 int Solver::ensure_plant() {
-    const size_t nab = (size_t)nx * nx + (size_t)nx * nu;
     if (d_plant && !plant_dirty) return 0;
     if (wait_last_launch()) return -1;   // (a chain still running reads it)
-    if (!d_plant && dev_alloc(d_plant, nab + nx)) return -1;
-    std::vector<double> ab(A.a);
-    ab.insert(ab.end(), B.a.begin(), B.a.end());
-    for (int r = 0; r < nx; ++r) ab.push_back(has_fdyn ? fdyn[r] : 0.0);
-    HIP_TRY(hipMemcpy(d_plant, ab.data(), ab.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (hetero && !d_plant_het) {
-        std::vector<double> abb((size_t)batch * nab);
-        for (size_t b = 0; b < (size_t)batch; ++b) {
-            std::copy(het_A.begin() + b * nx * nx, het_A.begin() + (b + 1) * nx * nx, abb.begin() + b * nab);
-            std::copy(het_B.begin() + b * nx * nu, het_B.begin() + (b + 1) * nx * nu, abb.begin() + b * nab + (size_t)nx * nx);
-        }
-        if (dev_alloc(d_plant_het, abb.size())) return -1;
-        HIP_TRY(hipMemcpy(d_plant_het, abb.data(), abb.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    plant_dirty = false;
-    return 0;
-}
-
-// The chain: per step one workspace-carrying launch and the plant step, stream-ordered.  stream_plant: the stream / generic
-// kernels' chain, whose every solve starts from the fp32 rounding in d_x0 (Pass::x0d null) and whose plant state goes on from
-// an earlier loop's; on the other kernels the launch reads the fp64 state itself.
-int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool stream_plant) {
-    if (ensure_plant() || plant_start(stream, stream_plant)) return -1;
-    // with a reference sequence every launch reads its step's slice of the sequence as its shared references (step 0's are the
-    // solver's own, which stay installed: nothing is copied, and the stream is not synchronised between steps)
-    const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
-    Pass pass = whole_batch(false, true);
-    pass.x0d = stream_plant ? nullptr : d_x0d;
-    for (int step = 0; step < mpc_steps; ++step) {
-        if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
-        if (launch_pass(stream, pass)) return -1;
-        if (stream_plant)
-            plant_step_affine_kernel<<<(unsigned)((batch + per_block - 1) / per_block), 256, 0, stream>>>(
-                d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, hetero ? d_plant_het : nullptr, d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N, (long)batch,
-                mpc_steps, step);
-        else
-            plant_step_kernel<<<(unsigned)((batch + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, d_mpc_x, d_mpc_u,
-                                                                               d_mpc_iter, nx, nu, N, (long)batch, mpc_steps, step);
-    }
-    HIP_TRY(hipGetLastError());
-    return record_done(stream);
-}
-
-// The step of an own-plant solver's chain (tinympc_set_plant / tinympc_set_disturbance): plant_step_affine_kernel's rule with the
-// coefficients of the plant instead of the model's and the disturbance added last — row r: acc = f_p[r], then A_p's row by
-// ascending column, then B_p's, one fma each; with a disturbance one fp64 add acc + w[r]; x0d = acc, x0 = mpc_x = (float)acc.
-// plant: [A | B | f] column-major fp64, instance b's block at plant + b * plant_stride (0: one shared block; an instance's
-// nx (nx + nu + 1) doubles are contiguous and row r of every column is lane r's, so a workgroup reads one contiguous span).
-// w: this step's row of the disturbance, instance b's at w + b * w_stride (0: shared); null: none.
-__global__ void plant_step_own_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved,
-                                      const double *plant, long plant_stride, const double *w, long w_stride, float *mpc_x,
-                                      float *mpc_u, int *mpc_iter, int nx, int nu, int N, long batch, int steps, int step) {
-    const int per_block = (int)blockDim.x / nx, t = (int)threadIdx.x, r = t % nx;
-    const long b = (long)blockIdx.x * per_block + t / nx;
-    const bool on = t < per_block * nx && b < batch;
-    double acc = 0.0;
-    if (on) {
-        const double *A = plant + b * plant_stride, *Bm = A + nx * nx;
-        const float *u0 = uout + b * (long)nu * (N - 1);
-        acc = Bm[nx * nu + r];
-        for (int j = 0; j < nx; ++j) acc = fma(A[r + j * nx], x0d[b * nx + j], acc);
-        for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
-        if (w) acc = acc + w[b * w_stride + r];
-    }
-    __syncthreads();
-    if (!on) return;
-    const long so = b * steps + step;
-    x0d[b * nx + r] = acc;
-    x0[b * nx + r] = (float)acc;
-    mpc_x[so * nx + r] = (float)acc;
-    for (int a = r; a < nu; a += nx) mpc_u[so * nu + a] = uout[b * (long)nu * (N - 1) + a];
-    if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
-}
-
-int Solver::set_plant(const double *A_, const double *B_, const double *f_, int per_instance) {
-    if (!A_ && !B_) {
-        if (plant_kind && wait_last_launch()) return -1;
-        plant_kind = 0;
-        own_A.clear(), own_B.clear(), own_f.clear();
-        own_plant_dirty = true;
-        if (!own_plant()) dev_free(d_own_plant);
-        return 0;
-    }
-    if (!A_ || !B_) {
-        set_error("set_plant: expected both A (nx x nx) and B (nx x nu), or neither to drop the plant");
-        return -1;
-    }
-    const size_t n = per_instance ? (size_t)batch : 1, na = (size_t)nx * nx, nb = (size_t)nx * nu;
-    own_A.assign(A_, A_ + n * na);
-    own_B.assign(B_, B_ + n * nb);
-    if (f_)
-        own_f.assign(f_, f_ + n * nx);
-    else
-        own_f.assign(n * nx, 0.0);
-    plant_kind = per_instance ? 2 : 1;
-    own_plant_dirty = true;
-    return 0;
-}
-
-int Solver::set_disturbance(const double *w, int steps, int per_instance) {
-    HIP_TRY(hipSetDevice(device));
-    if (wait_last_launch()) return -1;   // (a chain still running reads it)
-    if (!w || steps <= 0) {
-        dist_kind = 0, dist_steps = 0;
-        dist_w.clear();
-        dev_free(d_dist);
-        if (!own_plant()) dev_free(d_own_plant), own_plant_dirty = true;
-        return 0;
-    }
-    const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)steps * nx;
-    dist_w.assign(w, w + n);
-    if (dev_alloc(d_dist, n)) return -1;
-    HIP_TRY(hipMemcpy(d_dist, dist_w.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    dist_kind = per_instance ? 2 : 1, dist_steps = steps;
-    return 0;
-}
-
-void Solver::drop_own_plant() {
-    if (!own_plant()) return;
-    (void)wait_last_launch();
-    plant_kind = dist_kind = dist_steps = 0;
-    own_A.clear(), own_B.clear(), own_f.clear(), dist_w.clear();
-    dev_free(d_own_plant);
-    dev_free(d_dist);
-    own_plant_dirty = true;
-}
-
-// the own plant on the device: [A_p | B_p | f_p], shared or per instance; with a disturbance alone the model's — A, B and the
-// affine term, on a per-instance-family solver every instance's own A_b, B_b
-int Solver::ensure_own_plant() {
-    if (d_own_plant && !own_plant_dirty) return 0;
-    if (wait_last_launch()) return -1;
     const size_t na = (size_t)nx * nx, nb = (size_t)nx * nu, blk = na + nb + nx, n = own_plant_per_instance() ? (size_t)batch : 1;
     std::vector<double> h(n * blk);
     for (size_t b = 0; b < n; ++b) {
@@ -1786,14 +1599,63 @@ int Solver::ensure_own_plant() {
             for (int r = 0; r < nx; ++r) o[na + nb + r] = has_fdyn ? fdyn[r] : 0.0;
         }
     }
-    if (dev_alloc(d_own_plant, h.size())) return -1;
-    HIP_TRY(hipMemcpy(d_own_plant, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    own_plant_dirty = false;
+    if (dev_alloc(d_plant, h.size())) return -1;
+    HIP_TRY(hipMemcpy(d_plant, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    plant_dirty = false;
     return 0;
 }
 
+int Solver::set_plant(const double *A_, const double *B_, const double *f_, int per_instance) {
+    if (!A_ && !B_) {
+        plant_kind = 0;
+        own_A.clear(), own_B.clear(), own_f.clear();
+        plant_dirty = true;   // (back to the model's; ensure_plant waits for a chain still reading the image)
+        return 0;
+    }
+    if (!A_ || !B_) {
+        set_error("set_plant: expected both A (nx x nx) and B (nx x nu), or neither to drop the plant");
+        return -1;
+    }
+    const size_t n = per_instance ? (size_t)batch : 1, na = (size_t)nx * nx, nb = (size_t)nx * nu;
+    own_A.assign(A_, A_ + n * na);
+    own_B.assign(B_, B_ + n * nb);
+    if (f_)
+        own_f.assign(f_, f_ + n * nx);
+    else
+        own_f.assign(n * nx, 0.0);
+    plant_kind = per_instance ? 2 : 1;
+    plant_dirty = true;
+    return 0;
+}
+
+int Solver::set_disturbance(const double *w, int steps, int per_instance) {
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;   // (a chain still running reads it)
+    if (!w || steps <= 0) {
+        dist_kind = 0, dist_steps = 0;
+        dist_w.clear();
+        dev_free(d_dist);
+        return 0;
+    }
+    const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)steps * nx;
+    dist_w.assign(w, w + n);
+    if (dev_alloc(d_dist, n)) return -1;
+    HIP_TRY(hipMemcpy(d_dist, dist_w.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    dist_kind = per_instance ? 2 : 1, dist_steps = steps;
+    return 0;
+}
+
+void Solver::drop_own_plant() {
+    if (!own_plant()) return;
+    (void)wait_last_launch();
+    plant_kind = dist_kind = dist_steps = 0;
+    own_A.clear(), own_B.clear(), own_f.clear(), dist_w.clear();
+    dev_free(d_dist);
+    plant_dirty = true;
+}
+
 // ---- noise drawn on the device (tinympc_set_process_noise / _set_measurement_noise; the rule: noise.h) ----
-// The three kernels share plant_step_own_kernel's layout — 256 / nx instances per workgroup, lane (instance, r) owns row r — and
+// The kernels here share plant_step_kernel's layout — 256 / nx instances per workgroup, lane (instance, r) owns row r — and
 // one way to the noise vector: the lanes r < ceil(nx / 2) of an instance draw its pair r (one Philox block and one Box-Muller
 // each, nothing drawn twice) into the workgroup's LDS, and after the barrier every lane takes its row of G xi (noise_row).
 // G: instance b's factor at G + b * g_stride (0: shared).  Every lane of the workgroup reaches the barrier.
@@ -1836,15 +1698,31 @@ __global__ void measure_kernel(float *x0, float *ylog, const double *x0d, const 
     ylog[(b * steps + step) * nx + r] = y;
 }
 
-// plant_step_own_kernel's rule with noise: row r is acc = f_p[r], A_p's row, B_p's row (one fma each), then the uploaded
-// disturbance if any, then the process draw last — acc = (acc + w[r]) + (G_w xi_w[b][t])[r] (Gw null: none); x0d = acc and
-// mpc_x = (float)acc, the true state.  x0 = (float)acc too, unless Gv is given: then x0 and ylog[b][step + 1] take the NEXT
-// step's measurement (float)(acc + (G_v xi_v[b][t + 1])[r]), what measure_kernel would write ahead of that step's launch.
-__global__ void plant_step_noise_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved, const double *plant,
-                                        long plant_stride, const double *w, long w_stride, float *mpc_x, float *mpc_u, int *mpc_iter,
-                                        const double *Gw, long gw_stride, unsigned long long seed_w, const double *Gv, long gv_stride,
-                                        unsigned long long seed_v, float *ylog, int nx, int nu, int N, long batch, int steps, int step, int t) {
-    __shared__ double xi_w[256], xi_v[256];
+// The noise of one step (plant_step_kernel<true>): Gw / Gv null where that kind is not drawn in this launch; t = noise cursor + step
+struct StepNoise {
+    const double *Gw, *Gv;
+    long gw_stride, gv_stride;
+    unsigned long long seed_w, seed_v;
+    float *ylog;
+    int t;
+};
+
+// One closed-loop step behind a solve (cartpole_example_mpc.jl:35-51), the one rule of every chained closed loop:
+// x+ = f + A x + B u0 (+ w) (+ G_w xi_w) in fp64, u0 = the first column of the solution.  One thread per (instance, row), 256 / nx
+// instances per workgroup, lane (instance, r) owns row r: acc = f[r], then A's row by ascending column, then B's, one fma each;
+// with a disturbance one fp64 add acc + w[r]; the process draw last, acc + (G_w xi_w[b][t])[r]; every row has read the old state
+// at the barrier (which every lane reaches), then x0d = acc, mpc_x = (float)acc — the true state — the control and the iteration
+// count, signed by the solved flag, like the quad kernel's fused loop logs them.  x0 = (float)acc too, unless nz.Gv is given:
+// then x0 and ylog[b][step + 1] take the NEXT step's measurement (float)(acc + (G_v xi_v[b][t + 1])[r]), what measure_kernel
+// would write ahead of that step's launch.
+// plant: [A | B | f] column-major fp64, instance b's block at plant + b * plant_stride (0: one shared block; an instance's
+// nx (nx + nu + 1) doubles are contiguous and row r of every column is lane r's, so a workgroup reads one contiguous span).
+// w: this step's row of the disturbance, instance b's at w + b * w_stride (0: shared); null: none.
+// Two forms, because of what the draws cost: NOISE false reads nothing of nz and has no LDS; true holds the two draw buffers.
+template <bool NOISE>
+__global__ void plant_step_kernel(double *x0d, float *x0, const float *uout, const int *iter, const int *solved, const double *plant,
+                                  long plant_stride, const double *w, long w_stride, float *mpc_x, float *mpc_u, int *mpc_iter, StepNoise nz,
+                                  int nx, int nu, int N, long batch, int steps, int step) {
     const int per_block = (int)blockDim.x / nx, lane = (int)threadIdx.x, r = lane % nx;
     const long b = (long)blockIdx.x * per_block + lane / nx;
     const bool on = lane < per_block * nx && b < batch;
@@ -1857,33 +1735,40 @@ __global__ void plant_step_noise_kernel(double *x0d, float *x0, const float *uou
         for (int a = 0; a < nu; ++a) acc = fma(Bm[r + a * nx], (double)u0[a], acc);
         if (w) acc = acc + w[b * w_stride + r];
     }
-    if (Gw) acc = acc + noise_block_row(xi_w, Gw, gw_stride, seed_w, NOISE_PROCESS, b, (unsigned)t, nx, r, on);
     double next = acc;
-    if (Gv) next = acc + noise_block_row(xi_v, Gv, gv_stride, seed_v, NOISE_MEASUREMENT, b, (unsigned)t + 1u, nx, r, on);
+    if constexpr (NOISE) {
+        __shared__ double xi_w[256], xi_v[256];
+        if (nz.Gw) acc = acc + noise_block_row(xi_w, nz.Gw, nz.gw_stride, nz.seed_w, NOISE_PROCESS, b, (unsigned)nz.t, nx, r, on);
+        next = acc;
+        if (nz.Gv) next = acc + noise_block_row(xi_v, nz.Gv, nz.gv_stride, nz.seed_v, NOISE_MEASUREMENT, b, (unsigned)nz.t + 1u, nx, r, on);
+    }
     __syncthreads();   // (every row has read x0d)
     if (!on) return;
     const long so = b * steps + step;
     x0d[b * nx + r] = acc;
     x0[b * nx + r] = (float)next;
     mpc_x[so * nx + r] = (float)acc;
-    if (Gv) ylog[(so + 1) * nx + r] = (float)next;
+    if constexpr (NOISE)
+        if (nz.Gv) nz.ylog[(so + 1) * nx + r] = (float)next;
     for (int a = r; a < nu; a += nx) mpc_u[so * nu + a] = uout[b * (long)nu * (N - 1) + a];
     if (r == 0) mpc_iter[so] = solved[b] ? iter[b] : -iter[b];
 }
 
-// An own-plant solver's chain: per step the solver's ordinary kept-workspace launch — from the fp32 rounding in d_x0, Pass::x0d
-// null, what a host-stepped loop launches — and plant_step_own_kernel, stream-ordered; the fp64 state resumed as the stream chain's
-// With a reference trajectory every launch is handed its step's window first (ref_window_kernel, where the window on the device
-// is another), and the cursor is left mpc_steps further on.
-// With noise (tinympc_set_process_noise / _set_measurement_noise) the step is plant_step_noise_kernel instead, t = noise cursor +
-// step: it adds the process draw last, and — measurement noise — also writes the NEXT step's measurement into x0 (and the y log),
-// so only step 0's comes from measure_kernel ahead of the first launch; the last step leaves the true state's rounding in x0.
-// TINYMPC_HIP_NOISE_SPLIT (timing aid): measure_kernel ahead of every launch, the same values.  The noise cursor is left
-// mpc_steps further on.  Without noise: exactly the launches above.
-int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
-    if (ensure_own_plant() || plant_start(stream, true)) return -1;
+// The chain: per step one workspace-carrying launch and the plant step, stream-ordered, the plant state in fp64 on the device
+// between them.  from_x0: every launch is the solver's ordinary kept-workspace launch, from the fp32 rounding in d_x0 (Pass::x0d
+// null, what a host-stepped loop launches), and the fp64 state goes on from an earlier loop's (plant_start); otherwise — the
+// matrix-core and lean kernels' chains — the launch reads the fp64 state itself and the loop starts from x0.
+// With a reference sequence every launch reads its step's slice of the sequence as its shared references (step 0's are the
+// solver's own, which stay installed: nothing is copied, and the stream is not synchronised between steps).  With a reference
+// trajectory every launch is handed its step's window first (ref_window_kernel, where the window on the device is another),
+// and the cursor is left mpc_steps further on.
+// With noise the step is plant_step_kernel's noise form, t = noise cursor + step: with measurement noise it also writes the NEXT
+// step's measurement into x0 (and the y log), so only step 0's comes from measure_kernel ahead of the first launch; the last
+// step leaves the true state's rounding in x0.  TINYMPC_HIP_NOISE_SPLIT (timing aid): measure_kernel ahead of every launch,
+// the same values.  The noise cursor is left mpc_steps further on.
+int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool from_x0) {
+    if (ensure_plant() || plant_start(stream, from_x0)) return -1;
     const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
-    const long blk = (long)nx * nx + (long)nx * nu + nx;
     const unsigned step_groups = (unsigned)((batch + per_block - 1) / per_block);
     const bool measured = noise_kind[NOISE_MEASUREMENT] != 0;
     const long gw_stride = noise_kind[NOISE_PROCESS] == 2 ? (long)nx * nx : 0L, gv_stride = noise_kind[NOISE_MEASUREMENT] == 2 ? (long)nx * nx : 0L;
@@ -1895,6 +1780,7 @@ int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
         mpc_y_steps = mpc_steps;
     }
     Pass pass = whole_batch(false, true);
+    pass.x0d = from_x0 ? nullptr : d_x0d;
     for (int step = 0; step < mpc_steps; ++step) {
         if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
         if (traj_kind && ensure_ref_window(stream, ref_cursor + step)) return -1;
@@ -1904,20 +1790,20 @@ int Solver::rollout_chain_own(hipStream_t stream, int mpc_steps) {
         if (launch_pass(stream, pass)) return -1;
         const double *w = dist_kind ? d_dist + (size_t)step * nx : nullptr;
         const long w_stride = dist_kind == 2 ? (long)dist_steps * nx : 0L;
-        if (!noisy())
-            plant_step_own_kernel<<<step_groups, 256, 0, stream>>>(d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L,
-                                                                   w, w_stride, d_mpc_x, d_mpc_u, d_mpc_iter, nx, nu, N, (long)batch, mpc_steps, step);
-        else
-            plant_step_noise_kernel<<<step_groups, 256, 0, stream>>>(
-                d_x0d, d_x0, d_uout, d_iter, d_solved, d_own_plant, own_plant_per_instance() ? blk : 0L, w, w_stride, d_mpc_x, d_mpc_u, d_mpc_iter,
-                d_noise_G[NOISE_PROCESS], gw_stride, noise_seed[NOISE_PROCESS], measured && !sw.noise_split && step + 1 < mpc_steps ? d_noise_G[NOISE_MEASUREMENT] : nullptr,
-                gv_stride, noise_seed[NOISE_MEASUREMENT], d_mpc_y, nx, nu, N, (long)batch, mpc_steps, step, noise_cursor + step);
+        StepNoise nz{};
+        if (noisy())
+            nz = {d_noise_G[NOISE_PROCESS], measured && !sw.noise_split && step + 1 < mpc_steps ? d_noise_G[NOISE_MEASUREMENT] : nullptr,
+                  gw_stride, gv_stride, noise_seed[NOISE_PROCESS], noise_seed[NOISE_MEASUREMENT], d_mpc_y, noise_cursor + step};
+        (noisy() ? plant_step_kernel<true> : plant_step_kernel<false>)<<<step_groups, 256, 0, stream>>>(
+            d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, plant_stride(), w, w_stride, d_mpc_x, d_mpc_u, d_mpc_iter, nz, nx, nu, N, (long)batch,
+            mpc_steps, step);
     }
     HIP_TRY(hipGetLastError());
     if (traj_kind) ref_cursor += mpc_steps;   // (plan_rollout checked the sum)
     if (noisy()) noise_cursor += mpc_steps;   // (likewise)
     return record_done(stream);
 }
+
 
 // ---- noise: set, drop, read back (the kernels are above the chain) ----
 // G: nx x nx column-major fp64, or [batch][nx*nx]; null drops that kind.  The cursor stays where it is.
@@ -1932,7 +1818,6 @@ int Solver::set_noise(int which, const double *G, int per_instance, unsigned lon
             dev_free(d_mpc_y);
             mpc_y_cap = mpc_y_steps = 0;
         }
-        if (!own_plant()) dev_free(d_own_plant), own_plant_dirty = true;
         return 0;
     }
     const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)nx * nx;
@@ -1954,7 +1839,6 @@ void Solver::drop_noise() {
     }
     dev_free(d_mpc_y);
     mpc_y_cap = mpc_y_steps = 0;
-    if (!own_plant()) dev_free(d_own_plant), own_plant_dirty = true;
 }
 
 // the realised G xi of the steps t0 .. t0 + steps - 1, [batch][steps][nx] fp64, by noise_fill_kernel: the device function of the loop
