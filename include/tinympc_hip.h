@@ -158,6 +158,14 @@ int noise_cursor(void);
 int noise_mode(void);
 int get_noise(int which, int t0, int steps, double *buf);
 int get_mpc_measured(double *y);
+/* ... scored on the device (tinympc_set_rollout_metrics below, which describes the eleven slots): qw_data / rw_data with their
+ * lengths (checked: nx / nu; NULL with length 0: the diagonal of Q / R), the four limit arrays of nx / nu doubles or NULL.
+ * get_rollout_metrics fills [batch][11], get_rollout_summary [11][4].  Not on a set_gpus solver. */
+int set_rollout_metrics(int enable, double *qw_data, int qw_len, double *rw_data, int rw_len, double *x_lo, double *x_hi,
+                        double *u_lo, double *u_hi);
+int reset_rollout_metrics(void);
+int get_rollout_metrics(double *per_instance);
+int get_rollout_summary(double *summary);
 
 /* ------------------------------------------------------------------------- */
 /* (2) handle API                                                            */
@@ -414,6 +422,59 @@ int tinympc_get_noise(tinympc_solver *s, int which, int t0, int steps, double *b
 int tinympc_get_mpc_measured(tinympc_solver *s, double *y);
 int tinympc_host_noise(unsigned long long seed, int which, long long b, int t, int nx, const double *G, double *out);
 int tmpc_philox4x32_10(const unsigned *ctr4, const unsigned *key2, unsigned *out4);
+/* Per-instance metrics of the closed loop, folded on the device: what a Monte-Carlo sweep wants of its rollouts without the log
+ * leaving the device.  While enabled, every tinympc_mpc_rollout — whatever its route — is followed on its stream by one kernel
+ * that reads the log the rollout wrote and updates [batch][TMPC_METRIC_COUNT] fp64 accumulators, so the metrics accumulate over
+ * every step folded since the last reset: a long run is a sequence of short rollouts on a fixed-size log.
+ * THE RULE (csrc/metrics.h, the text the device kernel and tinympc_host_rollout_metrics compile), everything fp64:
+ *   for instance b and loop step s of a rollout, x_s = the logged state after the step (an fp32 widened to fp64), u_s the logged
+ *   control, it_s the logged signed iteration count (negative: the solve hit max_iter).  The target of the step is taken from the
+ *   references that step's solve used, xr_s = knot 1 of its x_ref and ur_s = knot 0 of its u_ref, fp32 device values widened:
+ *     a reference trajectory at cursor c (the one the rollout started from): xr_s = row min(c + s + 1, Lx - 1), ur_s = row
+ *       min(c + s, Lu - 1), zero without a u_traj;  a reference sequence: step s's slice;  constant references, shared or per
+ *       instance: the installed arrays;  no references: zero.
+ *   e = x_s - xr_s, v = u_s - ur_s, and the slots are
+ *     0 steps          number of steps folded
+ *     1 cost_x         sum_s sum_r qw[r] e[r]^2
+ *     2 cost_u         sum_s sum_a rw[a] v[a]^2
+ *     3 peak_err       max_s max_r |e[r]|
+ *     4 final_err      max_r |e[r]| of the last step folded
+ *     5 x_viol_max     max_s max_r max(x_s[r] - x_hi[r], x_lo[r] - x_s[r], 0)
+ *     6 x_viol_steps   number of steps with any row strictly outside [x_lo, x_hi]
+ *     7 first_viol     1 + (index, counted since the reset, of the first such step); 0 if never
+ *     8 u_sat_steps    number of steps with any u_s[a] >= u_hi[a] or <= u_lo[a]
+ *     9 iters          sum_s |it_s|
+ *    10 maxiter_steps  number of steps with it_s < 0
+ *   Counts are doubles holding integers.  Within a rollout the sums are taken in a fixed order that is not the host's step after
+ *   step; they agree with it to rounding, every other slot exactly.
+ * qw (nx) and rw (nu): non-negative weights shared by the batch; NULL: the diagonal of the solver's Q / R — refused on a
+ * per-instance-family solver, which has no one Q and R: give the weights.  x_lo, x_hi (nx), u_lo, u_hi (nu): shared limits, the
+ * metric's OWN safe set and deliberately not the solver's bounds (a soft corridor can be scored against a hard one); NULL: none,
+ * that side never counts.  Refused: a negative weight, lo > hi in any row.
+ * tinympc_set_rollout_metrics: enable = 1 installs or replaces the configuration and zeroes the accumulators; enable = 0 drops
+ * the configuration and frees the buffers (the getters and the reset are then refused).  tinympc_reset_rollout_metrics: the
+ * accumulators to zero, the configuration kept.  tinympc_rollout_metrics_mode: 0 off, 1 on.
+ * tinympc_get_rollout_metrics: the accumulators, [batch][TMPC_METRIC_COUNT].  tinympc_get_rollout_summary: over the instances,
+ * [TMPC_METRIC_COUNT][4] = per slot the sum, the minimum, the maximum and the number of instances whose value is > 0, folded on
+ * the device in a fixed order without atomics — the same bits from run to run.  Both wait for the last launch; before any
+ * rollout they return zeros.
+ * The fold is inside what tinympc_mpc_rollout(…, stream) orders and the getters wait for.  A solver without metrics launches
+ * exactly what it launched before.  tinympc_set_precision keeps configuration and accumulators, re-batching (set_batch_size)
+ * drops both as it drops every per-instance state.  A sharded solver has no mpc_rollout and takes none of it.
+ * tinympc_host_rollout_metrics: the same rule on the host, no device needed — one instance's log of `steps` steps (x_log
+ * [steps][nx], u_log [steps][nu], iter_log [steps]; xr [steps][nx] / ur [steps][nu] the targets step by step, NULL: zero) folded
+ * step after step into acc11, which is read and written: zeros to start, or what an earlier call left, to continue.  qw and rw
+ * are required here; the limits may be NULL. */
+#define TMPC_METRIC_COUNT 11
+int tinympc_set_rollout_metrics(tinympc_solver *s, int enable, const double *qw, const double *rw, const double *x_lo,
+                                const double *x_hi, const double *u_lo, const double *u_hi);
+int tinympc_reset_rollout_metrics(tinympc_solver *s);
+int tinympc_rollout_metrics_mode(tinympc_solver *s);
+int tinympc_get_rollout_metrics(tinympc_solver *s, double *per_instance /* [batch][11] */);
+int tinympc_get_rollout_summary(tinympc_solver *s, double *summary /* [11][4] */);
+int tinympc_host_rollout_metrics(int nx, int nu, int steps, const float *x_log, const float *u_log, const int *iter_log,
+                                 const float *xr, const float *ur, const double *qw, const double *rw, const double *x_lo,
+                                 const double *x_hi, const double *u_lo, const double *u_hi, double *acc11);
 /* Tolerance-terminated solves of big batches: with chunk_iters > 0 (rounded up to a multiple of check_termination)
  * a solve runs in chunks of that many iterations and, between chunks, gathers the instances still iterating into
  * a dense list, so that wavefronts do not idle behind their slowest instance.  Iterates, iteration counts and

@@ -114,6 +114,13 @@ from .tinympc import (  # noqa: E402,F401
     noise_mode,
     get_noise,
     host_noise,
+    set_rollout_metrics,
+    reset_rollout_metrics,
+    get_rollout_metrics,
+    get_rollout_summary,
+    host_rollout_metrics,
+    summary_dict,
+    METRIC_NAMES,
     mpc_rollout,
     set_batch_size,
     set_bound_constraints,

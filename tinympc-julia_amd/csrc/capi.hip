@@ -12,6 +12,7 @@
 #include "../../include/tinympc_hip.h"
 #include "solver.h"
 #include "noise.h"
+#include "metrics.h"
 
 using tmpc::set_error;
 
@@ -441,6 +442,58 @@ int tinympc_host_noise(unsigned long long seed, int which, long long b, int t, i
 int tmpc_philox4x32_10(const unsigned *ctr4, const unsigned *key2, unsigned *out4) {
     if (!ctr4 || !key2 || !out4) return -1;
     tmpc::philox4x32_10(ctr4, key2, out4);
+    return 0;
+}
+// ---- per-instance closed-loop metrics folded on the device (the rule: csrc/metrics.h; the kernels: metrics.hip) ----
+int tinympc_set_rollout_metrics(tinympc_solver *s, int enable, const double *qw, const double *rw, const double *x_lo, const double *x_hi,
+                                const double *u_lo, const double *u_hi) {
+    if (!s) return -1;
+    if (enable != 0 && enable != 1) {
+        set_error("set_rollout_metrics: enable is 1 (install the configuration, zero the accumulators) or 0 (drop both)");
+        return -1;
+    }
+    return guarded("set_rollout_metrics", [&] { return s->s.set_rollout_metrics(enable, qw, rw, x_lo, x_hi, u_lo, u_hi); });
+}
+int tinympc_reset_rollout_metrics(tinympc_solver *s) {
+    if (!s) return -1;
+    return guarded("reset_rollout_metrics", [&] { return s->s.reset_rollout_metrics(); });
+}
+int tinympc_rollout_metrics_mode(tinympc_solver *s) { return s ? (s->s.metrics_on ? 1 : 0) : -1; }
+int tinympc_get_rollout_metrics(tinympc_solver *s, double *per_instance) {
+    if (!s) return -1;
+    return guarded("get_rollout_metrics", [&] { return s->s.get_rollout_metrics(per_instance); });
+}
+int tinympc_get_rollout_summary(tinympc_solver *s, double *summary) {
+    if (!s) return -1;
+    return guarded("get_rollout_summary", [&] { return s->s.get_rollout_summary(summary); });
+}
+// the rule on the host: csrc/metrics.h, the text the device kernel compiles, step after step; touches no device
+int tinympc_host_rollout_metrics(int nx, int nu, int steps, const float *x_log, const float *u_log, const int *iter_log, const float *xr,
+                                 const float *ur, const double *qw, const double *rw, const double *x_lo, const double *x_hi, const double *u_lo,
+                                 const double *u_hi, double *acc11) {
+    if (nx < 1 || nu < 1 || steps < 0 || !x_log || !u_log || !iter_log || !qw || !rw || !acc11) {
+        set_error("host_rollout_metrics: expected nx >= 1, nu >= 1, steps >= 0, the three logs, the weights qw (nx) and rw (nu), and 11 doubles of accumulators");
+        return -1;
+    }
+    for (int r = 0; r < nx; ++r)
+        if (qw[r] < 0.0 || (x_lo && x_hi && x_lo[r] > x_hi[r])) {
+            set_error("host_rollout_metrics: a negative weight, or x_lo > x_hi, in row " + std::to_string(r));
+            return -1;
+        }
+    for (int a = 0; a < nu; ++a)
+        if (rw[a] < 0.0 || (u_lo && u_hi && u_lo[a] > u_hi[a])) {
+            set_error("host_rollout_metrics: a negative weight, or u_lo > u_hi, in row " + std::to_string(a));
+            return -1;
+        }
+    const tmpc::MetricConfig cfg{qw, rw, x_lo, x_hi, u_lo, u_hi};
+    for (int s = 0; s < steps; ++s) {
+        const tmpc::MetricStep m = tmpc::metric_step(nx, nu, x_log + (size_t)s * nx, u_log + (size_t)s * nu, xr ? xr + (size_t)s * nx : nullptr,
+                                                     ur ? ur + (size_t)s * nu : nullptr, cfg);
+        double one[tmpc::METRIC_COUNT];
+        tmpc::metric_step_slots(m, iter_log[s], one);
+        const double had = acc11[tmpc::METRIC_STEPS];
+        for (int k = 0; k < tmpc::METRIC_COUNT; ++k) acc11[k] = tmpc::metric_combine(k, acc11[k], one[k], had, 1.0);
+    }
     return 0;
 }
 int tinympc_get_mpc_log(tinympc_solver *s, double *x, double *u, int *iter) {
@@ -1099,6 +1152,20 @@ int noise_cursor(void) { return need_unsharded("noise_cursor") ? -1 : tinympc_no
 int noise_mode(void) { return need_unsharded("noise_mode") ? -1 : tinympc_noise_mode(g_solver.get()); }
 int get_noise(int which, int t0, int steps, double *buf) { return need_unsharded("get_noise") ? -1 : tinympc_get_noise(g_solver.get(), which, t0, steps, buf); }
 int get_mpc_measured(double *y) { return need_unsharded("get_mpc_measured") ? -1 : tinympc_get_mpc_measured(g_solver.get(), y); }
+// ... and scored on the device (tinympc_set_rollout_metrics): the weights ride with their lengths, which are checked here
+int set_rollout_metrics(int enable, double *qw_data, int qw_len, double *rw_data, int rw_len, double *x_lo, double *x_hi, double *u_lo, double *u_hi) {
+    if (need_unsharded("set_rollout_metrics")) return -1;
+    const tmpc::Solver &v = g_solver->s;
+    if (enable && ((qw_data && qw_len != v.nx) || (rw_data && rw_len != v.nu))) {
+        set_error("set_rollout_metrics: expected qw of nx and rw of nu weights (or none: the diagonal of Q / R); here nx = " + std::to_string(v.nx) +
+                  ", nu = " + std::to_string(v.nu));
+        return -1;
+    }
+    return tinympc_set_rollout_metrics(g_solver.get(), enable, qw_data, rw_data, x_lo, x_hi, u_lo, u_hi);
+}
+int reset_rollout_metrics(void) { return need_unsharded("reset_rollout_metrics") ? -1 : tinympc_reset_rollout_metrics(g_solver.get()); }
+int get_rollout_metrics(double *per_instance) { return need_unsharded("get_rollout_metrics") ? -1 : tinympc_get_rollout_metrics(g_solver.get(), per_instance); }
+int get_rollout_summary(double *summary) { return need_unsharded("get_rollout_summary") ? -1 : tinympc_get_rollout_summary(g_solver.get(), summary); }
 // ... and along a reference trajectory (tinympc_set_ref_trajectory): x nx x Lx and u nu x Lu column-major (shared), or
 // nx x (Lx batch) and nu x (Lu batch), instance after instance — the batch rides on the column count; shapes checked here
 int set_ref_trajectory(double *x_data, int x_rows, int x_cols, double *u_data, int u_rows, int u_cols, int per_instance, int verbose) {

@@ -500,6 +500,22 @@ struct Solver {
     int set_ref_trajectory(const double *x_traj, int Lx, const double *u_traj, int Lu, int per_instance);
     int drop_ref_trajectory(bool install_window);   // install_window: the window at the cursor becomes the ordinary references
     int ensure_ref_window(hipStream_t stream, int cursor);
+    // Per-instance closed-loop metrics folded on the device (tinympc_set_rollout_metrics; the rule: metrics.h; the kernels:
+    // metrics.hip).  While enabled every mpc_rollout enqueues rollout_metrics_kernel on its stream behind its route, whatever the
+    // route: it reads the log the route wrote and the references its solves used, and updates d_metrics [batch][11] fp64, which
+    // therefore accumulates across rollouts until reset_rollout_metrics.  d_metric_cfg: the weights and limits ([qw | rw | x_lo |
+    // x_hi | u_lo | u_hi], metric_limits bit 0..3: that limit array was given); d_metric_part: the summary's partials and result.
+    // A solver without them launches what it launched before.  set_precision keeps them, a re-batch drops them (free_batch).
+    bool metrics_on = false;
+    int metric_limits = 0;
+    double *d_metrics = nullptr, *d_metric_cfg = nullptr, *d_metric_part = nullptr;
+    int set_rollout_metrics(int enable, const double *qw, const double *rw, const double *x_lo, const double *x_hi, const double *u_lo,
+                            const double *u_hi);
+    int reset_rollout_metrics();
+    void drop_rollout_metrics();
+    int fold_rollout_metrics(hipStream_t stream, int mpc_steps, int cursor0);
+    int get_rollout_metrics(double *per_instance);
+    int get_rollout_summary(double *summary);
     int chunk_iters = 0;  // 0: off
     int *d_idx[2] = {nullptr, nullptr};
     int *d_count = nullptr;

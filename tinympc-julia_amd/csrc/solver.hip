@@ -248,6 +248,7 @@ void Solver::free_batch() {
     dev_free(d_uref_seq);
     ref_seq_steps = 0;
     mpc_cap = 0;
+    drop_rollout_metrics();   // (per-instance accumulators, and their configuration with them)
     xref_cap = uref_cap = scratch_cap = 0;
 }
 
@@ -1264,6 +1265,7 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     }
     const RolloutPlan rp = plan_rollout(mpc_steps);
     if (rp.route == Rollout::Refused || ensure_mpc_log(mpc_steps)) return -1;
+    const int cursor0 = ref_cursor;   // (the chain leaves the cursor mpc_steps further on)
     int rc = -1;
     switch (rp.route) {
     case Rollout::Fused: rc = launch_pass(stream, whole_batch(false, true, mpc_steps)); break;
@@ -1271,6 +1273,8 @@ int Solver::solve_async(hipStream_t stream, int mpc_steps) {
     default: rc = rollout_loop(stream, mpc_steps, rp.route); break;
     }
     if (rc) return rc;
+    // the metrics' fold, behind the route on its stream and inside what the done event covers (set_rollout_metrics)
+    if (metrics_on && fold_rollout_metrics(stream, mpc_steps, cursor0)) return -1;
     mpc_steps_last = mpc_steps;
     last_rollout_launches = rp.route == Rollout::Chain ? mpc_steps : 1;
     return 0;

@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_instance_bounds,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -365,6 +365,49 @@ function host_noise(seed::Integer, which::Integer, b::Integer, t::Integer, nx::I
                UInt64(seed), which, b, t, nx, G === nothing ? C_NULL : G, out)
     rc != 0 && error("host_noise failed ($(_last_error()))")
     return out
+end
+
+# Per-instance metrics of the closed loop, folded on the device: while enabled every mpc_rollout is followed on its stream by one
+# kernel that reads the log it wrote and updates 11 fp64 slots per instance (METRIC_NAMES; include/tinympc_hip.h states the rule):
+# they accumulate over rollouts until reset_rollout_metrics, so a long run is a sequence of short rollouts on a fixed-size log and
+# only the statistics leave the device.  qw (nx), rw (nu): non-negative weights, nothing = the diagonal of Q / R; x_lo, x_hi (nx),
+# u_lo, u_hi (nu): the metric's own safe set, nothing = that side never counts.  enable = false drops configuration and
+# accumulators.  get_rollout_metrics: (11, batch); get_rollout_summary: (4, 11) — per slot the sum, minimum, maximum and number of
+# instances > 0 (the C arrays [batch][11] and [11][4] seen column-major).  Not on a sharded solver (set_gpus > 1).
+# (Written against the C-ABI like the rest of this file, not executed here.)
+const METRIC_NAMES = (:steps, :cost_x, :cost_u, :peak_err, :final_err, :x_viol_max, :x_viol_steps, :first_viol, :u_sat_steps, :iters, :maxiter_steps)
+_vec_or_null(v::Union{Vector{Float64},Nothing}) = v === nothing ? C_NULL : v
+
+function set_rollout_metrics(solver::TinyMPCSolver, enable::Bool=true; qw::Union{Vector{Float64},Nothing}=nothing, rw::Union{Vector{Float64},Nothing}=nothing,
+                             x_lo::Union{Vector{Float64},Nothing}=nothing, x_hi::Union{Vector{Float64},Nothing}=nothing,
+                             u_lo::Union{Vector{Float64},Nothing}=nothing, u_hi::Union{Vector{Float64},Nothing}=nothing)
+    _need(solver)
+    for (v, n, name) in ((x_lo, solver.nx, "x_lo"), (x_hi, solver.nx, "x_hi"), (u_lo, solver.nu, "u_lo"), (u_hi, solver.nu, "u_hi"))
+        v === nothing || length(v) == n || error("set_rollout_metrics: expected $n values of $name")
+    end
+    _ok(ccall((:set_rollout_metrics, _lib_path()), Int32,
+              (Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              enable ? 1 : 0, _vec_or_null(qw), qw === nothing ? 0 : length(qw), _vec_or_null(rw), rw === nothing ? 0 : length(rw),
+              _vec_or_null(x_lo), _vec_or_null(x_hi), _vec_or_null(u_lo), _vec_or_null(u_hi)), "Failed to set the rollout metrics")
+end
+
+function reset_rollout_metrics(solver::TinyMPCSolver)
+    _need(solver)
+    _ok(ccall((:reset_rollout_metrics, _lib_path()), Int32, ()), "Failed to reset the rollout metrics")
+end
+
+function get_rollout_metrics(solver::TinyMPCSolver)
+    _need(solver)
+    buf = zeros(length(METRIC_NAMES), solver.batch)
+    _ok(ccall((:get_rollout_metrics, _lib_path()), Int32, (Ptr{Float64},), buf), "Failed to get the rollout metrics")
+    return buf
+end
+
+function get_rollout_summary(solver::TinyMPCSolver)
+    _need(solver)
+    buf = zeros(4, length(METRIC_NAMES))
+    _ok(ccall((:get_rollout_summary, _lib_path()), Int32, (Ptr{Float64},), buf), "Failed to get the rollout summary")
+    return buf
 end
 
 # A reference trajectory, windowed on the device: every instance tracks a moving target of its own through mpc_rollout, and nothing

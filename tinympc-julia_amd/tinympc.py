@@ -146,6 +146,16 @@ SIGNATURES = {
     "noise_mode": (c_int, []),
     "get_noise": (c_int, [c_int, c_int, c_int, c_dp]),
     "get_mpc_measured": (c_int, [c_dp]),
+    "tinympc_set_rollout_metrics": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "tinympc_reset_rollout_metrics": (c_int, [c_vp]),
+    "tinympc_rollout_metrics_mode": (c_int, [c_vp]),
+    "tinympc_get_rollout_metrics": (c_int, [c_vp, c_dp]),
+    "tinympc_get_rollout_summary": (c_int, [c_vp, c_dp]),
+    "tinympc_host_rollout_metrics": (c_int, [c_int, c_int, c_int, c_fp, c_fp, c_ip, c_fp, c_fp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "set_rollout_metrics": (c_int, [c_int, c_dp, c_int, c_dp, c_int, c_dp, c_dp, c_dp, c_dp]),
+    "reset_rollout_metrics": (c_int, []),
+    "get_rollout_metrics": (c_int, [c_dp]),
+    "get_rollout_summary": (c_int, [c_dp]),
     "tinympc_set_profiling": (c_int, [c_vp, c_int]),
     "tinympc_set_compaction": (c_int, [c_vp, c_int]),
     "tinympc_set_adaptive_rho": (c_int, [c_vp, c_int, c_dbl, c_dbl, c_int]),
@@ -544,6 +554,96 @@ def host_noise(seed, which, b, t, nx, G=None):
     rc = load_library().tinympc_host_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(which), int(b), int(t), int(nx), None if Gf is None else _dp(Gf), _dp(out))
     if rc != 0:
         raise TinyMPCError(f"host_noise failed ({_err()})")
+    return out
+
+
+METRIC_NAMES = ("steps", "cost_x", "cost_u", "peak_err", "final_err", "x_viol_max", "x_viol_steps", "first_viol", "u_sat_steps",
+                "iters", "maxiter_steps")
+METRIC_COUNT = len(METRIC_NAMES)
+SUMMARY_NAMES = ("sum", "min", "max", "count")
+
+
+def _metric_vec(v, n, what):
+    """a weight / limit array of n doubles, or None"""
+    if v is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+    if a.size != n:
+        raise TinyMPCError(f"{what}: expected {n} values, got {a.size}")
+    return a
+
+
+def _metric_config(nx, nu, qw, rw, x_lo, x_hi, u_lo, u_hi, what):
+    vecs = [_metric_vec(v, n, f"{what}: {name}") for v, n, name in ((qw, nx, "qw"), (rw, nu, "rw"), (x_lo, nx, "x_lo"), (x_hi, nx, "x_hi"),
+                                                                   (u_lo, nu, "u_lo"), (u_hi, nu, "u_hi"))]
+    return vecs, [None if v is None else _dp(v) for v in vecs]
+
+
+def summary_dict(summary):
+    """the (11, 4) batch summary as {slot name: {"sum", "min", "max", "count"}}"""
+    s = np.asarray(summary, dtype=np.float64).reshape(METRIC_COUNT, 4)
+    return {name: dict(zip(SUMMARY_NAMES, (float(x) for x in s[k]))) for k, name in enumerate(METRIC_NAMES)}
+
+
+def set_rollout_metrics(solver, enable=True, qw=None, rw=None, x_lo=None, x_hi=None, u_lo=None, u_hi=None):
+    """per-instance metrics of the global solver's closed loops, folded on the device (see BatchSolver.set_rollout_metrics);
+    enable=False drops them.  Not on a set_gpus solver"""
+    _need_setup(solver)
+    vecs, p = _metric_config(solver.nx, solver.nu, qw, rw, x_lo, x_hi, u_lo, u_hi, "set_rollout_metrics")
+    rc = load_library().set_rollout_metrics(1 if enable else 0, p[0], 0 if vecs[0] is None else vecs[0].size, p[1],
+                                            0 if vecs[1] is None else vecs[1].size, p[2], p[3], p[4], p[5])
+    if rc != 0:
+        raise TinyMPCError(f"set_rollout_metrics failed ({_err()})")
+
+
+def reset_rollout_metrics(solver):
+    """the global solver's metric accumulators to zero, the configuration kept"""
+    _need_setup(solver)
+    if load_library().reset_rollout_metrics() != 0:
+        raise TinyMPCError(f"reset_rollout_metrics failed ({_err()})")
+
+
+def get_rollout_metrics(solver):
+    """the global solver's per-instance metrics, (B, 11) fp64, columns in METRIC_NAMES' order"""
+    _need_setup(solver)
+    buf = np.zeros((solver.batch, METRIC_COUNT))
+    if load_library().get_rollout_metrics(_dp(buf)) != 0:
+        raise TinyMPCError(f"get_rollout_metrics failed ({_err()})")
+    return buf
+
+
+def get_rollout_summary(solver, as_dict=False):
+    """the global solver's batch summary, (11, 4) fp64: per slot the sum, minimum, maximum and number of instances > 0"""
+    _need_setup(solver)
+    buf = np.zeros((METRIC_COUNT, 4))
+    if load_library().get_rollout_summary(_dp(buf)) != 0:
+        raise TinyMPCError(f"get_rollout_summary failed ({_err()})")
+    return summary_dict(buf) if as_dict else buf
+
+
+def host_rollout_metrics(x_log, u_log, iter_log, qw, rw, xr=None, ur=None, x_lo=None, x_hi=None, u_lo=None, u_hi=None, acc=None):
+    """THE METRIC RULE on the host (csrc/metrics.h, the text the device kernel compiles; no device needed): one instance's log —
+    x_log (steps, nx), u_log (steps, nu), iter_log (steps,), the targets xr (steps, nx) / ur (steps, nu) or None = zero, all taken
+    as float32 / int32 — folded step after step into the 11 slots.  acc: the slots an earlier call returned, to continue them.
+    Returns (11,) fp64."""
+    x = np.ascontiguousarray(x_log, dtype=np.float32)
+    u = np.ascontiguousarray(u_log, dtype=np.float32)
+    it = np.ascontiguousarray(iter_log, dtype=np.int32).reshape(-1)
+    steps = it.size
+    if x.ndim != 2 or u.ndim != 2 or x.shape[0] != steps or u.shape[0] != steps:
+        raise TinyMPCError(f"host_rollout_metrics: expected x_log (steps, nx), u_log (steps, nu), iter_log (steps,); got {x.shape}, {u.shape}, {it.shape}")
+    nx, nu = x.shape[1], u.shape[1]
+    xr = None if xr is None else np.ascontiguousarray(xr, dtype=np.float32)
+    ur = None if ur is None else np.ascontiguousarray(ur, dtype=np.float32)
+    if (xr is not None and xr.shape != x.shape) or (ur is not None and ur.shape != u.shape):
+        raise TinyMPCError("host_rollout_metrics: the targets have the logs' shapes")
+    vecs, p = _metric_config(nx, nu, qw, rw, x_lo, x_hi, u_lo, u_hi, "host_rollout_metrics")
+    out = np.zeros(METRIC_COUNT) if acc is None else np.array(acc, dtype=np.float64).reshape(METRIC_COUNT).copy()
+    rc = load_library().tinympc_host_rollout_metrics(nx, nu, steps, x.ctypes.data_as(c_fp), u.ctypes.data_as(c_fp), it.ctypes.data_as(c_ip),
+                                                     None if xr is None else xr.ctypes.data_as(c_fp), None if ur is None else ur.ctypes.data_as(c_fp),
+                                                     p[0], p[1], p[2], p[3], p[4], p[5], _dp(out))
+    if rc != 0:
+        raise TinyMPCError(f"host_rollout_metrics failed ({_err()})")
     return out
 
 
@@ -1235,6 +1335,43 @@ class BatchSolver:
         return buf.reshape((self.nx, int(steps), self.batch), order="F")
 
     host_noise = staticmethod(host_noise)
+
+    def set_rollout_metrics(self, enable=True, qw=None, rw=None, x_lo=None, x_hi=None, u_lo=None, u_hi=None):
+        """per-instance metrics of the closed loop, folded on the device: while enabled every mpc_rollout, whatever its route, is
+        followed on its stream by one kernel that reads the log it wrote and updates 11 fp64 slots per instance (METRIC_NAMES:
+        steps, cost_x = sum qw e^2, cost_u = sum rw v^2, peak_err, final_err, x_viol_max, x_viol_steps, first_viol, u_sat_steps,
+        iters, maxiter_steps; e = x - the step's x target, v = u - its u target, the targets knot 1 / knot 0 of the references
+        the step's solve used; host_rollout_metrics states the rule).  They accumulate over rollouts until reset_rollout_metrics,
+        so a long run is a sequence of short rollouts on a fixed-size log and only the statistics leave the device.
+        qw (nx,), rw (nu,): non-negative weights, None = the diagonal of Q / R (refused on a per-instance-family solver).
+        x_lo, x_hi (nx,), u_lo, u_hi (nu,): the metric's own safe set, not the solver's bounds; None = that side never counts.
+        enable=True installs or replaces the configuration and zeroes the accumulators; False drops both.  set_precision keeps
+        them, re-batching drops them."""
+        vecs, p = _metric_config(self.nx, self.nu, qw, rw, x_lo, x_hi, u_lo, u_hi, "set_rollout_metrics")
+        self._chk(self.lib.tinympc_set_rollout_metrics(self.h, 1 if enable else 0, *p), "set_rollout_metrics")
+
+    def reset_rollout_metrics(self):
+        """the accumulators to zero, the configuration kept"""
+        self._chk(self.lib.tinympc_reset_rollout_metrics(self.h), "reset_rollout_metrics")
+
+    def rollout_metrics_mode(self):
+        """0 off, 1 on"""
+        return int(self.lib.tinympc_rollout_metrics_mode(self.h))
+
+    def get_rollout_metrics(self):
+        """the per-instance metrics, (B, 11) fp64, columns in METRIC_NAMES' order; zeros before any rollout"""
+        buf = np.zeros((self.batch, METRIC_COUNT))
+        self._chk(self.lib.tinympc_get_rollout_metrics(self.h, _dp(buf)), "get_rollout_metrics")
+        return buf
+
+    def get_rollout_summary(self, as_dict=False):
+        """the batch summary folded on the device in a fixed order, (11, 4) fp64: per slot the sum, the minimum, the maximum and
+        the number of instances whose value is > 0; as_dict: {slot name: {"sum", "min", "max", "count"}}"""
+        buf = np.zeros((METRIC_COUNT, 4))
+        self._chk(self.lib.tinympc_get_rollout_summary(self.h, _dp(buf)), "get_rollout_summary")
+        return summary_dict(buf) if as_dict else buf
+
+    host_rollout_metrics = staticmethod(host_rollout_metrics)
 
     def set_profiling(self, on):
         self._chk(self.lib.tinympc_set_profiling(self.h, 1 if on else 0), "set_profiling")
