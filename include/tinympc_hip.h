@@ -158,6 +158,17 @@ int noise_cursor(void);
 int noise_mode(void);
 int get_noise(int which, int t0, int steps, double *buf);
 int get_mpc_measured(double *y);
+/* ... and through a state estimator stepped on the device (tinympc_set_estimator below, which describes it): C_data ny x nx and
+ * L_data nx x ny column-major, or with per_instance = 1 ny x (nx batch) and nx x (ny batch), instance after instance; ny is
+ * C_rows; the counts are checked.  Both NULL drop it.  set_estimator_state: xhat nx x 1 (shared) or nx x batch, NULL re-arms the
+ * estimate at x0.  The others are the handle calls' forms.  Not on a set_gpus solver. */
+int set_estimator(double *C_data, int C_rows, int C_cols, double *L_data, int L_rows, int L_cols, int per_instance);
+int set_estimator_state(double *xhat_data, int xhat_rows, int xhat_cols);
+int estimator_mode(void);
+int estimator_outputs(void);
+int get_estimator_state(double *xhat);
+int get_mpc_estimate(double *xhat);
+int get_mpc_outputs(double *y);
 /* ... scored on the device (tinympc_set_rollout_metrics below, which describes the eleven slots): qw_data / rw_data with their
  * lengths (checked: nx / nu; NULL with length 0: the diagonal of Q / R), the four limit arrays of nx / nu doubles or NULL.
  * get_rollout_metrics fills [batch][11], get_rollout_summary [11][4].  Not on a set_gpus solver. */
@@ -422,6 +433,49 @@ int tinympc_get_noise(tinympc_solver *s, int which, int t0, int steps, double *b
 int tinympc_get_mpc_measured(tinympc_solver *s, double *y);
 int tinympc_host_noise(unsigned long long seed, int which, long long b, int t, int nx, const double *G, double *out);
 int tmpc_philox4x32_10(const unsigned *ctr4, const unsigned *key2, unsigned *out4);
+/* Output feedback: measured outputs y = C x + v, ny <= nx of them, and a fixed-gain state estimator (Luenberger / steady-state
+ * Kalman, current-estimator form) stepped in fp64 on the device, so that a closed loop under sensor noise that does not see its
+ * whole state still never leaves the device.
+ * THE RULE (csrc/estimator.h, the text the device kernel and tinympc_host_estimator_step compile), everything fp64, C ny x nx and
+ * L nx x ny column-major; per instance b and loop step s, t = noise cursor + s:
+ *   output   y_t[i] = (sum_j C[i + j ny] x_t[j]) + v_t[i]: acc = 0, one fma per j ascending, then one add; x_t is the true plant
+ *            state, v_t[i] row i < ny of the measurement noise G_v xi_v[b][t] (tinympc_get_noise(1, ..)[.., :ny]); without
+ *            measurement noise v = 0 and there is no add;
+ *   correct  e[i] = y_t[i] - (C xhat-_t)[i] (the same fma order); xhat_t[r] = xhat-_t[r], then fma(L[r + i nx], e[i], .), i ascending;
+ *   solve    from x0 = (float)xhat_t; u_t is its first control; the plant step is unchanged (and steps the true state);
+ *   predict  xhat-_{t+1}[r] = f[r], then fma(A[r + j nx], xhat_t[j], .), j ascending, then fma(B[r + a nx], u_t[a], .): the MODEL's A,
+ *            B and set_fdyn term (a per-instance-family solver: each instance's own A_b, B_b), never an installed plant.
+ * C and L are shared (per_instance = 0) or [batch] of each (1); C = L = NULL drops the estimator.  A solver with one is an
+ * own-plant solver: tinympc_mpc_rollout is the chain of `steps` launches on whatever kernel a kept-workspace solve takes, every
+ * kernel family and precision, no environment switch.  Between rollouts the solver holds xhat- of the next step in fp64, so
+ * mpc_rollout(a) then mpc_rollout(b) is mpc_rollout(a + b) bit for bit; a rollout leaves x0 = (float)(true state).  xhat-_0 is the
+ * caller's x0 (as the device holds it, fp32) at the first rollout after the estimator is installed, replaced or re-armed
+ * (tinympc_set_estimator_state with NULL), else what tinympc_set_estimator_state installed (xhat nx, shared, or [batch][nx]).
+ * tinympc_set_x0 moves the plant, not the estimate.
+ * Logs of the last rollout: tinympc_get_mpc_estimate [batch][steps][nx], what each solve started from; tinympc_get_mpc_outputs
+ * [batch][steps][ny], (float)y_t; tinympc_get_mpc_measured is refused while an estimator is installed.  tinympc_get_mpc_log and the
+ * rollout metrics keep the true state.  tinympc_get_estimator_state: the current xhat- [batch][nx] fp64.
+ * tinympc_estimator_mode: 0 none / 1 shared / 2 per instance; tinympc_estimator_outputs: ny (0: none).
+ * tinympc_set_precision keeps the estimator, re-batching drops it.  A solver without one launches exactly what it launched before.
+ * Refused here: ny < 1, ny > nx, only one of C and L, per_instance other than 0 / 1; by tinympc_mpc_rollout: adaptive rho, no
+ * persistent workspace.  TINYMPC_HIP_ESTIMATOR_SPLIT=1 launches predict and correct separately (same bits; a timing aid).
+ * tinympc_host_estimator_step: one predict and / or correct of the rule for one instance on the host, no device needed: xhat nx in
+ * and out; the predict reads A, B, f (NULL: zero) and u (nu); the correct reads C, L, the true state x, v (ny, NULL: none) and
+ * writes y (ny).  Both: predict first, as the fused kernel.
+ * tinympc_host_kalman_gain: the steady-state gain, host only: the filter Riccati recursion
+ * P <- A (P - P C' (C P C' + V)^-1 C P) A' + W from P = W until the update is <= 1e-13 |P|_inf (the ny x ny solve by Cholesky), then
+ * L = P C' (C P C' + V)^-1 (nx x ny) and, where P is not NULL, the prediction covariance.  -1 with a message after 100 000
+ * iterations, on a non-positive pivot or a covariance beyond 1e300 (an undetectable pair).  The setter always takes L. */
+int tinympc_set_estimator(tinympc_solver *s, const double *C, int ny, const double *L, int per_instance);
+int tinympc_set_estimator_state(tinympc_solver *s, const double *xhat, int per_instance);
+int tinympc_estimator_mode(tinympc_solver *s);
+int tinympc_estimator_outputs(tinympc_solver *s);
+int tinympc_get_estimator_state(tinympc_solver *s, double *xhat);
+int tinympc_get_mpc_estimate(tinympc_solver *s, double *xhat);
+int tinympc_get_mpc_outputs(tinympc_solver *s, double *y);
+int tinympc_host_estimator_step(int nx, int nu, int ny, int predict, int correct, const double *A, const double *B, const double *f,
+                                const double *C, const double *L, const double *u, const double *x, const double *v, double *xhat, double *y);
+int tinympc_host_kalman_gain(const double *A, const double *C, const double *W, const double *V, int nx, int ny, double *L, double *P);
 /* Per-instance metrics of the closed loop, folded on the device: what a Monte-Carlo sweep wants of its rollouts without the log
  * leaving the device.  While enabled, every tinympc_mpc_rollout — whatever its route — is followed on its stream by one kernel
  * that reads the log the rollout wrote and updates [batch][TMPC_METRIC_COUNT] fp64 accumulators, so the metrics accumulate over

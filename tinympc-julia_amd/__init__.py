@@ -114,6 +114,13 @@ from .tinympc import (  # noqa: E402,F401
     noise_mode,
     get_noise,
     host_noise,
+    set_estimator,
+    set_estimator_state,
+    estimator_mode,
+    get_estimator_state,
+    host_estimator_step,
+    host_kalman_gain,
+    kalman_gain,
     set_rollout_metrics,
     reset_rollout_metrics,
     get_rollout_metrics,

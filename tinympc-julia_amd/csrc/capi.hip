@@ -13,6 +13,7 @@
 #include "solver.h"
 #include "noise.h"
 #include "metrics.h"
+#include "estimator.h"
 
 using tmpc::set_error;
 
@@ -442,6 +443,81 @@ int tinympc_host_noise(unsigned long long seed, int which, long long b, int t, i
 int tmpc_philox4x32_10(const unsigned *ctr4, const unsigned *key2, unsigned *out4) {
     if (!ctr4 || !key2 || !out4) return -1;
     tmpc::philox4x32_10(ctr4, key2, out4);
+    return 0;
+}
+// ---- output feedback through a state estimator stepped on the device (the rule: csrc/estimator.h; the kernel: estimator.hip) ----
+int tinympc_set_estimator(tinympc_solver *s, const double *C, int ny, const double *L, int per_instance) {
+    if (!s) return -1;
+    if ((C == nullptr) != (L == nullptr)) {
+        set_error("set_estimator: expected both C (ny x nx) and L (nx x ny), or neither to drop the estimator");
+        return -1;
+    }
+    if (C && (ny < 1 || ny > s->s.nx)) {
+        set_error("set_estimator: ny = " + std::to_string(ny) + " outputs; expected 1 <= ny <= nx = " + std::to_string(s->s.nx));
+        return -1;
+    }
+    if (C && per_instance != 0 && per_instance != 1) {
+        set_error("set_estimator: per_instance is 0 (C ny x nx and L nx x ny column-major, shared) or 1 ([batch] of each)");
+        return -1;
+    }
+    return guarded("set_estimator", [&] { return s->s.set_estimator(C, ny, L, per_instance); });
+}
+int tinympc_set_estimator_state(tinympc_solver *s, const double *xhat, int per_instance) {
+    if (!s) return -1;
+    if (xhat && per_instance != 0 && per_instance != 1) {
+        set_error("set_estimator_state: per_instance is 0 (xhat nx, shared) or 1 (xhat [batch][nx])");
+        return -1;
+    }
+    return guarded("set_estimator_state", [&] { return s->s.set_estimator_state(xhat, per_instance); });
+}
+int tinympc_estimator_mode(tinympc_solver *s) { return s ? s->s.est_kind : -1; }
+int tinympc_estimator_outputs(tinympc_solver *s) { return s ? s->s.est_ny : -1; }
+int tinympc_get_estimator_state(tinympc_solver *s, double *xhat) {
+    if (!s) return -1;
+    return guarded("get_estimator_state", [&] { return s->s.get_estimator_state(xhat); });
+}
+int tinympc_get_mpc_estimate(tinympc_solver *s, double *xhat) {
+    if (!s) return -1;
+    return guarded("get_mpc_estimate", [&] { return s->s.get_mpc_estimate(xhat); });
+}
+int tinympc_get_mpc_outputs(tinympc_solver *s, double *y) {
+    if (!s) return -1;
+    return guarded("get_mpc_outputs", [&] { return s->s.get_mpc_outputs(y); });
+}
+// the rule on the host: csrc/estimator.h, the text the device kernel compiles, one instance and one step; touches no device
+int tinympc_host_estimator_step(int nx, int nu, int ny, int predict, int correct, const double *A, const double *B, const double *f, const double *C,
+                                const double *L, const double *u, const double *x, const double *v, double *xhat, double *y) {
+    if (nx < 1 || nu < 1 || ny < 1 || ny > nx || (!predict && !correct) || !xhat) {
+        set_error("host_estimator_step: expected nx >= 1, nu >= 1, 1 <= ny <= nx, predict and / or correct, and xhat (nx doubles, in and out)");
+        return -1;
+    }
+    if (predict && (!A || !B || !u)) {
+        set_error("host_estimator_step: the predict needs the model A (nx x nx), B (nx x nu) (f nx or null: zero) and the control u (nu)");
+        return -1;
+    }
+    if (correct && (!C || !L || !x || !y)) {
+        set_error("host_estimator_step: the correct needs C (ny x nx), L (nx x ny), the true state x (nx) and y (ny doubles of output); v (ny) or null: no noise");
+        return -1;
+    }
+    std::vector<double> model;
+    if (predict) {
+        model.assign(A, A + (size_t)nx * nx);
+        model.insert(model.end(), B, B + (size_t)nx * nu);
+        for (int r = 0; r < nx; ++r) model.push_back(f ? f[r] : 0.0);
+    }
+    tmpc::estimator_step_host(nx, nu, ny, predict != 0, correct != 0, model.data(), C, L, u, x, v, xhat, y);
+    return 0;
+}
+int tinympc_host_kalman_gain(const double *A, const double *C, const double *W, const double *V, int nx, int ny, double *L, double *P) {
+    if (!A || !C || !W || !V || !L || nx < 1 || ny < 1 || ny > nx) {
+        set_error("host_kalman_gain: expected A (nx x nx), C (ny x nx), W (nx x nx), V (ny x ny), 1 <= ny <= nx, and L (nx x ny doubles of output; P nx x nx or null)");
+        return -1;
+    }
+    std::string why;
+    if (!tmpc::kalman_gain_host(A, C, W, V, nx, ny, L, P, why)) {
+        set_error("host_kalman_gain: " + why);
+        return -1;
+    }
     return 0;
 }
 // ---- per-instance closed-loop metrics folded on the device (the rule: csrc/metrics.h; the kernels: metrics.hip) ----
@@ -1152,6 +1228,35 @@ int noise_cursor(void) { return need_unsharded("noise_cursor") ? -1 : tinympc_no
 int noise_mode(void) { return need_unsharded("noise_mode") ? -1 : tinympc_noise_mode(g_solver.get()); }
 int get_noise(int which, int t0, int steps, double *buf) { return need_unsharded("get_noise") ? -1 : tinympc_get_noise(g_solver.get(), which, t0, steps, buf); }
 int get_mpc_measured(double *y) { return need_unsharded("get_mpc_measured") ? -1 : tinympc_get_mpc_measured(g_solver.get(), y); }
+// ... and through a state estimator (tinympc_set_estimator): C ny x nx and L nx x ny column-major (shared), or ny x (nx batch) and
+// nx x (ny batch), instance after instance; ny is C's row count; shapes checked here
+int set_estimator(double *C_data, int C_rows, int C_cols, double *L_data, int L_rows, int L_cols, int per_instance) {
+    if (need_unsharded("set_estimator")) return -1;
+    const tmpc::Solver &v = g_solver->s;
+    if (!C_data && !L_data) return tinympc_set_estimator(g_solver.get(), nullptr, 0, nullptr, 0);
+    const long n = per_instance ? v.batch : 1;
+    if (C_data && L_data && ((per_instance != 0 && per_instance != 1) || (long)C_cols != (long)v.nx * n || L_rows != v.nx || (long)L_cols != (long)C_rows * n)) {
+        set_error("set_estimator: expected C ny x nx and L nx x ny (per_instance 0), or ny x (nx batch) and nx x (ny batch) (per_instance 1); here nx = " +
+                  std::to_string(v.nx) + ", batch = " + std::to_string(v.batch));
+        return -1;
+    }
+    return tinympc_set_estimator(g_solver.get(), C_data, C_rows, L_data, per_instance);
+}
+int set_estimator_state(double *xhat_data, int xhat_rows, int xhat_cols) {
+    if (need_unsharded("set_estimator_state")) return -1;
+    const tmpc::Solver &v = g_solver->s;
+    if (!xhat_data) return tinympc_set_estimator_state(g_solver.get(), nullptr, 0);
+    if (xhat_rows != v.nx || (xhat_cols != 1 && xhat_cols != v.batch)) {
+        set_error("set_estimator_state: expected xhat nx x 1 (shared) or nx x batch; here nx = " + std::to_string(v.nx) + ", batch = " + std::to_string(v.batch));
+        return -1;
+    }
+    return tinympc_set_estimator_state(g_solver.get(), xhat_data, xhat_cols == v.batch && v.batch > 1 ? 1 : 0);
+}
+int estimator_mode(void) { return need_unsharded("estimator_mode") ? -1 : tinympc_estimator_mode(g_solver.get()); }
+int estimator_outputs(void) { return need_unsharded("estimator_outputs") ? -1 : tinympc_estimator_outputs(g_solver.get()); }
+int get_estimator_state(double *xhat) { return need_unsharded("get_estimator_state") ? -1 : tinympc_get_estimator_state(g_solver.get(), xhat); }
+int get_mpc_estimate(double *xhat) { return need_unsharded("get_mpc_estimate") ? -1 : tinympc_get_mpc_estimate(g_solver.get(), xhat); }
+int get_mpc_outputs(double *y) { return need_unsharded("get_mpc_outputs") ? -1 : tinympc_get_mpc_outputs(g_solver.get(), y); }
 // ... and scored on the device (tinympc_set_rollout_metrics): the weights ride with their lengths, which are checked here
 int set_rollout_metrics(int enable, double *qw_data, int qw_len, double *rw_data, int rw_len, double *x_lo, double *x_hi, double *u_lo, double *u_hi) {
     if (need_unsharded("set_rollout_metrics")) return -1;

@@ -195,7 +195,8 @@ struct Switches {
          stream_mpc = false,                                // TINYMPC_HIP_STREAM_MPC: mpc_rollout on the stream and generic kernels (every precision), as the chain of launches
          stream_loop = false,                               // TINYMPC_HIP_STREAM_LOOP: with stream_mpc, one launch of the stream kernel's in-kernel loop where it is built
          event_markers = false,                             // TINYMPC_HIP_EVENT_MARKERS: profiled lean launches between separate event records
-         noise_split = false;                               // TINYMPC_HIP_NOISE_SPLIT: measurement noise by a kernel of its own ahead of every launch (timing aid)
+         noise_split = false,                               // TINYMPC_HIP_NOISE_SPLIT: measurement noise by a kernel of its own ahead of every launch (timing aid)
+         estimator_split = false;                           // TINYMPC_HIP_ESTIMATOR_SPLIT: the estimator's predict and correct as two launches a step (the A/B arm of the fused form)
     int mfmac_debug = 0;    // timing probe builds only
     int fold_slots = -1;    // TINYMPC_HIP_FOLD_SLOTS = n: the status fold's records for the first n workgroups only (at most
                             // GSLOT_DEFAULT_CAP; 0: none, the accumulator path for all — the A/B switch); unset: all of them
@@ -458,7 +459,7 @@ struct Solver {
     int plant_kind = 0, dist_kind = 0, dist_steps = 0;
     std::vector<double> own_A, own_B, own_f, dist_w;
     double *d_dist = nullptr;
-    bool own_plant() const { return plant_kind != 0 || dist_kind != 0 || noisy(); }
+    bool own_plant() const { return plant_kind != 0 || dist_kind != 0 || noisy() || estimating(); }
     bool own_plant_per_instance() const { return plant_kind == 2 || (plant_kind == 0 && hetero); }
     long plant_stride() const { return own_plant_per_instance() ? (long)nx * nx + (long)nx * nu + nx : 0L; }
     int plant_mode() const { return plant_kind | (dist_kind == 1 ? 4 : (dist_kind == 2 ? 8 : 0)); }
@@ -485,6 +486,32 @@ struct Solver {
     void drop_noise();   // both kinds (a re-batch)
     int get_noise(int which, int t0, int steps, double *buf);
     int get_mpc_measured(double *y);
+    // Output feedback through a fixed-gain state estimator stepped on the device (tinympc_set_estimator; the rule: estimator.h; the
+    // kernels and this block's functions: estimator.hip).  est_kind 0: none, 1: shared C (ny x nx) and L (nx x ny), 2: [batch] of
+    // each, column-major fp64, kept as given on the host and the device.  Such a solver is an own-plant solver (the from_x0 chain):
+    // the solve of step t starts from (float)(xhat_t), xhat_t = xhat-_t + L (y_t - C xhat-_t), y_t = C x_t + v_t (v_t: the first ny
+    // rows of the measurement noise, where installed), and behind the plant step xhat-_{t+1} = f + A xhat_t + B u_t with the MODEL
+    // (d_model: the model's image where a plant is installed, built by ensure_plant; else d_plant is the model).  d_xhat [batch][nx]
+    // fp64: xhat- of the next step between rollouts (xhat_t between a step's correct and its predict); xhat_live false: the next
+    // rollout takes xhat-_0 = (double)x0.  Logs: d_mpc_y takes (float)xhat_t, d_mpc_yout [batch][steps][ny] (float)y_t.
+    int est_kind = 0, est_ny = 0;
+    std::vector<double> est_C, est_L;
+    double *d_est_C = nullptr, *d_est_L = nullptr, *d_xhat = nullptr, *d_model = nullptr;
+    bool xhat_live = false;
+    float *d_mpc_yout = nullptr;
+    int mpc_yout_cap = 0, mpc_yout_steps = 0;   // steps x ny floats allocated per instance / ny; steps of the loop that wrote it
+    bool estimating() const { return est_kind != 0; }
+    long model_stride() const { return hetero ? (long)nx * nx + (long)nx * nu + nx : 0L; }
+    int set_estimator(const double *C, int ny, const double *L, int per_instance);
+    void drop_estimator();   // (a re-batch)
+    int set_estimator_state(const double *xhat, int per_instance);
+    int get_estimator_state(double *xhat);
+    int get_mpc_estimate(double *xhat);
+    int get_mpc_outputs(double *y);
+    int ensure_estimator_logs(int mpc_steps);
+    // one launch of estimator_step_kernel<predict, correct> on the chain's stream; step: the loop step whose solve the correct part
+    // feeds (its log row, its draw t = noise_cursor + step)
+    int estimator_step(hipStream_t stream, bool predict, bool correct, int mpc_steps, int step);
     // A reference trajectory (tinympc_set_ref_trajectory): x_traj Lx rows of nx and optionally u_traj Lu rows of nu, shared or
     // [batch][L][n] per instance, rounded to fp32 once when set; the references of a solve are its window at the cursor,
     // x_ref[k] = x_traj[min(c + k, Lx - 1)], u_ref[k] = u_traj[min(c + k, Lu - 1)] (no u_traj: zero).  traj_kind 0: none, 1: shared,

@@ -148,6 +148,7 @@ Solver::~Solver() {
     dev_free(d_sens);
     dev_free(d_lean);
     dev_free(d_plant);
+    dev_free(d_model);
     dev_free(d_dist);
     dev_free(d_xtraj);
     dev_free(d_utraj);
@@ -249,6 +250,7 @@ void Solver::free_batch() {
     ref_seq_steps = 0;
     mpc_cap = 0;
     drop_rollout_metrics();   // (per-instance accumulators, and their configuration with them)
+    drop_estimator();         // (the estimate is per instance, the matrices may be)
     xref_cap = uref_cap = scratch_cap = 0;
 }
 
@@ -373,6 +375,7 @@ Switches read_switches() {
     w.stream_loop = on("TINYMPC_HIP_STREAM_LOOP");
     w.event_markers = on("TINYMPC_HIP_EVENT_MARKERS");
     w.noise_split = on("TINYMPC_HIP_NOISE_SPLIT");
+    w.estimator_split = on("TINYMPC_HIP_ESTIMATOR_SPLIT");
     if (const char *d = std::getenv("TINYMPC_HIP_MFMAC_DEBUG")) w.mfmac_debug = std::atoi(d);
     if (const char *f = std::getenv("TINYMPC_HIP_FOLD_SLOTS")) w.fold_slots = std::max(0, std::atoi(f));
     return w;
@@ -1213,7 +1216,8 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
             return refuse("mpc_rollout: the disturbance holds " + std::to_string(dist_steps) + " steps, the loop asks for " + std::to_string(mpc_steps) +
                           " (one row per step, read from row 0)");
         if (st.adaptive_rho)
-            return refuse(noisy() ? "mpc_rollout: process / measurement noise is not available with adaptive rho"
+            return refuse(estimating() ? "mpc_rollout: a state estimator is not available with adaptive rho"
+                          : noisy() ? "mpc_rollout: process / measurement noise is not available with adaptive rho"
                                   : (own_plant() ? "mpc_rollout: a plant of its own / a disturbance is not available with adaptive rho"
                                                  : "mpc_rollout: a reference trajectory is not available with adaptive rho"));
         if (!warm_start) return refuse("mpc_rollout needs the persistent workspace (set_warm_start(1))");
@@ -1605,6 +1609,20 @@ int Solver::ensure_plant() {
     }
     if (dev_alloc(d_plant, h.size())) return -1;
     HIP_TRY(hipMemcpy(d_plant, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    // ... and, for an estimator beside an installed plant, the model's image as a second one (its predict never steps the plant)
+    if (estimating() && plant_kind) {
+        const size_t nm = hetero ? (size_t)batch : 1;
+        h.assign(nm * blk, 0.0);
+        for (size_t b = 0; b < nm; ++b) {
+            double *o = h.data() + b * blk;
+            const double *Am = hetero ? het_A.data() + b * na : A.a.data(), *Bm = hetero ? het_B.data() + b * nb : B.a.data();
+            std::copy(Am, Am + na, o);
+            std::copy(Bm, Bm + nb, o + na);
+            for (int r = 0; r < nx; ++r) o[na + nb + r] = has_fdyn ? fdyn[r] : 0.0;
+        }
+        if (dev_alloc(d_model, h.size())) return -1;
+        HIP_TRY(hipMemcpy(d_model, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     plant_dirty = false;
     return 0;
 }
@@ -1770,11 +1788,16 @@ __global__ void plant_step_kernel(double *x0d, float *x0, const float *uout, con
 // step's measurement into x0 (and the y log), so only step 0's comes from measure_kernel ahead of the first launch; the last
 // step leaves the true state's rounding in x0.  TINYMPC_HIP_NOISE_SPLIT (timing aid): measure_kernel ahead of every launch,
 // the same values.  The noise cursor is left mpc_steps further on.
+// With an estimator (set_estimator; estimator.hip) the solves start from its estimate instead: estimator_step_kernel<false, true>
+// ahead of the first launch, <true, true> behind every plant step but the last, <true, false> behind the last; no
+// measure_kernel, and the plant step draws no measurement (nz.Gv null).  TINYMPC_HIP_ESTIMATOR_SPLIT: predict and correct as
+// separate launches, the same bits.
 int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool from_x0) {
     if (ensure_plant() || plant_start(stream, from_x0)) return -1;
     const size_t EX = (size_t)ex(), EU = (size_t)eu(), per_block = 256 / nx;
     const unsigned step_groups = (unsigned)((batch + per_block - 1) / per_block);
-    const bool measured = noise_kind[NOISE_MEASUREMENT] != 0;
+    const bool est = estimating();                                 // (the estimator draws the measurement itself: estimator.hip)
+    const bool measured = noise_kind[NOISE_MEASUREMENT] != 0 && !est;
     const long gw_stride = noise_kind[NOISE_PROCESS] == 2 ? (long)nx * nx : 0L, gv_stride = noise_kind[NOISE_MEASUREMENT] == 2 ? (long)nx * nx : 0L;
     if (measured) {
         if (mpc_y_cap < mpc_steps) {
@@ -1783,11 +1806,13 @@ int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool from_x0) {
         }
         mpc_y_steps = mpc_steps;
     }
+    if (est && ensure_estimator_logs(mpc_steps)) return -1;
     Pass pass = whole_batch(false, true);
     pass.x0d = from_x0 ? nullptr : d_x0d;
     for (int step = 0; step < mpc_steps; ++step) {
         if (ref_seq_steps > 0 && step > 0) pass.xref = d_xref_seq + step * EX, pass.uref = d_uref_seq + step * EU;
         if (traj_kind && ensure_ref_window(stream, ref_cursor + step)) return -1;
+        if (est && (step == 0 || sw.estimator_split) && estimator_step(stream, false, true, mpc_steps, step)) return -1;
         if (measured && (step == 0 || sw.noise_split))
             measure_kernel<<<step_groups, 256, 0, stream>>>(d_x0, d_mpc_y, d_x0d, d_noise_G[NOISE_MEASUREMENT], gv_stride, noise_seed[NOISE_MEASUREMENT], nx,
                                                             (long)batch, mpc_steps, step, noise_cursor + step);
@@ -1801,6 +1826,9 @@ int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool from_x0) {
         (noisy() ? plant_step_kernel<true> : plant_step_kernel<false>)<<<step_groups, 256, 0, stream>>>(
             d_x0d, d_x0, d_uout, d_iter, d_solved, d_plant, plant_stride(), w, w_stride, d_mpc_x, d_mpc_u, d_mpc_iter, nz, nx, nu, N, (long)batch,
             mpc_steps, step);
+        // the estimator behind the plant step: the predict with this step's u, fused with the next step's correct (its log row,
+        // its draw) on every step but the last, which leaves x0 as the plant step wrote it
+        if (est && estimator_step(stream, true, !sw.estimator_split && step + 1 < mpc_steps, mpc_steps, step + 1)) return -1;
     }
     HIP_TRY(hipGetLastError());
     if (traj_kind) ref_cursor += mpc_steps;   // (plan_rollout checked the sum)
@@ -1872,6 +1900,11 @@ int Solver::get_noise(int which, int t0, int steps, double *buf) {
 
 // what every step's solve of the last loop started from, [batch][steps][nx] (measurement noise installed)
 int Solver::get_mpc_measured(double *y) {
+    if (estimating()) {
+        set_error("get_mpc_measured: an estimator is installed, the solves start from its estimate: get_mpc_estimate (what every solve started "
+                  "from) and get_mpc_outputs (the measured outputs y)");
+        return -1;
+    }
     if (!noise_kind[NOISE_MEASUREMENT] || mpc_steps_last <= 0 || mpc_y_steps != mpc_steps_last || !y) {
         set_error("get_mpc_measured: no mpc_rollout with measurement noise has run (set_measurement_noise, then mpc_rollout)");
         return -1;

@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -249,7 +249,14 @@ function mpc_rollout(solver::TinyMPCSolver, steps::Integer)
     x, u, it = zeros(nx, steps, B), zeros(nu, steps, B), zeros(Int32, steps, B)
     st = ccall((:mpc_rollout, _lib_path()), Int32, (Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), steps, x, u, it)
     st < 0 && error("mpc_rollout failed ($(_last_error()))")
-    if ccall((:noise_mode, _lib_path()), Int32, ()) >= 4      # measurement noise installed: what every step's solve started from
+    if ccall((:estimator_mode, _lib_path()), Int32, ()) > 0      # an estimator: what every solve started from, and the measured outputs
+        ny = ccall((:estimator_outputs, _lib_path()), Int32, ())
+        xhat, yout = zeros(nx, steps, B), zeros(ny, steps, B)
+        _ok(ccall((:get_mpc_estimate, _lib_path()), Int32, (Ptr{Float64},), xhat), "Failed to get the estimates")
+        _ok(ccall((:get_mpc_outputs, _lib_path()), Int32, (Ptr{Float64},), yout), "Failed to get the measured outputs")
+        return (status=st, x=x, u=u, iter=it, xhat=xhat, yout=yout)
+    end
+    if ccall((:noise_mode, _lib_path()), Int32, ()) >= 4     # measurement noise installed: what every step's solve started from
         y = zeros(nx, steps, B)
         _ok(ccall((:get_mpc_measured, _lib_path()), Int32, (Ptr{Float64},), y), "Failed to get the measured states")
         return (status=st, x=x, u=u, iter=it, y=y)
@@ -365,6 +372,76 @@ function host_noise(seed::Integer, which::Integer, b::Integer, t::Integer, nx::I
                UInt64(seed), which, b, t, nx, G === nothing ? C_NULL : G, out)
     rc != 0 && error("host_noise failed ($(_last_error()))")
     return out
+end
+
+# Output feedback through a fixed-gain state estimator stepped on the device: the loop measures y = C x + v (ny <= nx outputs, v the
+# first ny rows of the measurement noise where installed), corrects xhat = xhat- + L (y - C xhat-), solves from Float32(xhat) and
+# predicts xhat-+ = f + A xhat + B u with the MODEL (include/tinympc_hip.h states the rule).  C (ny, nx) and L (nx, ny) shared, or
+# (ny, nx, batch) and (nx, ny, batch); set_estimator(solver, nothing, nothing) drops it.  mpc_rollout then is the own-plant chain, returns
+# xhat (nx, steps, batch) — what every solve started from — and yout (ny, steps, batch), and no y.  Between rollouts the solver keeps
+# xhat- of the next step; set_x0 moves the plant, not the estimate.  Not with adaptive rho, not on a sharded solver.
+# (Written against the C-ABI like the rest of this file, not executed here.)
+function set_estimator(solver::TinyMPCSolver, C::Union{Array{Float64},Nothing}, L::Union{Array{Float64},Nothing})
+    _need(solver)
+    if C === nothing && L === nothing
+        return _ok(ccall((:set_estimator, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Int32), C_NULL, 0, 0, C_NULL, 0, 0, 0),
+                   "Failed to drop the estimator")
+    end
+    (C === nothing || L === nothing) && error("set_estimator: expected both C (ny, nx) and L (nx, ny), or neither to drop the estimator")
+    _ok(ccall((:set_estimator, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Int32),
+              C, size(C, 1), div(length(C), size(C, 1)), L, size(L, 1), div(length(L), size(L, 1)), ndims(C) == 3 ? 1 : 0), "Failed to set the estimator")
+end
+
+# xhat- of the next step: (nx,) shared or (nx, batch); nothing re-arms it (the next mpc_rollout takes xhat-_0 = x0)
+function set_estimator_state(solver::TinyMPCSolver, xhat::Union{Array{Float64},Nothing})
+    _need(solver)
+    xhat === nothing && return _ok(ccall((:set_estimator_state, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32), C_NULL, 0, 0), "Failed to re-arm the estimate")
+    _ok(ccall((:set_estimator_state, _lib_path()), Int32, (Ptr{Float64}, Int32, Int32), xhat, size(xhat, 1), div(length(xhat), size(xhat, 1))),
+        "Failed to set the estimate")
+end
+
+# 0: no estimator, 1: shared C and L, 2: per instance
+function estimator_mode(solver::TinyMPCSolver)
+    _need(solver)
+    m = ccall((:estimator_mode, _lib_path()), Int32, ())
+    m < 0 && error("estimator_mode failed ($(_last_error()))")
+    return Int(m)
+end
+
+# the current xhat- of the next step, (nx, batch)
+function get_estimator_state(solver::TinyMPCSolver)
+    _need(solver)
+    buf = zeros(solver.nx, solver.batch)
+    _ok(ccall((:get_estimator_state, _lib_path()), Int32, (Ptr{Float64},), buf), "Failed to get the estimate")
+    return buf
+end
+
+# the rule on the host for one instance (no device needed): predict (A, B, f or nothing, u) and / or correct (C, L, the true state x,
+# v or nothing); returns (xhat, y), y nothing without the correct
+function host_estimator_step(xhat::Vector{Float64}; A=nothing, B=nothing, f=nothing, u=nothing, C=nothing, L=nothing, x=nothing, v=nothing,
+                             predict::Bool=true, correct::Bool=true)
+    nx = length(xhat)
+    nu = B === nothing ? 1 : size(B, 2)
+    ny = C === nothing ? 1 : size(C, 1)
+    out, y = copy(xhat), zeros(ny)
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    rc = GC.@preserve A B f u C L x v out y ccall((:tinympc_host_estimator_step, _lib_path()), Int32,
+               (Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Float64}), nx, nu, ny, predict ? 1 : 0, correct ? 1 : 0, p(A), p(B), p(f), p(C), p(L), p(u), p(x), p(v), pointer(out), pointer(y))
+    rc != 0 && error("host_estimator_step failed ($(_last_error()))")
+    return out, (correct ? y : nothing)
+end
+
+# the steady-state Kalman gain L (nx, ny) of the model (A, C) under the factors of set_process_noise / set_measurement_noise:
+# W = Gw Gw', V = Gv[1:ny, :] Gv[1:ny, :]' (the filter Riccati recursion from P = W, host only)
+function kalman_gain(A::Matrix{Float64}, C::Matrix{Float64}, Gw::Matrix{Float64}, Gv::Matrix{Float64})
+    nx, ny = size(A, 1), size(C, 1)
+    W, V = Gw * Gw', Gv[1:ny, :] * Gv[1:ny, :]'
+    L, P = zeros(nx, ny), zeros(nx, nx)
+    rc = ccall((:tinympc_host_kalman_gain, _lib_path()), Int32, (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+               A, C, W, V, nx, ny, L, P)
+    rc != 0 && error("kalman_gain failed ($(_last_error()))")
+    return L
 end
 
 # Per-instance metrics of the closed loop, folded on the device: while enabled every mpc_rollout is followed on its stream by one

@@ -146,6 +146,22 @@ SIGNATURES = {
     "noise_mode": (c_int, []),
     "get_noise": (c_int, [c_int, c_int, c_int, c_dp]),
     "get_mpc_measured": (c_int, [c_dp]),
+    "tinympc_set_estimator": (c_int, [c_vp, c_dp, c_int, c_dp, c_int]),
+    "tinympc_set_estimator_state": (c_int, [c_vp, c_dp, c_int]),
+    "tinympc_estimator_mode": (c_int, [c_vp]),
+    "tinympc_estimator_outputs": (c_int, [c_vp]),
+    "tinympc_get_estimator_state": (c_int, [c_vp, c_dp]),
+    "tinympc_get_mpc_estimate": (c_int, [c_vp, c_dp]),
+    "tinympc_get_mpc_outputs": (c_int, [c_vp, c_dp]),
+    "tinympc_host_estimator_step": (c_int, [c_int, c_int, c_int, c_int, c_int] + [c_dp] * 10),
+    "tinympc_host_kalman_gain": (c_int, [c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_dp, c_dp]),
+    "set_estimator": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_int, c_int]),
+    "set_estimator_state": (c_int, [c_dp, c_int, c_int]),
+    "estimator_mode": (c_int, []),
+    "estimator_outputs": (c_int, []),
+    "get_estimator_state": (c_int, [c_dp]),
+    "get_mpc_estimate": (c_int, [c_dp]),
+    "get_mpc_outputs": (c_int, [c_dp]),
     "tinympc_set_rollout_metrics": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "tinympc_reset_rollout_metrics": (c_int, [c_vp]),
     "tinympc_rollout_metrics_mode": (c_int, [c_vp]),
@@ -557,6 +573,125 @@ def host_noise(seed, which, b, t, nx, G=None):
     return out
 
 
+def _estimator_matrices(C, L, what):
+    """(flat C, flat L, ny, nx, per_instance) of an estimator: C (ny, nx) and L (nx, ny), or (ny, nx, B) and (nx, ny, B)"""
+    C, L = np.asarray(C, dtype=np.float64), np.asarray(L, dtype=np.float64)
+    if C.ndim not in (2, 3) or L.ndim != C.ndim or L.shape[:2] != C.shape[:2][::-1] or (C.ndim == 3 and C.shape[2] != L.shape[2]):
+        raise TinyMPCError(f"{what}: expected C (ny, nx) and L (nx, ny), or (ny, nx, batch) and (nx, ny, batch); got {C.shape} and {L.shape}")
+    return _flat_f(C), _flat_f(L), C.shape[0], C.shape[1], 1 if C.ndim == 3 else 0
+
+
+def set_estimator(solver, C, L=None):
+    """a fixed-gain state estimator for the global solver's closed loops, stepped on the device (see BatchSolver.set_estimator): C
+    (ny, nx) and L (nx, ny) shared, or (ny, nx, B) and (nx, ny, B) per instance; C None drops it.  Not on a set_gpus solver"""
+    _need_setup(solver)
+    lib = load_library()
+    if C is None and L is None:
+        rc = lib.set_estimator(None, 0, 0, None, 0, 0, 0)
+    elif C is None or L is None:
+        raise TinyMPCError("set_estimator: expected both C (ny, nx) and L (nx, ny), or neither to drop the estimator")
+    else:
+        Cf, Lf, ny, nx, per = _estimator_matrices(C, L, "set_estimator")
+        rc = lib.set_estimator(_dp(Cf), ny, Cf.size // ny, _dp(Lf), nx, Lf.size // nx, per)
+    if rc != 0:
+        raise TinyMPCError(f"set_estimator failed ({_err()})")
+
+
+def set_estimator_state(solver, xhat):
+    """install the global solver's estimate xhat- of the next step: (nx,) shared or (nx, B); None re-arms it at x0"""
+    _need_setup(solver)
+    lib = load_library()
+    if xhat is None:
+        rc = lib.set_estimator_state(None, 0, 0)
+    else:
+        xh = np.asarray(xhat, dtype=np.float64)
+        xf = _flat_f(xh)
+        rc = lib.set_estimator_state(_dp(xf), xh.shape[0], xf.size // max(1, xh.shape[0]))
+    if rc != 0:
+        raise TinyMPCError(f"set_estimator_state failed ({_err()})")
+
+
+def estimator_mode(solver):
+    """0: no estimator, 1: shared C and L, 2: per instance"""
+    _need_setup(solver)
+    m = int(load_library().estimator_mode())
+    if m < 0:
+        raise TinyMPCError(f"estimator_mode failed ({_err()})")
+    return m
+
+
+def get_estimator_state(solver):
+    """the global solver's current estimate xhat- of the next step, (nx, B) fp64"""
+    _need_setup(solver)
+    buf = np.zeros(solver.nx * solver.batch)
+    if load_library().get_estimator_state(_dp(buf)) != 0:
+        raise TinyMPCError(f"get_estimator_state failed ({_err()})")
+    return buf.reshape((solver.nx, solver.batch), order="F")
+
+
+def host_estimator_step(xhat, A=None, B=None, f=None, u=None, C=None, L=None, x=None, v=None, predict=True, correct=True):
+    """THE ESTIMATOR'S RULE on the host (csrc/estimator.h, the text the device kernel compiles; no device needed), one step for one
+    instance or a batch of them: predict xhat- = f + A xhat + B u with the model (A (nx, nx), B (nx, nu), f (nx,) or None, u (nu,)) and /
+    or correct xhat = xhat- + L (y - C xhat-), y = C x + v (C (ny, nx), L (nx, ny), the true state x, v (ny,) or None); with both the
+    predict first, as the fused kernel.  xhat (nx,), or (nx, n) with u (nu, n), x (nx, n), v (ny, n) and matrices shared or with a
+    trailing axis n.  Returns (xhat, y): shaped as the input, y (ny,) / (ny, n), None without the correct."""
+    lib = load_library()
+    xh = np.array(xhat, dtype=np.float64)
+    single = xh.ndim == 1
+    xh2 = xh.reshape(xh.shape[0], -1)
+    nx, n = xh2.shape
+    if predict and (A is None or B is None or u is None):
+        raise TinyMPCError("host_estimator_step: the predict needs A, B and u")
+    if correct and (C is None or L is None or x is None):
+        raise TinyMPCError("host_estimator_step: the correct needs C, L and the true state x")
+
+    def inst(M, b, nd):
+        """instance b's slice of an array that is shared (nd axes) or carries a trailing axis, flat column-major"""
+        if M is None:
+            return None
+        M = np.asarray(M, dtype=np.float64)
+        return _flat_f(M[..., b] if M.ndim == nd + 1 else M)
+
+    nu = np.asarray(B).shape[1] if B is not None else 1
+    ny = np.asarray(C).shape[0] if C is not None else 1
+    out, ys = np.zeros((nx, n)), np.zeros((ny, n))
+    for b in range(n):
+        xb, yb = np.ascontiguousarray(xh2[:, b]), np.zeros(ny)
+        args = [inst(A, b, 2), inst(B, b, 2), inst(f, b, 1), inst(C, b, 2), inst(L, b, 2), inst(u, b, 1), inst(x, b, 1), inst(v, b, 1)]
+        rc = lib.tinympc_host_estimator_step(nx, nu, ny, int(bool(predict)), int(bool(correct)),
+                                             *[None if a is None else _dp(a) for a in args], _dp(xb), _dp(yb))
+        if rc != 0:
+            raise TinyMPCError(f"host_estimator_step failed ({_err()})")
+        out[:, b], ys[:, b] = xb, yb
+    if single:
+        return out[:, 0], (ys[:, 0] if correct else None)
+    return out, (ys if correct else None)
+
+
+def host_kalman_gain(A, C, W, V):
+    """the steady-state gain of the filter Riccati recursion P <- A (P - P C' (C P C' + V)^-1 C P) A' + W from P = W (host only,
+    csrc/estimator.h): (L (nx, ny) = P C' (C P C' + V)^-1, P (nx, nx)).  TinyMPCError: an undetectable pair, a V that is not positive
+    definite"""
+    A, C, W, V = (np.asarray(M, dtype=np.float64) for M in (A, C, W, V))
+    nx, ny = A.shape[0], C.shape[0]
+    if A.shape != (nx, nx) or C.shape != (ny, nx) or W.shape != (nx, nx) or V.shape != (ny, ny):
+        raise TinyMPCError(f"host_kalman_gain: expected A (nx, nx), C (ny, nx), W (nx, nx), V (ny, ny); got {A.shape}, {C.shape}, {W.shape}, {V.shape}")
+    L, P = np.zeros(nx * ny), np.zeros(nx * nx)
+    if load_library().tinympc_host_kalman_gain(_dp(_flat_f(A)), _dp(_flat_f(C)), _dp(_flat_f(W)), _dp(_flat_f(V)), nx, ny, _dp(L), _dp(P)) != 0:
+        raise TinyMPCError(f"host_kalman_gain failed ({_err()})")
+    return L.reshape((nx, ny), order="F"), P.reshape((nx, nx), order="F")
+
+
+def kalman_gain(A, C, Gw, Gv):
+    """the steady-state Kalman gain L (nx, ny) of the model (A, C) under the noise factors of set_process_noise / set_measurement_noise:
+    W = Gw Gw', V = Gv[:ny] Gv[:ny]' — the covariance of the first ny rows of G_v xi_v, the estimator's output noise; Gw, Gv (nx, nx) or
+    (nx,) = diag(sigma)"""
+    C = np.asarray(C, dtype=np.float64)
+    Gw, Gv = (np.diag(G) if np.ndim(G) == 1 else np.asarray(G, dtype=np.float64) for G in (Gw, Gv))
+    ny = C.shape[0]
+    return host_kalman_gain(A, C, Gw @ Gw.T, Gv[:ny] @ Gv[:ny].T)[0]
+
+
 METRIC_NAMES = ("steps", "cost_x", "cost_u", "peak_err", "final_err", "x_viol_max", "x_viol_steps", "first_viol", "u_sat_steps",
                 "iters", "maxiter_steps")
 METRIC_COUNT = len(METRIC_NAMES)
@@ -722,7 +857,13 @@ def mpc_rollout(solver, steps):
     it = it.reshape((steps, B), order="F")
     out = dict(status=st, x=x.reshape((nx, steps, B), order="F"), u=u.reshape((nu, steps, B), order="F"),
                iter=np.abs(it), solved=(it > 0).astype(np.int32))
-    if max(0, int(lib.noise_mode())) & 12:
+    if int(lib.estimator_mode()) > 0:
+        ny = int(lib.estimator_outputs())
+        xh, yo = np.zeros(nx * steps * B), np.zeros(ny * steps * B)
+        if lib.get_mpc_estimate(_dp(xh)) != 0 or lib.get_mpc_outputs(_dp(yo)) != 0:
+            raise TinyMPCError(f"get_mpc_estimate / get_mpc_outputs failed ({_err()})")
+        out["xhat"], out["yout"] = xh.reshape((nx, steps, B), order="F"), yo.reshape((ny, steps, B), order="F")
+    elif max(0, int(lib.noise_mode())) & 12:
         y = np.zeros(nx * steps * B)
         if lib.get_mpc_measured(_dp(y)) != 0:
             raise TinyMPCError(f"get_mpc_measured failed ({_err()})")
@@ -1279,11 +1420,61 @@ class BatchSolver:
         it = it.reshape((steps, B), order="F")
         out = dict(status=st, x=x.reshape((nx, steps, B), order="F"), u=u.reshape((nu, steps, B), order="F"),
                    iter=np.abs(it), solved=(it > 0).astype(np.int32))
-        if self.noise_mode() & 12:
+        if self.estimator_mode():
+            ny = int(self.lib.tinympc_estimator_outputs(self.h))
+            xh, yo = np.zeros(nx * steps * B), np.zeros(ny * steps * B)
+            self._chk(self.lib.tinympc_get_mpc_estimate(self.h, _dp(xh)), "get_mpc_estimate")
+            self._chk(self.lib.tinympc_get_mpc_outputs(self.h, _dp(yo)), "get_mpc_outputs")
+            out["xhat"], out["yout"] = xh.reshape((nx, steps, B), order="F"), yo.reshape((ny, steps, B), order="F")
+        elif self.noise_mode() & 12:
             y = np.zeros(nx * steps * B)
             self._chk(self.lib.tinympc_get_mpc_measured(self.h, _dp(y)), "get_mpc_measured")
             out["y"] = y.reshape((nx, steps, B), order="F")
         return out
+
+    def set_estimator(self, C, L=None):
+        """output feedback: the loop measures y = C x + v (ny <= nx outputs; v the first ny rows of the measurement noise, where
+        installed) and a fixed-gain estimator stepped in fp64 on the device feeds the solves — correct xhat_t = xhat-_t + L (y_t - C
+        xhat-_t), the solve of step t from float32(xhat_t), predict xhat-_{t+1} = f + A xhat_t + B u_t with the MODEL (never an
+        installed plant; a per-instance-family solver: each instance's A_b, B_b); host_estimator_step states the rule.  C (ny, nx)
+        and L (nx, ny) shared, or (ny, nx, B) and (nx, ny, B); kalman_gain gives the steady-state L.  C None drops it.  Such a
+        solver is an own-plant solver (see mpc_rollout): the chain of `steps` launches, every kernel family and precision; its
+        log has xhat (nx, steps, B), what each solve started from, and yout (ny, steps, B), and no y.  Between rollouts the solver
+        keeps xhat- of the next step (get_estimator_state): two loops in a row are one; the first loop after set_estimator takes
+        xhat-_0 = x0 unless set_estimator_state installed another; set_x0 moves the plant, not the estimate.  set_precision
+        keeps the estimator, re-batching drops it."""
+        if C is None and L is None:
+            self._chk(self.lib.tinympc_set_estimator(self.h, None, 0, None, 0), "set_estimator")
+            return
+        if C is None or L is None:
+            raise TinyMPCError("set_estimator: expected both C (ny, nx) and L (nx, ny), or neither to drop the estimator")
+        Cf, Lf, ny, nx, per = _estimator_matrices(C, L, "set_estimator")
+        if nx != self.nx or (per and np.shape(C)[2] != self.batch):
+            raise TinyMPCError(f"set_estimator: expected C (ny, {self.nx}) and L ({self.nx}, ny), or with a trailing axis of {self.batch}; got {np.shape(C)} and {np.shape(L)}")
+        self._chk(self.lib.tinympc_set_estimator(self.h, _dp(Cf), ny, _dp(Lf), per), "set_estimator")
+
+    def set_estimator_state(self, xhat):
+        """install xhat- of the next step, (nx,) shared or (nx, B) fp64; None re-arms it: the next mpc_rollout takes xhat-_0 = x0"""
+        if xhat is None:
+            self._chk(self.lib.tinympc_set_estimator_state(self.h, None, 0), "set_estimator_state")
+            return
+        xh = np.asarray(xhat, dtype=np.float64)
+        if xh.shape not in ((self.nx,), (self.nx, self.batch)):
+            raise TinyMPCError(f"set_estimator_state: expected xhat ({self.nx},) or ({self.nx}, {self.batch}); got {xh.shape}")
+        self._chk(self.lib.tinympc_set_estimator_state(self.h, _dp(_flat_f(xh)), 1 if xh.ndim == 2 else 0), "set_estimator_state")
+
+    def estimator_mode(self):
+        """0: no estimator, 1: shared C and L, 2: per instance"""
+        return int(self.lib.tinympc_estimator_mode(self.h))
+
+    def get_estimator_state(self):
+        """the current xhat- of the next step, (nx, B) fp64"""
+        buf = np.zeros(self.nx * self.batch)
+        self._chk(self.lib.tinympc_get_estimator_state(self.h, _dp(buf)), "get_estimator_state")
+        return buf.reshape((self.nx, self.batch), order="F")
+
+    host_estimator_step = staticmethod(host_estimator_step)
+    kalman_gain = staticmethod(kalman_gain)
 
     def _set_noise(self, which, G, seed):
         name = "set_process_noise" if which == NOISE_PROCESS else "set_measurement_noise"
