@@ -106,7 +106,11 @@ int print_problem_data(int verbose);
  * TinyMPC.jl:258-267); enables the non-empty halves.  set_cone_constraints: per-knot second-order cones, inputs first; cone i covers rows
  * [Ac[i], Ac[i]+qc[i]) of each knot, the LAST row is the axis: ||head|| <= c[i] * axis
  * (rocket_landing_constraints.jl:51-57,132); at most 8 cones per side; enables the non-empty halves.
- * Cone, linear-inequality and fdyn arithmetic lives only in the absent submodule — parity UNPINNED. */
+ * Cone, linear-inequality and fdyn arithmetic lives only in the absent submodule — parity UNPINNED.
+ * With batch > 1 the batch dimension may ride on the widths, as it does for set_bound_constraints: Alin_x rows_x x (nx*batch)
+ * with blin_x_len = rows_x*batch, Alin_u rows_u x (nu*batch) with blin_u_len = rows_u*batch give every instance its own rows
+ * (tinympc_set_instance_linear: [batch] blocks of rows x n, column-major, and [batch][rows]; a set_gpus solver scatters the
+ * slices to its shards).  Every non-empty side must then have the per-instance width: mixed widths are an error. */
 int set_linear_constraints(double *Alin_x_data, int Alin_x_rows, int Alin_x_cols,
                            double *blin_x_data, int blin_x_len, double *Alin_u_data,
                            int Alin_u_rows, int Alin_u_cols, double *blin_u_data, int blin_u_len,
@@ -216,7 +220,7 @@ int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const 
  * precision 1 and 2; tinympc_kernel_name reports "stream4<NX,NU;ib>", "generic<ib>" or "generic<f64;ib>".  A per-instance-family
  * solver needs the stream form.  Refused, tinympc_last_error naming the condition: adaptive rho beside per-instance bounds (in
  * either order); tinympc_mpc_rollout, unless TINYMPC_HIP_STREAM_MPC=1 gives the solver the chain of launches (there is no
- * in-kernel loop with per-instance bounds).  Per-instance cones and linear rows do not exist. */
+ * in-kernel loop with per-instance bounds).  Linear rows per instance: tinympc_set_instance_linear.  Per-instance cones do not exist. */
 int tinympc_set_instance_bounds(tinympc_solver *s, const double *x_min, const double *x_max, const double *u_min,
                                 const double *u_max, int per_knot);
 /* 0: shared bounds, 1: per instance and constant over the horizon, 2: per instance and per knot */
@@ -232,6 +236,36 @@ int tinympc_enable_cones(tinympc_solver *s, int en_state_soc, int en_input_soc);
 int tinympc_set_linear_constraints(tinympc_solver *s, const double *Alin_x, int rows_x, const double *blin_x,
                                    const double *Alin_u, int rows_u, const double *blin_u);
 int tinympc_enable_linear(tinympc_solver *s, int en_state_linear, int en_input_linear);
+/* Linear rows PER INSTANCE (no counterpart in the reference, whose solver holds one constraint set: every vehicle of a fleet
+ * its own obstacle plane, a sweep over constraint placements, corridor walls that are not axis aligned).  The rule is the
+ * shared set's, applied per instance: instance b's rows of a side are projected one after the other, in order, at every knot.
+ *   Alin_x: [batch] blocks of rows_x x nx, column-major; blin_x: [batch][rows_x]; Alin_u / blin_u alike with nu.
+ * The row counts are one pair for the whole batch, each at most 8; a side with 0 rows is empty (its pointers may be null).  An
+ * all-zero row of an instance means "this instance has no row k" (stored as a = 0, b = FLT_MAX, |a|^2 = 1: never violated) —
+ * that is how instances carry different numbers of rows.  A side that is enabled carries its slack and dual for every
+ * instance, an instance whose rows on that side are all absent included — as a shared set whose rows never act does: such
+ * an instance's iterates are those of a solver with rows that never bind, not bit for bit those of a solver without rows.
+ * Rows are constant over the horizon.  Values are rounded to fp32 as the shared set's are, so per-instance rows that all equal
+ * a shared set reproduce the shared-rows stream kernel bit for bit.  Non-empty sides are enabled on success, as
+ * tinympc_set_linear_constraints does; tinympc_enable_linear / tinympc_update_settings switch a side off and on again
+ * without a new upload.  The solver keeps host copies (a later tinympc_set_precision keeps the rows); re-batching a solver
+ * (set_batch_size, set_gpus) drops them, as it resets every per-instance input; tinympc_set_linear_constraints afterwards
+ * drops them too: back to the shared set and to the kernels that serve it.  Both sides empty: no rows at all, shared mode.
+ * Such a solver runs on the `il` forms of the run-time-shape kernels, whatever on-chip kernel its shape has: the stream
+ * kernel's for (nx, nu) in {(4,1), (6,3), (12,4)} at precision 0 — any horizon the LDS image holds, one family or one per
+ * instance, the affine term, cones, chunked solves — and the generic kernel's for every other shape and for precision 1 and
+ * 2; tinympc_kernel_name reports "stream4<NX,NU;il>", "generic<il>" or "generic<f64;il>".  The `il` forms read their box bounds
+ * per instance, so per-instance bounds (tinympc_set_instance_bounds) combine with the rows at no extra cost and under the
+ * same names; tinympc_bounds_mode keeps reporting what the caller set.  A per-instance-family solver needs the stream form.
+ * Refused, tinympc_last_error naming the condition: more than 8 rows on a side; a null side with rows > 0; adaptive rho beside
+ * per-instance rows (in either order); tinympc_mpc_rollout unless the solver has a plant of its own / a disturbance / a
+ * reference trajectory (whose loop is a chain of launches) or TINYMPC_HIP_STREAM_MPC=1 gives it that chain — there is no
+ * in-kernel loop with per-instance rows.  Follow-ups, not built: rows per knot, per-instance cones, the on-chip families, the
+ * fp64-state and adaptive stream forms, loop forms, units specialised at setup, per-instance equality helpers. */
+int tinympc_set_instance_linear(tinympc_solver *s, const double *Alin_x, int rows_x, const double *blin_x,
+                                const double *Alin_u, int rows_u, const double *blin_u);
+/* 0: no rows or rows shared by the batch, 1: per instance */
+int tinympc_lin_mode(tinympc_solver *s);
 int tinympc_get_cache_terms(tinympc_solver *s, double *Kinf, double *Pinf, double *Quu_inv,
                             double *AmBKt);
 /* Adaptive rho — admm.cpp:147-174 + rho_benchmark.cpp, per instance: every 5th ADMM iteration each instance predicts
@@ -568,7 +602,8 @@ int tinympc_set_strict_precision(tinympc_solver *s, int strict);
 int tinympc_reload_switches(tinympc_solver *s);
 int tinympc_effective_precision(tinympc_solver *s);
 /* Name of the kernel family the solver's shape / options select: "quad<nx,nu,N,gG>", "mfma<...>", "mfmat<...>",
- * "stream4<nx,nu>", "generic", ...; with per-instance bounds "stream4<nx,nu;ib>", "generic<ib>", "generic<f64;ib>" */
+ * "stream4<nx,nu>", "generic", ...; with per-instance bounds "stream4<nx,nu;ib>", "generic<ib>", "generic<f64;ib>"; with
+ * per-instance linear rows (beside per-instance bounds or not) "stream4<nx,nu;il>", "generic<il>", "generic<f64;il>" */
 const char *tinympc_kernel_name(tinympc_solver *s);
 /* Name of the kernel the most recent launch actually ran: the family above, or the variant a launch of that family took
  * for its calling pattern — "lean<nx,nu,N>" for one-shot solves (cold start, workspace not kept) of a one-lane-per-instance
@@ -576,7 +611,8 @@ const char *tinympc_kernel_name(tinympc_solver *s);
 const char *tinympc_last_launch_name(tinympc_solver *s);
 /* Algorithmic HBM bytes and FLOPs of one solve of the whole batch (SURVEY.md 8d formulas);
  * flops assume `iters` ADMM iterations per instance.  Per-instance bounds count too: given per knot, 2 (nx N + nu (N-1)) floats
- * per instance and iteration (max_iter of them); constant over the horizon, 2 (nx + nu) floats per instance, once. */
+ * per instance and iteration (max_iter of them); constant over the horizon, 2 (nx + nu) floats per instance, once.  Per-instance
+ * linear rows: rows_x (nx + 2) + rows_u (nu + 2) floats per instance, once. */
 double tinympc_algorithmic_bytes(tinympc_solver *s);
 double tinympc_algorithmic_flops(tinympc_solver *s, int iters);
 const char *tinympc_last_error(void);
@@ -638,6 +674,10 @@ int tinympc_sharded_set_compaction(tinympc_sharded *s, int chunk_iters);
  * instance, shard i gets the slice [lo_i, hi_i) */
 int tinympc_sharded_set_instance_bounds(tinympc_sharded *s, const double *x_min, const double *x_max, const double *u_min,
                                         const double *u_max, int per_knot);
+/* per-instance linear rows over the WHOLE batch (arguments as tinympc_set_instance_linear): contiguous per instance, shard i
+ * gets the slice [lo_i, hi_i) */
+int tinympc_sharded_set_instance_linear(tinympc_sharded *s, const double *Alin_x, int rows_x, const double *blin_x,
+                                        const double *Alin_u, int rows_u, const double *blin_u);
 /* per-instance inputs over the WHOLE batch (cols as tinympc_set_x0 / _x_ref / _u_ref), scattered to the shards */
 int tinympc_sharded_set_x0(tinympc_sharded *s, const double *x0, int cols);
 int tinympc_sharded_set_x_ref(tinympc_sharded *s, const double *x_ref, int cols);

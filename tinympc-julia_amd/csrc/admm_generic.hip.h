@@ -12,7 +12,9 @@
 // callers who want its digits back rather than the 1e-5 of the fp32-state kernels (ill-conditioned families miss 1e-5
 // there by rounding their duals to fp32 every iteration: profiles/r03_fuzz_large.txt).  The precision-2 workspace lives in
 // its own fp64 block (P.ws64, layout below); inputs x0 / references and the returned solution stay fp32 arrays.
-#pragma once
+#ifndef TMPC_ADMM_GENERIC_HIP_H   // (no #pragma once: the file includes itself once, at its end, for the per-instance-rows form's entry point)
+#define TMPC_ADMM_GENERIC_HIP_H
+#define TMPC_GENERIC_IL 0
 #include <hip/hip_runtime.h>
 
 #include "admm_params.h"
@@ -65,10 +67,27 @@ __device__ __forceinline__ double gmax(double a, double b) { return fmax(a, b); 
 __device__ __forceinline__ float gsqrt(float a) { return sqrtf(a); }
 __device__ __forceinline__ double gsqrt(double a) { return sqrt(a); }
 
+}  // namespace tmpc
+#endif  // TMPC_ADMM_GENERIC_HIP_H
+
+#ifndef TMPC_GENERIC_BOTH
+namespace tmpc {
+
 // IB: box bounds per instance (tinympc_set_instance_bounds) — read from P.ibx / P.ibu ([min | max][knot][instance][row], the
 // knot stride 0 where they are constant over the horizon) at this instance's column instead of the shared pack; fixed rho.
+// The kernel is compiled twice from this one text — the file includes itself at its end with TMPC_GENERIC_IL = 1 — as
+// admm_generic_kernel and as admm_generic_il_kernel<RT, ST>, the per-instance-rows form (tinympc_set_instance_linear): the IB
+// form whose linear rows are the instance's own, read [b]-strided from P.il_ax .. P.il_n2u ([row][instance][entry] and
+// [row][instance]).  A kernel of its own name, so that the other forms keep theirs.
+#if TMPC_GENERIC_IL
+template <class RT, class ST>
+__global__ __launch_bounds__(256) void admm_generic_il_kernel(const AdmmParams P) {
+    constexpr bool IB = true, IL = true;
+#else
 template <class RT, class ST = float, bool IB = false>
 __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
+    constexpr bool IL = false;
+#endif
     constexpr bool WIDE = sizeof(ST) == 8;
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= P.batch) return;
@@ -84,6 +103,31 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
     // linear-inequality pack: rows, right-hand sides, squared row norms, states then inputs
     const float *lAx = P.lin, *lbx = lAx + P.mlx * nx, *ln2x = lbx + P.mlx;
     const float *lAu = ln2x + P.mlx, *lbu = lAu + P.mlu * nu, *ln2u = lbu + P.mlu;
+    // entry j, right-hand side and |a|^2 of row c: the shared pack's, or (IL) this instance's own
+    auto rAx = [&](int c, int j) -> ST {
+        if constexpr (IL) return (ST)P.il_ax[(long)c * P.il_rx + b * nx + j];
+        else return (ST)lAx[c * nx + j];
+    };
+    auto rbx = [&](int c) -> ST {
+        if constexpr (IL) return (ST)P.il_bx[(long)c * P.il_rb + b];
+        else return (ST)lbx[c];
+    };
+    auto rn2x = [&](int c) -> ST {
+        if constexpr (IL) return (ST)P.il_n2x[(long)c * P.il_rb + b];
+        else return (ST)ln2x[c];
+    };
+    auto rAu = [&](int c, int j) -> ST {
+        if constexpr (IL) return (ST)P.il_au[(long)c * P.il_ru + b * nu + j];
+        else return (ST)lAu[c * nu + j];
+    };
+    auto rbu = [&](int c) -> ST {
+        if constexpr (IL) return (ST)P.il_bu[(long)c * P.il_rb + b];
+        else return (ST)lbu[c];
+    };
+    auto rn2u = [&](int c) -> ST {
+        if constexpr (IL) return (ST)P.il_n2u[(long)c * P.il_rb + b];
+        else return (ST)ln2u[c];
+    };
     const float *xmin = P.bounds, *xmax = P.bounds + EX, *umin = P.bounds + 2 * EX,
                 *umax = P.bounds + 2 * EX + EU, *cQd = P.bounds + 2 * EX + 2 * EU,
                 *cRd = P.bounds + 2 * EX + 2 * EU + nx;
@@ -249,10 +293,10 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
                 for (int a = 0; a < nu; ++a) AT(szln, k * nu + a) = AT(su, k * nu + a) + AT(syl, k * nu + a);
                 for (int c = 0; c < P.mlu; ++c) {
                     ST dot = 0;
-                    for (int j = 0; j < nu; ++j) dot = gfma((ST)lAu[c * nu + j], AT(szln, k * nu + j), dot);
-                    if (dot > (ST)lbu[c]) {
-                        const ST tt = (dot - (ST)lbu[c]) / (ST)ln2u[c];
-                        for (int j = 0; j < nu; ++j) AT(szln, k * nu + j) -= tt * (ST)lAu[c * nu + j];
+                    for (int j = 0; j < nu; ++j) dot = gfma(rAu(c, j), AT(szln, k * nu + j), dot);
+                    if (dot > rbu(c)) {
+                        const ST tt = (dot - rbu(c)) / rn2u(c);
+                        for (int j = 0; j < nu; ++j) AT(szln, k * nu + j) -= tt * rAu(c, j);
                     }
                 }
                 for (int a = 0; a < nu; ++a) {
@@ -311,10 +355,10 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
                 for (int r = 0; r < nx; ++r) AT(svln, k * nx + r) = AT(sx, k * nx + r) + AT(sgl, k * nx + r);
                 for (int c = 0; c < P.mlx; ++c) {
                     ST dot = 0;
-                    for (int j = 0; j < nx; ++j) dot = gfma((ST)lAx[c * nx + j], AT(svln, k * nx + j), dot);
-                    if (dot > (ST)lbx[c]) {
-                        const ST tt = (dot - (ST)lbx[c]) / (ST)ln2x[c];
-                        for (int j = 0; j < nx; ++j) AT(svln, k * nx + j) -= tt * (ST)lAx[c * nx + j];
+                    for (int j = 0; j < nx; ++j) dot = gfma(rAx(c, j), AT(svln, k * nx + j), dot);
+                    if (dot > rbx(c)) {
+                        const ST tt = (dot - rbx(c)) / rn2x(c);
+                        for (int j = 0; j < nx; ++j) AT(svln, k * nx + j) -= tt * rAx(c, j);
                     }
                 }
                 for (int r = 0; r < nx; ++r) {
@@ -496,3 +540,10 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
 }
 
 }  // namespace tmpc
+#if !TMPC_GENERIC_IL
+#undef TMPC_GENERIC_IL
+#define TMPC_GENERIC_IL 1
+#include "admm_generic.hip.h"
+#define TMPC_GENERIC_BOTH
+#endif
+#endif  // TMPC_GENERIC_BOTH

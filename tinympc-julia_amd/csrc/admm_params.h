@@ -113,6 +113,14 @@ struct AdmmParams {
     const float *ibx, *ibu;
     long ib_kx, ib_ku, ib_hx, ib_hu;
     int ib_on;        // IB_STATE | IB_INPUT: the sides the settings leave switched on (the other clamps against -+inf, unread)
+    // ---- stream / generic kernels, `il` forms: linear rows PER INSTANCE (tinympc_set_instance_linear), fp32, P.mlx / P.mlu
+    // rows a side as for the shared set.  Coefficients [row][instance][real entry] — the scratch block's layout, a row il_rx /
+    // il_ru elements (batch * nx / batch * nu of the solver's whole batch) behind the one before; right-hand sides and |a|^2
+    // [row][instance], a row il_rb elements apart.  Indexed by the INSTANCE, as the `ib` bounds are.  An instance's absent row
+    // is a = 0, b = FLT_MAX, |a|^2 = 1: `dot > b` never holds.  The `il` forms read their bounds from ibx / ibu (a solver with
+    // shared bounds uploads them replicated).  NULL: the rows are the shared pack's (P.lin) ----
+    const float *il_ax, *il_au, *il_bx, *il_n2x, *il_bu, *il_n2u;
+    long il_rx, il_ru, il_rb;
 };
 enum : int { IB_STATE = 1, IB_INPUT = 2 };
 enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4, HF_LEAN_SCALED = 8 };   // (HF_LEAN_SCALED: the lean pack's scaled block is valid)

@@ -19,10 +19,11 @@
 //     quad kernel); one family per instance (HET): the same rows as per-lane columns in HBM;
 //   * second-order cones may straddle lanes: squared head norms and the axis value are summed over
 //     the group with DPP steps.
-#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself twice, at its end, for the loop form's and the per-instance-bounds form's entry points)
+#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself three times, at its end, for the loop form's, the per-instance-bounds form's and the per-instance-rows form's entry points)
 #define TMPC_ADMM_STREAMG_HIP_H
 #define TMPC_STREAMG_MPC 0
 #define TMPC_STREAMG_IB 0
+#define TMPC_STREAMG_IL 0
 #include <hip/hip_runtime.h>
 
 #include "admm_generic.hip.h"   // Ws64, the type-generic gmin / gmax / gsqrt / gfma / gupmax
@@ -293,9 +294,10 @@ namespace tmpc {
 // lanes' x_j and u_a by quad broadcasts; the next solve starts from (float)x+ with the workspace as the scratch block
 // already holds it (what saving and reloading it would give: the kept arrays stay, the work arrays are zeroed), with the
 // step's slice of P.xref_seq / P.uref_seq as its references.  The last solve leaves through the ordinary epilogue.
-// The kernel below is compiled three times from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1,
-// then with TMPC_STREAMG_IB = 1 — as admm_streamg_kernel, as the loop form's admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST> and
-// as the per-instance-bounds form's admm_streamg_ib_kernel<NX, NU, G, EXT, HET, OS>.  The preprocessor decides what
+// The kernel below is compiled four times from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1,
+// then with TMPC_STREAMG_IB = 1, then with TMPC_STREAMG_IL = 1 — as admm_streamg_kernel, as the loop form's
+// admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST>, as the per-instance-bounds form's admm_streamg_ib_kernel<NX, NU, G, EXT, HET, OS>
+// and as the per-instance-rows form's admm_streamg_il_kernel<NX, NU, G, HET, OS>.  The preprocessor decides what
 // `if constexpr` cannot wrap (the loop over steps around the iteration loop, the step's reference pointers), so that the plain
 // kernel's text, name and code are what they were before the other forms existed (a further template parameter, even a
 // defaulted one, renames every stream kernel).
@@ -305,23 +307,40 @@ namespace tmpc {
 // [min | max][knot][instance][real row], the scratch block's layout — at knot strides that are 0 for bounds constant over the
 // horizon (one line per instance, re-read from cache at every knot: no further HBM stream).  The clamp is the shared form's
 // expression, so per-instance bounds that all equal a shared set give the plain kernel's results bit for bit.
-#if TMPC_STREAMG_IB
+//
+// IL: linear rows PER INSTANCE (tinympc_set_instance_linear), the file's third self-inclusion: admm_streamg_il_kernel<NX, NU, G,
+// HET, OS>, the IB form with EXT = 2 whose rows are the instance's own.  Rows are constant over the horizon, so they are read
+// from HBM once, in the prologue — P.il_ax / P.il_au, [row][instance][real entry], a lane its RX / RU entries of a row in one
+// load_rows at the IB form's instance offsets; P.il_bx .. P.il_n2u, [row][instance] — into a slice of LDS behind the bound
+// image: [row][lane][entry] (a lane's entries RX / RU words apart from its neighbour's: no bank is hit twice), then per group
+// b and |a|^2 of both sides.  Between knots they live there: not in registers ((12, 4) holds its EXT = 2 `ib` twin at two
+// wavefronts with little to spare, and 8 + 8 rows are 64 more), not re-read through the cache (a dependent load in front of
+// every row of a projection that takes them one after the other).  Only the rows present are held: 4 T (mlx RX + mlu RU) +
+// 8 (T / G) (mlx + mlu) bytes a workgroup.  The projection is project_halfspaces_group, the shared form's, on other pointers.
+#if TMPC_STREAMG_IL
+template <int NX, int NU, int G, bool HET, bool OS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES_IB(G, NX)))) void admm_streamg_il_kernel(const AdmmParams P) {
+    using RT = double;
+    using ST = float;
+    constexpr int EXT = 2;
+    constexpr bool ADP = false, MPC = false, IB = true, IL = true;
+#elif TMPC_STREAMG_IB
 template <int NX, int NU, int G, int EXT, bool HET, bool OS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES_IB(G, NX)))) void admm_streamg_ib_kernel(const AdmmParams P) {
     using RT = double;
     using ST = float;
-    constexpr bool ADP = false, MPC = false, IB = true;
+    constexpr bool ADP = false, MPC = false, IB = true, IL = false;
 #elif !TMPC_STREAMG_MPC
 template <int NX, int NU, int G, class RT, int EXT, bool HET, bool OS, bool ADP = false, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, OS) : TMPC_STREAM_WAVES(G)))) void admm_streamg_kernel(const AdmmParams P) {
-    constexpr bool MPC = false, IB = false;
+    constexpr bool MPC = false, IB = false, IL = false;
 #else
 template <int NX, int NU, int G, int EXT, bool HET, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, false) : TMPC_STREAM_WAVES(G)))) void admm_streamg_mpc_kernel(const AdmmParams P) {
     using RT = double;
-    constexpr bool OS = false, ADP = false, MPC = true, IB = false;
+    constexpr bool OS = false, ADP = false, MPC = true, IB = false, IL = false;
 #endif
     static_assert(!IB || (!ADP && sizeof(ST) == 4 && sizeof(RT) == 8 && G == 4), "per-instance bounds: fixed rho, fp32 state, fp64 recurrences, four lanes");
     static_assert(!ADP || (!HET && EXT == 0), "adaptive rho: one family, box sets only");
@@ -339,8 +358,8 @@ __global__ __launch_bounds__(256)
     float *s_bnd = reinterpret_cast<float *>(s_rawg + sizeof(RT) * G * PK::CP);
     __shared__ uint4 s_cmask[8 * G];
     // linear inequalities (EXT == 2): per row and lane role the local entries, then right-hand sides and |a|^2
-    __shared__ float s_lax[EXT == 2 ? LIN_MAX_ROWS * G * RX : 1], s_lau[EXT == 2 ? LIN_MAX_ROWS * G * RU : 1],
-        s_lb[4 * LIN_MAX_ROWS];
+    __shared__ float s_lax[EXT == 2 && !IL ? LIN_MAX_ROWS * G * RX : 1], s_lau[EXT == 2 && !IL ? LIN_MAX_ROWS * G * RU : 1],
+        s_lb[IL ? 1 : 4 * LIN_MAX_ROWS];
 
     const int N = P.N;
     const int tid = threadIdx.x;
@@ -444,7 +463,7 @@ __global__ __launch_bounds__(256)
     const uint4 *cm = s_cmask + q;
     const bool soc_x = ncx > 0, soc_u = ncu > 0;
     const int mlx = EXT == 2 ? P.mlx : 0, mlu = EXT == 2 ? P.mlu : 0;
-    if constexpr (EXT == 2) {
+    if constexpr (EXT == 2 && !IL) {
         const float *gAx = P.lin, *gbx = gAx + mlx * NX, *gn2x = gbx + mlx;
         const float *gAu = gn2x + mlx, *gbu = gAu + mlu * NU, *gn2u = gbu + mlu;
         for (int i = tid; i < LIN_MAX_ROWS * G * RX; i += T) {
@@ -464,7 +483,15 @@ __global__ __launch_bounds__(256)
         __syncthreads();
     }
     const bool lin_x = mlx > 0, lin_u = mlu > 0;
-    const float *lax = s_lax + q * RX, *lau = s_lau + q * RU;
+    // the rows this lane projects onto: its RX / RU entries of row k at lax / lau + k * LSX / LSU, right-hand sides and |a|^2 by
+    // row at lbx, ln2x, lbu, ln2u — the workgroup's shared image, or (IL) the lane's and its group's places in the LDS slice
+    // behind the bound image (filled below, once the instance offsets exist)
+    constexpr int LSX = IL ? T * RX : G * RX, LSU = IL ? T * RU : G * RU;
+    float *const s_il = IL ? s_bnd + bnd_len : nullptr;
+    float *const s_ilb = IL ? s_il + (long)T * (mlx * RX + mlu * RU) + (tid / G) * 2 * (mlx + mlu) : nullptr;
+    const float *lax = IL ? s_il + tid * RX : s_lax + q * RX, *lau = IL ? s_il + T * mlx * RX + tid * RU : s_lau + q * RU;
+    const float *lbx = IL ? s_ilb : s_lb, *ln2x = IL ? s_ilb + mlx : s_lb + LIN_MAX_ROWS;
+    const float *lbu = IL ? s_ilb + 2 * mlx : s_lb + 2 * LIN_MAX_ROWS, *ln2u = IL ? s_ilb + 2 * mlx + mlu : s_lb + 3 * LIN_MAX_ROWS;
 
     // Scratch: [array][knot][instance][real row].  Addresses are (uniform 64-bit base in SGPRs) + (32-bit byte
     // offset of the lane); the knot index is made opaque per knot (knot_sgpr) so that no per-array 64-bit
@@ -577,6 +604,36 @@ __global__ __launch_bounds__(256)
             }
         }
     };
+    if constexpr (IL) {   // this instance's rows, HBM -> the LDS slice; entries of rows the lane does not own are 0, as the shared image has them
+        const long bi = active ? b : 0;
+        for (int k = 0; k < mlx; ++k) {
+            float a[RX];
+            const float *base = P.il_ax + (long)k * P.il_rx;
+            if constexpr (XFULL) {
+                load_rows<RX>(lane_elem(sgpr_ptr(base), lxi[0]), a);
+            } else {
+#pragma unroll
+                for (int m = 0; m < RX; ++m) a[m] = *lane_elem(sgpr_ptr(base), lxi[m]);
+            }
+#pragma unroll
+            for (int m = 0; m < RX; ++m) s_il[((long)k * T + tid) * RX + m] = OKX(m) ? a[m] : 0.f;
+            if (q == 0) s_ilb[k] = P.il_bx[(long)k * P.il_rb + bi], s_ilb[mlx + k] = P.il_n2x[(long)k * P.il_rb + bi];
+        }
+        for (int k = 0; k < mlu; ++k) {
+            float a[RU];
+            const float *base = P.il_au + (long)k * P.il_ru;
+            if constexpr (UFULL) {
+                load_rows<RU>(lane_elem(sgpr_ptr(base), lui[0]), a);
+            } else {
+#pragma unroll
+                for (int m = 0; m < RU; ++m) a[m] = *lane_elem(sgpr_ptr(base), lui[m]);
+            }
+#pragma unroll
+            for (int m = 0; m < RU; ++m) s_il[(long)T * mlx * RX + ((long)k * T + tid) * RU + m] = OKU(m) ? a[m] : 0.f;
+            if (q == 0) s_ilb[2 * mlx + k] = P.il_bu[(long)k * P.il_rb + bi], s_ilb[2 * mlx + mlu + k] = P.il_n2u[(long)k * P.il_rb + bi];
+        }
+        __syncthreads();
+    }
     auto mkx = [&](ST v, int m) __attribute__((always_inline)) { return OKX(m) ? v : (ST)0; };
     auto mku = [&](ST v, int m) __attribute__((always_inline)) { return OKU(m) ? v : (ST)0; };
     const bool x_owner = ALLX || !XFULL || xl, u_owner = ALLU || !UFULL || ul;
@@ -815,7 +872,7 @@ __global__ __launch_bounds__(256)
                     if (lin_x) {
 #pragma unroll
                         for (int m = 0; m < RX; ++m) wl[m] = xf[m] + mkx(f.gl[m], m);
-                        project_halfspaces_group<G, RX>(wl, lax, G * RX, mlx, s_lb, s_lb + LIN_MAX_ROWS);
+                        project_halfspaces_group<G, RX>(wl, lax, LSX, mlx, lbx, ln2x);
 #pragma unroll
                         for (int m = 0; m < RX; ++m) {
                             gln[m] = (mkx(f.gl[m], m) + xf[m]) - wl[m];
@@ -936,8 +993,7 @@ __global__ __launch_bounds__(256)
                         if (lin_u) {
 #pragma unroll
                             for (int m = 0; m < RU; ++m) zl2[m] = uf[m] + mku(f.yl[m], m);
-                            project_halfspaces_group<G, RU>(zl2, lau, G * RU, mlu, s_lb + 2 * LIN_MAX_ROWS,
-                                                            s_lb + 3 * LIN_MAX_ROWS);
+                            project_halfspaces_group<G, RU>(zl2, lau, LSU, mlu, lbu, ln2u);
 #pragma unroll
                             for (int m = 0; m < RU; ++m) {
                                 yln[m] = (mku(f.yl[m], m) + uf[m]) - zl2[m];
@@ -1377,7 +1433,7 @@ __global__ __launch_bounds__(256)
 }
 
 }  // namespace tmpc
-#if !TMPC_STREAMG_MPC && !TMPC_STREAMG_IB
+#if !TMPC_STREAMG_MPC && !TMPC_STREAMG_IB && !TMPC_STREAMG_IL
 #undef TMPC_STREAMG_MPC
 #define TMPC_STREAMG_MPC 1
 #include "admm_streamg.hip.h"
@@ -1385,6 +1441,11 @@ __global__ __launch_bounds__(256)
 #define TMPC_STREAMG_MPC 0
 #undef TMPC_STREAMG_IB
 #define TMPC_STREAMG_IB 1
+#include "admm_streamg.hip.h"
+#undef TMPC_STREAMG_IB
+#define TMPC_STREAMG_IB 0
+#undef TMPC_STREAMG_IL
+#define TMPC_STREAMG_IL 1
 #include "admm_streamg.hip.h"
 #define TMPC_STREAMG_BOTH
 #endif

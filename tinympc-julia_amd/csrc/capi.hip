@@ -218,6 +218,15 @@ int tinympc_set_linear_constraints(tinympc_solver *s, const double *Alin_x, int 
                    [&] { return s->s.set_linear(Alin_x, rows_x, blin_x, Alin_u, rows_u, blin_u); });
 }
 
+int tinympc_set_instance_linear(tinympc_solver *s, const double *Alin_x, int rows_x, const double *blin_x,
+                                const double *Alin_u, int rows_u, const double *blin_u) {
+    if (!s) return -1;
+    return guarded("set_instance_linear",
+                   [&] { return s->s.set_instance_linear(Alin_x, rows_x, blin_x, Alin_u, rows_u, blin_u); });
+}
+
+int tinympc_lin_mode(tinympc_solver *s) { return s ? s->s.lin_mode : -1; }
+
 int tinympc_set_cone_constraints(tinympc_solver *s, const int *Acu, const int *qcu, const double *cu,
                                  int n_input_cones, const int *Acx, const int *qcx, const double *cx,
                                  int n_state_cones) {
@@ -253,6 +262,10 @@ int tinympc_set_adaptive_rho(tinympc_solver *s, int enable, double rho_min, doub
     }
     if (enable && v.bounds_mode) {
         set_error("adaptive_rho is not available with per-instance bounds (set_instance_bounds)");
+        return -1;
+    }
+    if (enable && v.lin_mode) {
+        set_error("adaptive_rho is not available with per-instance linear rows (set_instance_linear)");
         return -1;
     }
     if (enable && !(rho_min > 0.0 && rho_max >= rho_min)) {
@@ -745,6 +758,8 @@ double tinympc_algorithmic_bytes(tinympc_solver *s) {
     // (the kernels stream them with the knot's other arrays), once where they are constant over the horizon
     if (v.bounds_mode == 2) per += 4.0 * 2.0 * (EX + EU) * v.st.max_iter;
     if (v.bounds_mode == 1) per += 4.0 * 2.0 * (v.nx + v.nu);
+    // per-instance linear rows: coefficients, right-hand side and |a|^2 of every row, read once (they are constant over the horizon)
+    if (v.lin_mode) per += 4.0 * (v.mlx * (v.nx + 2.0) + v.mlu * (v.nu + 2.0));
     return per * v.batch;
 }
 
@@ -1108,6 +1123,31 @@ int set_linear_constraints(double *Alin_x_data, int Alin_x_rows, int Alin_x_cols
     const tmpc::Solver &v = g_solver->s;
     // an empty side arrives as 0 x n (TinyMPC.jl:264 zeros(0, nu)); a non-empty one must match nx / nu
     const bool has_x = Alin_x_rows > 0 && blin_x_len > 0, has_u = Alin_u_rows > 0 && blin_u_len > 0;
+    // the batch dimension rides on the widths, as set_bound_constraints' does: Alin_x rows_x x (nx*batch) with blin_x of
+    // rows_x*batch entries is one row set per instance ([batch] blocks of rows_x x nx, [batch][rows_x] in memory)
+    const int gb = global_batch();
+    const bool wide_x = has_x && gb > 1 && (long)Alin_x_cols == (long)v.nx * gb, wide_u = has_u && gb > 1 && (long)Alin_u_cols == (long)v.nu * gb;
+    if (wide_x || wide_u) {
+        if ((has_x && !wide_x) || (has_u && !wide_u) || (has_x && (long)blin_x_len != (long)Alin_x_rows * gb) ||
+            (has_u && (long)blin_u_len != (long)Alin_u_rows * gb)) {
+            set_error("set_linear_constraints: mixed widths — per-instance rows need every non-empty side per instance (Alin_x m x (nx*batch) "
+                      "with m*batch entries in blin_x, Alin_u m x (nu*batch) likewise); shared rows need m x nx and m x nu");
+            return -1;
+        }
+        const int mx = has_x ? Alin_x_rows : 0, mu = has_u ? Alin_u_rows : 0;
+        if (g_sharded) {
+            if (g_solver->s.st.adaptive_rho) {
+                set_error("set_linear_constraints: per-instance linear rows are not available with adaptive rho");
+                return -1;
+            }
+            if (mx > 0) g_solver->s.st.en_state_linear = 1;   // (the master keeps the family-level state)
+            if (mu > 0) g_solver->s.st.en_input_linear = 1;
+            return guarded("set_linear_constraints", [&] {
+                return tinympc_sharded_set_instance_linear(g_sharded.get(), Alin_x_data, mx, blin_x_data, Alin_u_data, mu, blin_u_data);
+            });
+        }
+        return tinympc_set_instance_linear(g_solver.get(), Alin_x_data, mx, blin_x_data, Alin_u_data, mu, blin_u_data);
+    }
     if ((has_x && (Alin_x_cols != v.nx || blin_x_len != Alin_x_rows)) ||
         (has_u && (Alin_u_cols != v.nu || blin_u_len != Alin_u_rows))) {
         set_error("set_linear_constraints: Alin_x must be (m x nx) with m entries in blin_x, Alin_u (m x nu) likewise");

@@ -254,6 +254,27 @@ int tinympc_sharded_set_instance_bounds(tinympc_sharded *s, const double *x_min,
     }
     return 0;
 }
+// per-instance linear rows over the WHOLE batch: both arrays of a side are contiguous per instance, shard i takes [lo_i, hi_i)
+int tinympc_sharded_set_instance_linear(tinympc_sharded *s, const double *Alin_x, int rows_x, const double *blin_x,
+                                        const double *Alin_u, int rows_u, const double *blin_u) {
+    if (!s) return -1;
+    if (rows_x < 0 || rows_u < 0 || rows_x > tmpc::LIN_MAX_ROWS || rows_u > tmpc::LIN_MAX_ROWS) {
+        set_error("set_instance_linear: at most 8 rows per side");
+        return -1;
+    }
+    if ((rows_x > 0 && (!Alin_x || !blin_x)) || (rows_u > 0 && (!Alin_u || !blin_u))) {
+        set_error("set_instance_linear: null matrix or right-hand side");
+        return -1;
+    }
+    const size_t pax = (size_t)rows_x * s->nx, pau = (size_t)rows_u * s->nu;   // elements per instance
+    for (int i = 0; i < s->n(); ++i) {
+        const size_t lo = (size_t)s->lo[i];
+        if (tinympc_set_instance_linear(s->shard[i], rows_x ? Alin_x + lo * pax : nullptr, rows_x, rows_x ? blin_x + lo * rows_x : nullptr,
+                                        rows_u ? Alin_u + lo * pau : nullptr, rows_u, rows_u ? blin_u + lo * rows_u : nullptr))
+            return -1;
+    }
+    return 0;
+}
 static int sharded_set_ref(tinympc_sharded *s, bool is_x, const double *ref, int cols) {
     if (!s || !ref) return -1;
     const int kn = is_x ? s->N : s->N - 1, rows = is_x ? s->nx : s->nu;

@@ -155,6 +155,12 @@ struct StreamEntry {
     // the name it reports, "stream4<NX,NU;ib>" — both null where the form is not built (sinst_ib_*.hip)
     hipError_t (*launch_ib)(const AdmmParams &, int ext, bool het, hipStream_t) = nullptr;
     const char *name_ib = nullptr;
+    // the per-instance-rows form (tinympc_set_instance_linear; the `ib` form with the instance's own rows), the name it
+    // reports, "stream4<NX,NU;il>", and the LDS bytes its rows take behind the image of lds_bytes — null where the form is
+    // not built (sinst_il_*.hip)
+    hipError_t (*launch_il)(const AdmmParams &, bool het, hipStream_t) = nullptr;
+    const char *name_il = nullptr;
+    size_t (*il_lds_bytes)(int mlx, int mlu) = nullptr;
 };
 const StreamEntry *find_stream_kernel(int nx, int nu);
 // One (nx, nu) instantiation of the LDS-resident matrix-core kernel with a run-time horizon (admm_mfmac.hip.h):
@@ -233,6 +239,20 @@ struct Solver {
     int set_instance_bounds(const double *xmin, const double *xmax, const double *umin, const double *umax, int per_knot);
     void drop_instance_bounds();
     int upload_instance_bounds();
+    bool ib_by_knot = false;   // the device arrays' layout as last uploaded: per knot, or one line per instance
+    // Linear rows PER INSTANCE (tinympc_set_instance_linear).  lin_mode 0: the shared set below (or none); 1: mlx / mlu rows a
+    // side, every instance its own — il_Ax [batch] blocks of mlx x nx column-major, il_bx [batch][mlx], the input side alike,
+    // the caller's fp64 arrays as given (they survive a change of precision or of the settings); d_il holds them rounded and
+    // transposed to the kernels' layout (AdmmParams::il_ax).  An all-zero row of an instance is that instance's absent row; a
+    // side that is enabled carries its slack and dual for every instance, those without a row on it included (so does a
+    // shared set whose rows never act).  Such a solver runs on the `il` forms of the stream and generic kernels only, which
+    // read their bounds per instance as the `ib` forms do (shared bounds are uploaded replicated).
+    int lin_mode = 0;
+    std::vector<double> il_Ax, il_bx, il_Au, il_bu;
+    float *d_il = nullptr;
+    int set_instance_linear(const double *Ax, int mx, const double *bx, const double *Au, int mu, const double *bu);
+    void drop_instance_linear();
+    int upload_instance_linear();
     // affine dynamics term and cone constraints (parity UNPINNED: they exist only in the absent
     // TinyMPC submodule; run on the stream kernel, or the generic one for shapes outside its grid)
     std::vector<double> fdyn;  // nx, all zero by default

@@ -3,6 +3,7 @@
 #include "admm_generic.hip.h"   // Ws64 (layout of the precision-2 workspace)
 #include "noise.h"              // the draw rule of the closed loop's noise (host and device)
 
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -188,7 +189,8 @@ int Solver::copy_family_state(const Solver &o) {
         Acx[i] = o.Acx[i], qcx[i] = o.qcx[i], cx[i] = o.cx[i];
         Acu[i] = o.Acu[i], qcu[i] = o.qcu[i], cu[i] = o.cu[i];
     }
-    mlx = o.mlx, mlu = o.mlu;
+    drop_instance_linear();   // (per-instance rows are per-instance inputs: they are not family state, on either side)
+    mlx = o.lin_mode ? 0 : o.mlx, mlu = o.lin_mode ? 0 : o.mlu;
     lin_Ax = o.lin_Ax, lin_bx = o.lin_bx, lin_Au = o.lin_Au, lin_bu = o.lin_bu;
     lin_dirty = true;
     cache = o.cache;
@@ -222,6 +224,7 @@ void Solver::free_batch() {
     dev_free(d_het_aux);
     dev_free(d_ibx);
     dev_free(d_ibu);
+    dev_free(d_il);
     dev_free(d_sgc);
     dev_free(d_svc);
     dev_free(d_syc);
@@ -393,7 +396,7 @@ Switches read_switches() {
 // lanes-per-instance family, its adaptive-rho variants included (precision = 1 — fp32 recurrences, asked for to save time —
 // stays here only where no matrix-core kernel exists, or with TINYMPC_HIP_STRICT_FP32: route_mfma)
 const KernelEntry *Solver::route_quad(bool rollout) const {
-    if (sw.no_quad || extensions_active() || hetero || bounds_mode) return nullptr;   // (per-instance bounds: the pack holds one bound image)
+    if (sw.no_quad || extensions_active() || hetero || bounds_mode || lin_mode) return nullptr;   // (per-instance bounds / rows: the pack holds one image)
     if (!st.adaptive_rho) {
         const KernelEntry *k = sw.group ? find_quad_kernel(nx, nu, N, sw.group) : nullptr;
         if (!k) k = select_quad_kernel(nx, nu, N, batch);
@@ -419,7 +422,7 @@ const KernelEntry *Solver::route_quad(bool rollout) const {
 // on the quad kernel), and the adaptive-rho variant (the instance's own Kinf as a correction to the shared products) where
 // the quad family has none
 const KernelEntry *Solver::route_mfma(bool rollout, const KernelEntry *quad) const {
-    if (strict_fp32() || sw.group || sw.no_mfma || sw.no_quad || bounds_mode) return nullptr;
+    if (strict_fp32() || sw.group || sw.no_mfma || sw.no_quad || bounds_mode || lin_mode) return nullptr;
     const KernelEntry *m = find_mfma_kernel(nx, nu, N);
     if (!m || (m->jit && sw.no_jit)) return nullptr;
     if (st.adaptive_rho)
@@ -441,6 +444,8 @@ const StreamEntry *Solver::route_stream() const {
     // per-instance bounds: the `ib` form, built for the benchmark shapes with fp64 recurrences (the 32-bit guard above covers
     // its bound arrays: an instance's rows of one knot lie below 4 batch max(nx, nu) bytes)
     if (s2 && bounds_mode && (precision != 0 || !s2->launch_ib)) s2 = nullptr;
+    // per-instance rows: the `il` form, the same three shapes; its rows take LDS behind the image
+    if (s2 && lin_mode && (precision != 0 || !s2->launch_il || s2->lds_bytes(N, precision) + s2->il_lds_bytes(mlx, mlu) > 150 * 1024)) s2 = nullptr;
     return s2;
 }
 
@@ -448,7 +453,7 @@ const StreamEntry *Solver::route_stream() const {
 // affine term, cones, linear rows, cold or kept workspace.  One family, fixed rho, the whole batch in one launch (no
 // chunks): everything else stays on the generic kernel's fp64-state form.
 const StreamEntry *Solver::route_stream_f64() const {
-    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0 || bounds_mode) return nullptr;
+    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0 || bounds_mode || lin_mode) return nullptr;
     const StreamEntry *s2 = find_stream_kernel(nx, nu);
     if (!s2 || !s2->launch_f64) return nullptr;
     if (32.0 * batch * std::max(nx, nu) >= 4.0e9) return nullptr;   // 32-bit lane byte offsets, 8-byte elements
@@ -461,7 +466,7 @@ const StreamEntry *Solver::route_stream_f64() const {
 // against 5.5 on the quad kernel), else the LDS-resident one (mfmac, any horizon).  Only where a workspace-carrying
 // kernel exists to fall back to (`fallback`).
 const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stream) const {
-    if (bounds_mode) return nullptr;
+    if (bounds_mode || lin_mode) return nullptr;
     const ConeEntry *cn = sw.no_mfmar ? nullptr : find_cone_kernel(nx, nu, N);
     if (cn && cn->supports && !cn->supports(*this)) cn = nullptr;
     const bool plain_ok = sw.mfmac_all || (cn != nullptr && cn->plain);
@@ -479,7 +484,7 @@ const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stre
 // transposed-sets matrix-core kernel: every kind of solve (one-shot, warm-started, workspace kept, chunked, the fused closed
 // loop) of a shape that has it, with the affine term / at most one cone per side (box-only problems where the entry says so)
 const ConeEntry *Solver::route_trans(bool rollout, const ConeEntry *oneshot) const {
-    if (sw.no_mfmat || sw.no_mfma || sw.group || bounds_mode) return nullptr;
+    if (sw.no_mfmat || sw.no_mfma || sw.group || bounds_mode || lin_mode) return nullptr;
     if (strict_fp32() || hetero || st.adaptive_rho || (rollout && refs_per_instance() && ref_seq_steps > 0) || st.max_iter < 1 || (double)batch * ex() >= 2.0e9)
         return nullptr;
     const ConeEntry *ct = find_trans_kernel(nx, nu, N);
@@ -514,7 +519,7 @@ std::vector<long> Solver::routing_key(bool rollout) const {
             cache_overridden, refs_device_owned, xref_kind, uref_kind, ref_mode, adapt_pure, adapt_dirty, ref_seq_steps,
             st.max_iter < 1, st.en_state_soc, st.en_input_soc, ncx, ncu, Acx[0], qcx[0], Acu[0], qcu[0], mlx, mlu, rollout, strict_precision,
             (long)route_gen, Acx[1], qcx[1], Acu[1], qcu[1], st.en_state_linear, st.en_input_linear,
-            extensions_active() && bounds_vary_by_knot(), layout_final, bounds_mode};   // (a unit specialised at setup is compiled for one bound kind)
+            extensions_active() && bounds_vary_by_knot(), layout_final, bounds_mode, lin_mode};   // (a unit specialised at setup is compiled for one bound kind)
 }
 
 int Solver::select_kernel(bool rollout) {
@@ -526,6 +531,10 @@ int Solver::select_kernel(bool rollout) {
     }
     if (st.adaptive_rho && bounds_mode) {
         set_error("adaptive_rho is not available with per-instance bounds (set_instance_bounds); shared bounds (set_bound_constraints) drop them");
+        return -1;
+    }
+    if (st.adaptive_rho && lin_mode) {
+        set_error("adaptive_rho is not available with per-instance linear rows (set_instance_linear); shared rows (set_linear_constraints) drop them");
         return -1;
     }
     if (precision == 2) {   // fp64 end to end: the stream kernel's fp64-state form (route_stream_f64), else the generic kernel's, whatever the shape
@@ -540,7 +549,7 @@ int Solver::select_kernel(bool rollout) {
         const StreamEntry *s2 = route_stream_f64();
         if (ke || ce || s2 != se) packs_dirty = true;
         ke = nullptr, se = s2, ce = nullptr;
-        kernel_name = se ? se->name_f64 : (bounds_mode ? "generic<f64;ib>" : "generic<f64>");
+        kernel_name = se ? se->name_f64 : (lin_mode ? "generic<f64;il>" : (bounds_mode ? "generic<f64;ib>" : "generic<f64>"));
         routed_key = std::move(key);
         routed = true;
         return 0;
@@ -552,7 +561,8 @@ int Solver::select_kernel(bool rollout) {
     }
     const StreamEntry *s2 = k ? nullptr : route_stream();
     if (hetero && !s2) {
-        set_error(bounds_mode ? "per-instance families with per-instance bounds need the stream kernel's ib form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
+        set_error(lin_mode ? "per-instance families with per-instance linear rows need the stream kernel's il form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
+                  bounds_mode ? "per-instance families with per-instance bounds need the stream kernel's ib form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
                   "per-instance families need a stream-kernel instantiation for (nx, nu) (nx in {2,3,4,6,8,10,12}, nu <= 4)");
         return -1;
     }
@@ -561,7 +571,7 @@ int Solver::select_kernel(bool rollout) {
     if (c2) k = nullptr, s2 = nullptr;
     if (k != ke || s2 != se || c2 != ce) packs_dirty = true;
     ke = k, se = s2, ce = c2;
-    kernel_name = ke ? ke->name : (se ? (bounds_mode ? se->name_ib : se->name) : (ce ? ce->name : (bounds_mode ? "generic<ib>" : "generic")));
+    kernel_name = ke ? ke->name : (se ? (lin_mode ? se->name_il : (bounds_mode ? se->name_ib : se->name)) : (ce ? ce->name : (lin_mode ? "generic<il>" : (bounds_mode ? "generic<ib>" : "generic"))));
     routed_key = std::move(key);
     routed = true;
     return 0;
@@ -579,6 +589,7 @@ int Solver::alloc_batch(int batch_) {
     HIP_TRY(hipSetDevice(device));
     free_batch();
     drop_instance_bounds();   // (per-instance inputs do not survive a re-batch: back to the shared bounds)
+    drop_instance_linear();   // (... and to no rows)
     drop_own_plant();         // (... and back to the model plant)
     (void)drop_ref_trajectory(false);   // (... and to the references set below)
     drop_noise();             // (... and no noise: a factor may be per instance)
@@ -690,7 +701,8 @@ int Solver::upload_packs() {
                 state_bounds_active = true;
                 break;
             }
-    if (bounds_mode && upload_instance_bounds()) return -1;
+    if ((bounds_mode || lin_mode) && upload_instance_bounds()) return -1;   // (the `il` forms read their bounds per instance too)
+    if (lin_mode && !d_il && upload_instance_linear()) return -1;
     std::vector<unsigned char> coef;
     std::vector<float> bnd;
     if (ke) {
@@ -717,7 +729,7 @@ int Solver::upload_packs() {
     // precision 2 (the generic kernel's fp64-state form, one lane per instance like this one): one-shot solves of a shape the lean
     // kernel holds run on ITS fp64-state form, specialised on request — the reference's digits at the headline kernel's speed
     // (`se` at precision 2 is the stream kernel's fp64-state form: it takes what the lean kernel leaves)
-    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise && !bounds_mode) lean_jit = true;
+    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise && !bounds_mode && !lin_mode) lean_jit = true;
     std::fill(le_var_tried, le_var_tried + LV_COUNT, false);
     lean_ok = false;
     lean_scaled_ok = false;
@@ -918,17 +930,30 @@ void Solver::drop_instance_bounds() {
     packs_dirty = true;
 }
 
-// the host copies, narrowed to fp32 and transposed from the API's instance-major layout to [min | max][knot][instance][row]
+// the host copies, narrowed to fp32 and transposed from the API's instance-major layout to [min | max][knot][instance][row].
+// A solver with shared bounds and per-instance rows (bounds_mode 0 under lin_mode) uploads the shared set replicated: one
+// line per instance, constant over the horizon — or per knot, where the shared bounds differ between knots.
 int Solver::upload_instance_bounds() {
     HIP_TRY(hipSetDevice(device));
-    const size_t Bn = (size_t)batch, kx = bounds_mode == 2 ? (size_t)N : 1, ku = bounds_mode == 2 ? (size_t)(N - 1) : 1;
+    bool shared_by_knot = false;
+    if (!bounds_mode) {
+        for (int k = 1; k < N && !shared_by_knot; ++k)
+            for (int r = 0; r < nx; ++r)
+                if (x_min[r + (size_t)k * nx] != x_min[r] || x_max[r + (size_t)k * nx] != x_max[r]) shared_by_knot = true;
+        for (int k = 1; k < N - 1 && !shared_by_knot; ++k)
+            for (int a = 0; a < nu; ++a)
+                if (u_min[a + (size_t)k * nu] != u_min[a] || u_max[a + (size_t)k * nu] != u_max[a]) shared_by_knot = true;
+    }
+    ib_by_knot = bounds_mode == 2 || shared_by_knot;
+    const size_t Bn = (size_t)batch, kx = ib_by_knot ? (size_t)N : 1, ku = ib_by_knot ? (size_t)(N - 1) : 1;
+    const bool rep = !bounds_mode;   // every instance reads the shared arrays ([knot][row])
     auto pack = [&](const std::vector<double> &lo, const std::vector<double> &hi, size_t rows, size_t knots, float *&dptr) -> int {
         const size_t half = knots * Bn * rows;
         std::vector<float> h(2 * half);
         for (size_t b = 0; b < Bn; ++b)
             for (size_t k = 0; k < knots; ++k)
                 for (size_t r = 0; r < rows; ++r) {
-                    const size_t src = (b * knots + k) * rows + r, dst = (k * Bn + b) * rows + r;
+                    const size_t src = ((rep ? 0 : b) * knots + k) * rows + r, dst = (k * Bn + b) * rows + r;
                     h[dst] = (float)lo[src];
                     h[half + dst] = (float)hi[src];
                 }
@@ -936,7 +961,100 @@ int Solver::upload_instance_bounds() {
         HIP_TRY(hipMemcpy(dptr, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     };
+    if (rep) return pack(x_min, x_max, (size_t)nx, kx, d_ibx) || pack(u_min, u_max, (size_t)nu, ku, d_ibu);
     return pack(ib_xmin, ib_xmax, (size_t)nx, kx, d_ibx) || pack(ib_umin, ib_umax, (size_t)nu, ku, d_ibu);
+}
+
+// Linear rows PER INSTANCE.  Ax is [batch] blocks of mx x nx, column-major, bx [batch][mx]; the input side likewise.  An all-zero
+// row of an instance is that instance's absent row.  Enables the non-empty sides, as set_linear does; the solver leaves the
+// on-chip families for the stream / generic kernels' `il` forms (select_kernel).  Both sides empty: no rows at all.
+int Solver::set_instance_linear(const double *Ax, int mx, const double *bx, const double *Au, int mu, const double *bu) {
+    if (mx < 0 || mu < 0 || mx > LIN_MAX_ROWS || mu > LIN_MAX_ROWS) {
+        set_error("set_instance_linear: at most 8 rows per side");
+        return -1;
+    }
+    if ((mx > 0 && (!Ax || !bx)) || (mu > 0 && (!Au || !bu))) {
+        set_error("set_instance_linear: null matrix or right-hand side");
+        return -1;
+    }
+    if (st.adaptive_rho) {
+        set_error("set_instance_linear: per-instance linear rows are not available with adaptive rho");
+        return -1;
+    }
+    if (mx == 0 && mu == 0) return set_linear(nullptr, 0, nullptr, nullptr, 0, nullptr);
+    if (wait_last_launch()) return -1;
+    const size_t Bn = (size_t)batch;
+    // what a refusal puts back
+    const int o_mode = lin_mode, o_mlx = mlx, o_mlu = mlu, o_sl = st.en_state_linear, o_il = st.en_input_linear;
+    std::vector<double> o_ax, o_bx, o_au, o_bu;
+    o_ax.swap(il_Ax), o_bx.swap(il_bx), o_au.swap(il_Au), o_bu.swap(il_bu);
+    route_gen += 1;
+    lin_mode = 1;
+    mlx = mx, mlu = mu;
+    il_Ax.assign(Ax, Ax + (mx ? Bn * mx * nx : 0));
+    il_bx.assign(bx, bx + (mx ? Bn * mx : 0));
+    il_Au.assign(Au, Au + (mu ? Bn * mu * nu : 0));
+    il_bu.assign(bu, bu + (mu ? Bn * mu : 0));
+    if (mlx > 0) st.en_state_linear = 1;
+    if (mlu > 0) st.en_input_linear = 1;
+    packs_dirty = true;
+    if (select_kernel() || ensure_extension_buffers() || upload_instance_linear()) {   // (no kernel takes the combination: the solver stays as it was)
+        const std::string why = last_error();
+        lin_mode = o_mode, mlx = o_mlx, mlu = o_mlu, st.en_state_linear = o_sl, st.en_input_linear = o_il;
+        il_Ax.swap(o_ax), il_bx.swap(o_bx), il_Au.swap(o_au), il_bu.swap(o_bu);
+        route_gen += 1;
+        dev_free(d_il);   // (re-made from the host copies at the next upload_packs where they are still per instance)
+        (void)select_kernel();
+        set_error(why);
+        return -1;
+    }
+    return 0;
+}
+
+void Solver::drop_instance_linear() {
+    if (!lin_mode) return;
+    (void)wait_last_launch();
+    lin_mode = 0;
+    mlx = mlu = 0;   // (the shared host arrays hold no rows while the per-instance ones are installed)
+    il_Ax.clear(), il_bx.clear(), il_Au.clear(), il_bu.clear();
+    lin_Ax.clear(), lin_bx.clear(), lin_Au.clear(), lin_bu.clear();
+    dev_free(d_il);
+    if (!bounds_mode) {
+        dev_free(d_ibx);
+        dev_free(d_ibu);
+    }
+    route_gen += 1;
+    lin_dirty = true;
+    packs_dirty = true;
+}
+
+// the host copies, rounded as the shared pack rounds them ((float)a, (float)b, (float) of the fp64 sum of squares of the
+// unrounded entries) and laid out as the kernels read them: Ax [row][instance][nx] | Au [row][instance][nu] | bx | |ax|^2 | bu |
+// |au|^2, each [row][instance].  An all-zero row: a = 0, b = FLT_MAX, |a|^2 = 1 — `dot > b` never holds.
+int Solver::upload_instance_linear() {
+    HIP_TRY(hipSetDevice(device));
+    const size_t Bn = (size_t)batch, nax = (size_t)mlx * Bn * nx, nau = (size_t)mlu * Bn * nu;
+    std::vector<float> h(nax + nau + 2 * Bn * (mlx + mlu));
+    auto put = [&](const std::vector<double> &A, const std::vector<double> &bv, size_t m, size_t n, float *a, float *rb, float *rn2) {
+        for (size_t b = 0; b < Bn; ++b)
+            for (size_t k = 0; k < m; ++k) {
+                double n2 = 0.0;
+                for (size_t j = 0; j < n; ++j) {
+                    const double v = A[b * m * n + k + j * m];
+                    a[(k * Bn + b) * n + j] = (float)v;
+                    n2 += v * v;
+                }
+                const bool absent = !(n2 > 0.0);
+                rb[k * Bn + b] = absent ? FLT_MAX : (float)bv[b * m + k];
+                rn2[k * Bn + b] = absent ? 1.f : (float)n2;
+            }
+    };
+    float *bx = h.data() + nax + nau, *n2x = bx + Bn * mlx, *bu = n2x + Bn * mlx, *n2u = bu + Bn * mlu;
+    put(il_Ax, il_bx, (size_t)mlx, (size_t)nx, h.data(), bx, n2x);
+    put(il_Au, il_bu, (size_t)mlu, (size_t)nu, h.data() + nax, bu, n2u);
+    if (dev_alloc(d_il, h.size())) return -1;
+    HIP_TRY(hipMemcpy(d_il, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
 }
 
 int Solver::set_fdyn(const double *f) {
@@ -989,6 +1107,7 @@ int Solver::set_cones(const int *Acu_, const int *qcu_, const double *cu_, int n
 // UNPINNED (bindings.cpp:413-450): Alin_x (mx x nx), Alin_u (mu x nu) column-major; enables the non-empty halves
 int Solver::set_linear(const double *Ax, int mx, const double *bx, const double *Au, int mu, const double *bu) {
     route_gen += 1;   // (array-valued state the routes read: the routing key only carries scalars)
+    if (lin_mode && mx >= 0 && mu >= 0 && mx <= LIN_MAX_ROWS && mu <= LIN_MAX_ROWS) drop_instance_linear();   // the shared set replaces a per-instance one
     if (mx < 0 || mu < 0 || mx > LIN_MAX_ROWS || mu > LIN_MAX_ROWS) {
         set_error("set_linear_constraints: at most 8 rows per side");
         return -1;
@@ -1112,7 +1231,7 @@ int Solver::ensure_extension_buffers() {
         HIP_TRY(hipMemset(d_syl, 0, Bn * EU * sizeof(float)));
         HIP_TRY(hipMemset(d_szl, 0, Bn * EU * sizeof(float)));
     }
-    if (lin_dirty || (lin_active() && !d_lin)) {
+    if (!lin_mode && (lin_dirty || (lin_active() && !d_lin))) {   // (per-instance rows: upload_instance_linear)
         // [mlx][nx] rows | b | |a|^2 | [mlu][nu] rows | b | |a|^2   (fp32)
         std::vector<float> pk;
         auto put = [&](const std::vector<double> &A, const std::vector<double> &b, int m, int n) {
@@ -1205,6 +1324,8 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
         if (precision == 2 && !sw.stream_mpc && !own_plant())
             return refuse("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
     }
+    if (lin_mode && !sw.stream_mpc && !(own_plant() || traj_kind))
+        return refuse("mpc_rollout: per-instance linear rows have no closed loop by default (a plant of its own, or TINYMPC_HIP_STREAM_MPC=1, gives one as a chain of launches; or step it from the host)");
     if (bounds_mode && !sw.stream_mpc)
         return refuse("mpc_rollout: per-instance bounds have no closed loop by default (TINYMPC_HIP_STREAM_MPC=1 gives one as a chain of launches; or step it from the host)");
     if (own_plant() || traj_kind) {
@@ -1446,11 +1567,17 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     P.ws64 = d_ws64;
     P.abs_pri_tol64 = st.abs_pri_tol;
     P.abs_dua_tol64 = st.abs_dua_tol;
-    if (bounds_mode) {
+    if (bounds_mode || lin_mode) {   // (ib_by_knot: upload_instance_bounds — bounds_mode 2, or shared bounds that differ between knots under lin_mode)
         P.ibx = d_ibx, P.ibu = d_ibu;
-        P.ib_kx = bounds_mode == 2 ? (long)batch * nx : 0, P.ib_ku = bounds_mode == 2 ? (long)batch * nu : 0;
-        P.ib_hx = (long)batch * nx * (bounds_mode == 2 ? N : 1), P.ib_hu = (long)batch * nu * (bounds_mode == 2 ? N - 1 : 1);
+        P.ib_kx = ib_by_knot ? (long)batch * nx : 0, P.ib_ku = ib_by_knot ? (long)batch * nu : 0;
+        P.ib_hx = (long)batch * nx * (ib_by_knot ? N : 1), P.ib_hu = (long)batch * nu * (ib_by_knot ? N - 1 : 1);
         P.ib_on = (st.en_state_bound ? IB_STATE : 0) | (st.en_input_bound ? IB_INPUT : 0);
+    }
+    if (lin_mode) {
+        const long Bn = batch;
+        P.il_ax = d_il, P.il_au = P.il_ax + (long)mlx * Bn * nx;
+        P.il_bx = P.il_au + (long)mlu * Bn * nu, P.il_n2x = P.il_bx + Bn * mlx, P.il_bu = P.il_n2x + Bn * mlx, P.il_n2u = P.il_bu + Bn * mlu;
+        P.il_rx = Bn * nx, P.il_ru = Bn * nu, P.il_rb = Bn;
     }
     P.host_flags = (sw.no_refill ? HF_NO_REFILL : 0) | (sw.no_uni ? HF_NO_UNI : 0) | (sw.no_os ? HF_NO_OS : 0) |
                    (lean_ok && lean_scaled_ok && !sw.lean_unscaled ? HF_LEAN_SCALED : 0);
@@ -1490,7 +1617,7 @@ Solver::Pick Solver::pick_kernel(const Pass &a) {
         if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, k.plan.form == LF_SPARSE ? k.plan.sp : 0, verbose), le_var_tried[v] = true;
         k.lean = le_var[v];
     }
-    k.stream_loop = a.stream_loop && !k.lean && se && !bounds_mode && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);   // (no `ib` loop form)
+    k.stream_loop = a.stream_loop && !k.lean && se && !bounds_mode && !lin_mode && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);   // (no `ib` loop form)
     return k;
 }
 
@@ -1541,6 +1668,7 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
                    : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
                          : (se ? (sloop ? se->launch_mpc(P, precision, stream_ext(), hetero, stream)
                                         : (precision == 2 ? se->launch_f64(P, stream_ext(), stream)
+                                                          : lin_mode ? se->launch_il(P, hetero, stream)
                                                           : (bounds_mode ? se->launch_ib(P, stream_ext(), hetero, stream)
                                                                          : se->launch(P, precision, stream_ext(), hetero, stream))))
                                : launch_generic(P, precision, stream))));

@@ -286,6 +286,42 @@ hipError_t launch_streamg_ib(const AdmmParams &P, int ext, bool het, hipStream_t
     return hipGetLastError();
 }
 
+// LDS bytes of the per-instance-rows form's slice behind the bound image: a lane's entries of every row present, and per group
+// b and |a|^2 of both sides (admm_streamg_il_kernel)
+template <int NX, int NU, int G>
+size_t streamg_il_lds_bytes(int mlx, int mlu) {
+    using PK = StreamPackG<NX, NU, G>;
+    return 4 * ((size_t)256 * (mlx * PK::RX + mlu * PK::RU) + (size_t)(256 / G) * 2 * (mlx + mlu));
+}
+
+// The per-instance-rows form (admm_streamg_il_kernel: the `ib` form with EXT = 2 — cones and the sides of the rows are run-time
+// flags — whose rows are the instance's own, P.il_*): one family or one per instance x OS, four kernels per (nx, nu).
+template <int NX, int NU, int G>
+hipError_t launch_streamg_il(const AdmmParams &P, bool het, hipStream_t stream) {
+    const int grid = (P.batch + 256 / G - 1) / (256 / G);
+    const size_t lds = streamg_lds_bytes<NX, NU, G>(P.N, 0) + streamg_il_lds_bytes<NX, NU, G>(P.mlx, P.mlu);
+    const bool oneshot = P.cold_start && !P.save_state;
+#define TMPC_LAUNCH(HET_, OS_)                                                                                  \
+    do {                                                                                                        \
+        if (lds > 48 * 1024)                                                                                    \
+            (void)hipFuncSetAttribute((const void *)admm_streamg_il_kernel<NX, NU, G, HET_, OS_>,               \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
+        hipLaunchKernelGGL((admm_streamg_il_kernel<NX, NU, G, HET_, OS_>), dim3(grid), dim3(256), lds, stream, P); \
+    } while (0)
+    if (het) {
+        if (oneshot) TMPC_LAUNCH(true, true); else TMPC_LAUNCH(true, false);
+    } else {
+        if (oneshot) TMPC_LAUNCH(false, true); else TMPC_LAUNCH(false, false);
+    }
+#undef TMPC_LAUNCH
+    return hipGetLastError();
+}
+
+// the per-instance-rows launcher of a shape, in a translation unit of its own (sinst_il_*.hip)
+#define TMPC_DEFINE_STREAMG_IL(NX, NU, GG)                                                               \
+    hipError_t launch_stream##GG##_il_##NX##_##NU(const AdmmParams &P, bool het, hipStream_t stream) {   \
+        return launch_streamg_il<NX, NU, GG>(P, het, stream);                                            \
+    }
 // the per-instance-bounds launcher of a shape, in a translation unit of its own (sinst_ib_*.hip)
 #define TMPC_DEFINE_STREAMG_IB(NX, NU, GG)                                                                         \
     hipError_t launch_stream##GG##_ib_##NX##_##NU(const AdmmParams &P, int ext, bool het, hipStream_t stream) {    \
@@ -302,18 +338,22 @@ hipError_t launch_streamg_ib(const AdmmParams &P, int ext, bool het, hipStream_t
         return launch_streamg_f64<NX, NU, GG>(P, ext, stream);                                                \
     }
 // ... and the entry of a shape that has one: TMPC_DEFINE_STREAMG_ENTRY plus that launcher and its reported name — and, the same
-// three shapes having them, the loop launcher (sinst_mpc_*.hip) and the per-instance-bounds launcher (sinst_ib_*.hip)
+// three shapes having them, the loop launcher (sinst_mpc_*.hip), the per-instance-bounds launcher (sinst_ib_*.hip) and the
+// per-instance-rows launcher (sinst_il_*.hip)
 #define TMPC_DEFINE_STREAMG_ENTRY_F64(NX, NU, GG)                                                                   \
     hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &, int, hipStream_t);                          \
     hipError_t launch_stream##GG##_mpc_##NX##_##NU(const AdmmParams &, int, int, bool, hipStream_t);               \
     hipError_t launch_stream##GG##_ib_##NX##_##NU(const AdmmParams &, int, bool, hipStream_t);                     \
+    hipError_t launch_stream##GG##_il_##NX##_##NU(const AdmmParams &, bool, hipStream_t);                          \
     const StreamEntry *stream##GG##_entry_##NX##_##NU() {                                                          \
         static const StreamEntry e = {NX, NU, GG, "stream" #GG "<" #NX "," #NU ">", &build_streamg_coef<NX, NU, GG>, \
                                       &build_streamg_bounds<NX, NU, GG>, &streamg_lds_bytes<NX, NU, GG>,           \
                                       &streamg_scratch_floats<NX, NU>, &launch_streamg<NX, NU, GG>,                \
                                       &launch_stream##GG##_f64_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";f64>",  \
                                       &launch_stream##GG##_mpc_##NX##_##NU, &streamg_mpc_has<NX, NU>,              \
-                                      &launch_stream##GG##_ib_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";ib>"};   \
+                                      &launch_stream##GG##_ib_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";ib>",    \
+                                      &launch_stream##GG##_il_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";il>",    \
+                                      &streamg_il_lds_bytes<NX, NU, GG>};                                          \
         return &e;                                                                                                 \
     }
 

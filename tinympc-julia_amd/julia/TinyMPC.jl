@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds, set_instance_linear,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -600,6 +600,24 @@ function set_linear_constraints(solver::TinyMPCSolver, Alin_x::Matrix{Float64}, 
               Alin_x, size(Alin_x, 1), size(Alin_x, 2), blin_x, length(blin_x),
               Alin_u, size(Alin_u, 1), size(Alin_u, 2), blin_u, length(blin_u), _flag(verbose)),
         "Failed to set linear constraints")
+end
+
+# linear rows PER INSTANCE, batch > 1: Alin_x (rows, nx, batch) with blin_x (rows, batch), Alin_u (rows, nu, batch) with blin_u
+# (rows, batch); an empty side is zeros(0, n, batch) with zeros(0, batch); an all-zero row of an instance is a row that
+# instance does not have.  The batch dimension rides on the widths of the process-global entry point, as for
+# set_bound_constraints.  The solver then runs on the `il` form of the stream or the generic kernel (kernel_name()); the
+# shared method above returns it to shared rows.  Not with adaptive rho; mpc_rollout only as a chain of launches.
+# (Written and not executed, like the rest of this file: no Julia on the build machine.)
+function set_instance_linear(solver::TinyMPCSolver, Alin_x::Array{Float64,3}, blin_x::Matrix{Float64},
+                             Alin_u::Array{Float64,3}, blin_u::Matrix{Float64}; verbose::Bool=false)
+    _need(solver)
+    Ax, Au = _mat(Alin_x), _mat(Alin_u)
+    bx, bu = vec(blin_x), vec(blin_u)
+    _ok(ccall((:set_linear_constraints, _lib_path()), Int32,
+              (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32),
+              Ax, size(Ax, 1), size(Ax, 2), bx, length(bx),
+              Au, size(Au, 1), size(Au, 2), bu, length(bu), _flag(verbose)),
+        "Failed to set per-instance linear constraints")
 end
 
 function set_equality_constraints(solver::TinyMPCSolver, Aeq_x::Matrix{Float64}, beq_x::Vector{Float64};

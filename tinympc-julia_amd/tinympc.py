@@ -86,6 +86,8 @@ SIGNATURES = {
     "tinympc_enable_cones": (c_int, [c_vp, c_int, c_int]),
     "tinympc_set_linear_constraints": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_int, c_dp]),
     "tinympc_enable_linear": (c_int, [c_vp, c_int, c_int]),
+    "tinympc_set_instance_linear": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_int, c_dp]),
+    "tinympc_lin_mode": (c_int, [c_vp]),
     "tinympc_set_x0": (c_int, [c_vp, c_dp, c_int]),
     "tinympc_set_x_ref": (c_int, [c_vp, c_dp, c_int]),
     "tinympc_set_u_ref": (c_int, [c_vp, c_dp, c_int]),
@@ -203,6 +205,7 @@ SIGNATURES = {
     "tinympc_sharded_update_settings": (c_int, [c_vp, c_dbl, c_dbl, c_int, c_int, c_int, c_int]),
     "tinympc_sharded_set_bound_constraints": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "tinympc_sharded_set_instance_bounds": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_int]),
+    "tinympc_sharded_set_instance_linear": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_int, c_dp]),
     "tinympc_sharded_set_warm_start": (c_int, [c_vp, c_int]),
     "tinympc_sharded_reset": (c_int, [c_vp]),
     "tinympc_sharded_set_precision": (c_int, [c_vp, c_int]),
@@ -928,11 +931,32 @@ def _lin_block(A, b, n):
     return A, b
 
 
+def _instance_linear(A, b, n, batch):
+    """one side of set_instance_linear, (rows, n, B) with (rows, B), in the library's layout: [B] blocks of rows x n,
+    column-major, and [B][rows]; an empty side (None, or zero rows) gives 0 rows"""
+    if A is None or np.asarray(A).size == 0:
+        return np.zeros(0), np.zeros(0), 0
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if A.ndim != 3 or b.ndim != 2 or A.shape[1:] != (n, batch) or b.shape != (A.shape[0], batch):
+        raise TinyMPCError(f"set_instance_linear: expected (rows, {n}, {batch}) with (rows, {batch})")
+    return (np.ascontiguousarray(np.asfortranarray(A).reshape(-1, order="F")),
+            np.ascontiguousarray(np.asfortranarray(b).reshape(-1, order="F")), A.shape[0])
+
+
 def set_linear_constraints(solver, Alin_x, blin_x, Alin_u, blin_u, *, verbose=False):
-    """TinyMPC.jl:229-243: Alin_x x <= blin_x, Alin_u u <= blin_u at every knot; parity unpinned."""
+    """TinyMPC.jl:229-243: Alin_x x <= blin_x, Alin_u u <= blin_u at every knot; parity unpinned.  (rows, nx)
+    with (rows,) shared by the batch, or — batch > 1 — (rows, nx, batch) with (rows, batch): every instance its own rows
+    (an all-zero row is a row that instance does not have); the input side alike."""
     _need_setup(solver)
-    Ax, bx = _lin_block(Alin_x, blin_x, solver.nx)
-    Au, bu = _lin_block(Alin_u, blin_u, solver.nu)
+    def side(A, b, n):     # a 3-D side travels with the batch on its width; the library refuses mixed widths by name
+        if A is not None and np.asarray(A).ndim == 3:
+            A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+            return (_mat(np.asfortranarray(A).reshape(A.shape[0], -1, order="F")),
+                    np.ascontiguousarray(np.asfortranarray(b).reshape(-1, order="F")))
+        return _lin_block(np.zeros((0, n)) if A is None else A, [] if b is None else b, n)
+    Ax, bx = side(Alin_x, blin_x, solver.nx)
+    Au, bu = side(Alin_u, blin_u, solver.nu)
     status = load_library().set_linear_constraints(_dp(Ax), Ax.shape[0], Ax.shape[1], _dp(bx), len(bx),
                                                    _dp(Au), Au.shape[0], Au.shape[1], _dp(bu), len(bu),
                                                    1 if verbose else 0)
@@ -1154,6 +1178,20 @@ class BatchSolver:
         Au, bu = _lin_block(Alin_u, blin_u, self.nu)
         self._chk(self.lib.tinympc_set_linear_constraints(self.h, _dp(Ax), Ax.shape[0], _dp(bx), _dp(Au), Au.shape[0],
                                                           _dp(bu)), "set_linear_constraints")
+
+    def set_instance_linear(self, Alin_x, blin_x, Alin_u, blin_u):
+        """linear rows PER INSTANCE: Alin_x (rows, nx, B) with blin_x (rows, B), Alin_u (rows, nu, B) with blin_u (rows, B); an
+        empty side is None or zero rows; an all-zero row of an instance is a row that instance does not have.  The solver
+        then runs on the `il` form of the stream or the generic kernel; set_linear_constraints returns it to shared rows.
+        Not with adaptive rho; mpc_rollout only as a chain (a plant of its own, or TINYMPC_HIP_STREAM_MPC)."""
+        Ax, bx, mx = _instance_linear(Alin_x, blin_x, self.nx, self.batch)
+        Au, bu, mu = _instance_linear(Alin_u, blin_u, self.nu, self.batch)
+        self._chk(self.lib.tinympc_set_instance_linear(self.h, _dp(Ax) if mx else None, mx, _dp(bx) if mx else None,
+                                                       _dp(Au) if mu else None, mu, _dp(bu) if mu else None), "set_instance_linear")
+
+    def lin_mode(self):
+        """0 no rows or rows shared by the batch, 1 per instance"""
+        return int(self.lib.tinympc_lin_mode(self.h))
 
     def enable_linear(self, en_state_linear, en_input_linear):
         """the two linear-row switches of update_settings (TinyMPC.jl:98-99) on their own: a side keeps its rows while it is off"""
@@ -1697,6 +1735,13 @@ class ShardedBatchSolver:
             raise TinyMPCError("set_instance_bounds: expected (nx, batch) / (nu, batch) or (nx, N, batch) / (nu, N-1, batch)")
         self._chk(self.lib.tinympc_sharded_set_instance_bounds(self.h, *[_dp(f) for f in flat], 1 if per_knot else 0),
                   "set_instance_bounds")
+
+    def set_instance_linear(self, Alin_x, blin_x, Alin_u, blin_u):
+        """per-instance linear rows over the whole batch (shapes as BatchSolver.set_instance_linear), scattered to the shards"""
+        Ax, bx, mx = _instance_linear(Alin_x, blin_x, self.nx, self.batch)
+        Au, bu, mu = _instance_linear(Alin_u, blin_u, self.nu, self.batch)
+        self._chk(self.lib.tinympc_sharded_set_instance_linear(self.h, _dp(Ax) if mx else None, mx, _dp(bx) if mx else None,
+                                                               _dp(Au) if mu else None, mu, _dp(bu) if mu else None), "set_instance_linear")
 
     def set_warm_start(self, on):
         self._chk(self.lib.tinympc_sharded_set_warm_start(self.h, 1 if on else 0), "set_warm_start")
