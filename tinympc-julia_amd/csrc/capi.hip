@@ -176,6 +176,7 @@ int tinympc_enable_cones(tinympc_solver *s, int en_state_soc, int en_input_soc) 
     s->s.st.en_state_soc = en_state_soc ? 1 : 0;
     s->s.st.en_input_soc = en_input_soc ? 1 : 0;
     s->s.route_gen += 1;
+    s->s.packs_dirty = true;   // (upload_packs decides from extensions_active() whether the lean kernel takes one-shot solves)
     return 0;
 }
 
@@ -208,6 +209,7 @@ int tinympc_enable_linear(tinympc_solver *s, int en_state_linear, int en_input_l
     s->s.st.en_input_linear = en_input_linear ? 1 : 0;
     s->s.lin_dirty = true;   // the device pack holds the enabled sides only
     s->s.route_gen += 1;
+    s->s.packs_dirty = true;   // (upload_packs decides from extensions_active() whether the lean kernel takes one-shot solves)
     return 0;
 }
 

@@ -547,7 +547,9 @@ int Solver::select_kernel(bool rollout) {
             return -1;
         }
         const StreamEntry *s2 = route_stream_f64();
-        if (ke || ce || s2 != se) packs_dirty = true;
+        // (the key moved: whether the lean kernel's fp64-state form takes the one-shot solves — lean_jit, its pack — is decided
+        // with the packs, from the extensions as they are now, also where the entries stay what they were)
+        packs_dirty = true;
         ke = nullptr, se = s2, ce = nullptr;
         kernel_name = se ? se->name_f64 : (lin_mode ? "generic<f64;il>" : (bounds_mode ? "generic<f64;ib>" : "generic<f64>"));
         routed_key = std::move(key);
@@ -1101,6 +1103,7 @@ int Solver::set_cones(const int *Acu_, const int *qcu_, const double *cu_, int n
     }
     if (ncu > 0) st.en_input_soc = 1;  // bindings.cpp:478-483: only the non-empty halves are enabled
     if (ncx > 0) st.en_state_soc = 1;
+    packs_dirty = true;   // (what upload_packs decides from extensions_active(): lean_jit)
     return select_kernel() || ensure_extension_buffers();
 }
 
@@ -1144,6 +1147,7 @@ int Solver::set_linear(const double *Ax, int mx, const double *bx, const double 
     lin_dirty = true;
     if (mlx > 0) st.en_state_linear = 1;  // bindings.cpp:438-443: only the non-empty halves are enabled
     if (mlu > 0) st.en_input_linear = 1;
+    packs_dirty = true;   // (what upload_packs decides from extensions_active(): lean_jit)
     return select_kernel() || ensure_extension_buffers();
 }
 
