@@ -86,19 +86,6 @@ __global__ void __launch_bounds__(256) estimator_step_kernel(EstimatorStep a) {
 }
 
 // ---- the solver's side ----
-template <class T>
-static int dev_realloc(T *&p, size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    HIP_TRY(hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)));
-    return 0;
-}
-template <class T>
-static void dev_drop(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 int Solver::estimator_step(hipStream_t stream, bool predict, bool correct, int mpc_steps, int step) {
     const long per_block = 256 / nx;
     const bool measured = noise_kind[NOISE_MEASUREMENT] != 0;
@@ -130,11 +117,11 @@ int Solver::estimator_step(hipStream_t stream, bool predict, bool correct, int m
 // the logs of a loop of mpc_steps: (float)xhat_t in d_mpc_y (the buffer measurement noise logs into without an estimator), (float)y_t
 int Solver::ensure_estimator_logs(int mpc_steps) {
     if (mpc_y_cap < mpc_steps) {
-        if (dev_realloc(d_mpc_y, (size_t)batch * mpc_steps * nx)) return -1;
+        if (d_mpc_y.alloc((size_t)batch * mpc_steps * nx)) return -1;
         mpc_y_cap = mpc_steps;
     }
     if (mpc_yout_cap < mpc_steps) {
-        if (dev_realloc(d_mpc_yout, (size_t)batch * mpc_steps * est_ny)) return -1;
+        if (d_mpc_yout.alloc((size_t)batch * mpc_steps * est_ny)) return -1;
         mpc_yout_cap = mpc_steps;
     }
     mpc_y_steps = mpc_yout_steps = mpc_steps;
@@ -146,14 +133,14 @@ void Solver::drop_estimator() {
     (void)wait_last_launch();   // (a chain still running reads and writes them)
     est_kind = est_ny = 0;
     est_C.clear(), est_L.clear();
-    dev_drop(d_est_C);
-    dev_drop(d_est_L);
-    dev_drop(d_xhat);
-    dev_drop(d_model);
-    dev_drop(d_mpc_yout);
+    d_est_C.free();
+    d_est_L.free();
+    d_xhat.free();
+    d_model.free();
+    d_mpc_yout.free();
     mpc_yout_cap = mpc_yout_steps = 0;
     if (!noise_kind[NOISE_MEASUREMENT]) {   // (the estimate's log is not a measurement log)
-        dev_drop(d_mpc_y);
+        d_mpc_y.free();
         mpc_y_cap = 0;
     }
     mpc_y_steps = 0;
@@ -185,12 +172,10 @@ int Solver::set_estimator(const double *C, int ny, const double *L, int per_inst
     const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)nx * ny;
     est_C.assign(C, C + n);
     est_L.assign(L, L + n);
-    if (dev_realloc(d_est_C, n) || dev_realloc(d_est_L, n)) return -1;
-    HIP_TRY(hipMemcpy(d_est_C, est_C.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_est_L, est_L.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    if (!d_xhat && dev_realloc(d_xhat, (size_t)batch * nx)) return -1;
+    if (d_est_C.upload(est_C) || d_est_L.upload(est_L)) return -1;
+    if (!d_xhat && d_xhat.alloc((size_t)batch * nx)) return -1;
     if (ny != est_ny) {   // (the output log's row length)
-        dev_drop(d_mpc_yout);
+        d_mpc_yout.free();
         mpc_yout_cap = mpc_yout_steps = 0;
     }
     est_kind = per_instance ? 2 : 1, est_ny = ny;

@@ -66,7 +66,7 @@ std::string lib_dir() {   // .../tinympc-julia_amd/lib (where this library was l
 }
 // FNV-1a over the kernel headers: the cache key of everything a unit is compiled from
 std::string source_hash(const std::string &csrc) {
-    static const char *files[] = {"admm_params.h", "solver.h", "host_setup.h", "admm_quad.hip.h", "quad_entry.hip.h", "admm_mfma.hip.h",
+    static const char *files[] = {"admm_params.h", "solver.h", "devbuf.h", "host_setup.h", "admm_quad.hip.h", "quad_entry.hip.h", "admm_mfma.hip.h",
                                   "mfma_entry.hip.h", "admm_mfmac.hip.h", "mfmac_entry.hip.h", "admm_mfmat.hip.h", "mfmat_entry.hip.h",
                                   "admm_lean.hip.h", "lean_entry.hip.h"};
     unsigned long long h = 1469598103934665603ull;

@@ -161,18 +161,13 @@ __global__ void metrics_summary_final_kernel(double *summary, const double *part
 }
 
 // ---- host side ----
-static void dev_free_d(double *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 void Solver::drop_rollout_metrics() {
     if (!metrics_on && !d_metrics) return;
     (void)wait_last_launch();   // (a fold still running reads and writes them)
     metrics_on = false;
-    dev_free_d(d_metrics);
-    dev_free_d(d_metric_cfg);
-    dev_free_d(d_metric_part);
+    d_metrics.free();
+    d_metric_cfg.free();
+    d_metric_part.free();
     metric_limits = 0;
 }
 
@@ -216,13 +211,13 @@ int Solver::set_rollout_metrics(int enable, const double *qw, const double *rw, 
     HIP_TRY(hipSetDevice(device));
     if (wait_last_launch()) return -1;   // (a fold still running reads the configuration)
     const size_t n = (size_t)batch * METRIC_COUNT;
-    if (!d_metrics) {
-        HIP_TRY(hipMalloc((void **)&d_metrics, n * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&d_metric_cfg, h.size() * sizeof(double)));
-        HIP_TRY(hipMalloc((void **)&d_metric_part, (size_t)(METRIC_SUMMARY_GROUPS + 1) * METRIC_SUMMARY * sizeof(double)));
+    // all three or none: !d_metrics means that none of them exists
+    if (!d_metrics && (d_metrics.alloc(n) || d_metric_cfg.alloc(h.size()) || d_metric_part.alloc((size_t)(METRIC_SUMMARY_GROUPS + 1) * METRIC_SUMMARY))) {
+        d_metrics.free(), d_metric_cfg.free(), d_metric_part.free();
+        return -1;
     }
     HIP_TRY(hipMemcpy(d_metric_cfg, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_metrics, 0, n * sizeof(double)));
+    if (d_metrics.zero()) return -1;
     metric_limits = (x_lo ? 1 : 0) | (x_hi ? 2 : 0) | (u_lo ? 4 : 0) | (u_hi ? 8 : 0);
     metrics_on = true;
     return 0;
@@ -235,8 +230,7 @@ int Solver::reset_rollout_metrics() {
     }
     HIP_TRY(hipSetDevice(device));
     if (wait_last_launch()) return -1;
-    HIP_TRY(hipMemset(d_metrics, 0, (size_t)batch * METRIC_COUNT * sizeof(double)));
-    return 0;
+    return d_metrics.zero();
 }
 
 // The fold of the rollout just enqueued on `stream`, behind it; cursor0: the reference cursor the rollout started from.  The

@@ -85,7 +85,7 @@ struct tinympc_sharded {
     std::vector<tinympc_solver *> shard;
     std::vector<int> dev, lo, hi;
     std::vector<hipStream_t> stream;
-    std::vector<uint32_t *> d_fold;   // [GSTAT_WORDS] per device: the all-reduce operand
+    std::vector<tmpc::DevBuf<uint32_t>> d_fold;   // [GSTAT_WORDS] per device: the all-reduce operand
     std::vector<ncclComm_t> comm;     // empty: host fold (repeated devices)
     uint32_t h_fold[tmpc::GSTAT_WORDS] = {0};
     bool pending = false;
@@ -100,7 +100,7 @@ struct tinympc_sharded {
             if (c && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c);
         for (int i = 0; i < n(); ++i) {
             (void)hipSetDevice(dev[i]);
-            if (i < (int)d_fold.size() && d_fold[i]) (void)hipFree(d_fold[i]);
+            if (i < (int)d_fold.size()) d_fold[i].free();
             if (i < (int)stream.size() && stream[i]) (void)hipStreamDestroy(stream[i]);
             tinympc_destroy(shard[i]);
         }
@@ -167,10 +167,8 @@ int tinympc_create_sharded(tinympc_sharded **out, const double *A, const double 
         hipStream_t st = nullptr;
         SH_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         s->stream.push_back(st);
-        uint32_t *f = nullptr;
-        SH_TRY(hipMalloc((void **)&f, tmpc::GSTAT_WORDS * sizeof(uint32_t)));
-        SH_TRY(hipMemset(f, 0, tmpc::GSTAT_WORDS * sizeof(uint32_t)));
-        s->d_fold.push_back(f);
+        s->d_fold.emplace_back();
+        if (s->d_fold.back().alloc_zero(tmpc::GSTAT_WORDS)) return -1;
     }
     if ((int)distinct.size() == n_gpus) {
         // one communicator per device, all owned by this process (ncclCommInitAll); a single device is a one-rank clique

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "admm_params.h"
+#include "devbuf.h"
 #include "host_setup.h"
 
 namespace tmpc {
@@ -220,7 +221,32 @@ struct Settings {
     double adaptive_rho_min = 0.1, adaptive_rho_max = 10.0;
 };
 
-struct Solver {
+// The device buffers sized by the batch.  A buffer declared HERE dies at a re-batch (Solver::free_batch assigns a fresh
+// BatchBuffers over this part of the solver); one declared in Solver itself lives until the solver goes.
+struct BatchBuffers {
+    DevBuf<float> d_x0, d_xref, d_uref;   // (the reference arrays grow on demand: upload_refs, set_ref_trajectory)
+    DevBuf<float> d_xout, d_uout, d_res;
+    DevBuf<int> d_iter, d_solved;
+    DevBuf<float> d_sd, d_sy, d_sz, d_sg, d_sv;
+    DevBuf<float> d_scratch;
+    DevBuf<double> d_ws64;                // precision 2: the fp64 workspace block (admm_generic.hip.h, Ws64)
+    DevBuf<float> d_het_aux;
+    DevBuf<float> d_ibx, d_ibu, d_il;     // per-instance bounds and rows in the kernels' layout
+    DevBuf<float> d_sgc, d_svc, d_syc, d_szc;
+    DevBuf<int> d_idx[2], d_count;        // chunked solves: the index lists of the instances still iterating
+    DevBuf<float> d_lin, d_sgl, d_svl, d_syl, d_szl;
+    DevBuf<double> d_adapt;
+    DevBuf<unsigned char> d_adp_cols;     // stream kernel, adaptive rho: per-lane coefficient columns (scratch)
+    DevBuf<double> d_x0d;                 // [B][nx] plant state
+    DevBuf<float> d_mpc_x, d_mpc_u;       // closed-loop logs
+    DevBuf<int> d_mpc_iter;
+    DevBuf<float> d_mpc_y, d_mpc_yout;
+    DevBuf<float> d_xref_seq, d_uref_seq; // shared references of every step of a fused closed loop
+    DevBuf<double> d_metrics, d_metric_cfg, d_metric_part;
+    DevBuf<double> d_est_C, d_est_L, d_xhat;
+};
+
+struct Solver : BatchBuffers {
     int nx = 0, nu = 0, N = 0, batch = 1, device = 0;
     int verbose = 0;
     Mat A, B, Q, R;
@@ -235,7 +261,6 @@ struct Solver {
     // `ib` forms of the stream and generic kernels only: the on-chip families' packs hold one bound image.
     int bounds_mode = 0;
     std::vector<double> ib_xmin, ib_xmax, ib_umin, ib_umax;
-    float *d_ibx = nullptr, *d_ibu = nullptr;
     int set_instance_bounds(const double *xmin, const double *xmax, const double *umin, const double *umax, int per_knot);
     void drop_instance_bounds();
     int upload_instance_bounds();
@@ -249,7 +274,6 @@ struct Solver {
     // read their bounds per instance as the `ib` forms do (shared bounds are uploaded replicated).
     int lin_mode = 0;
     std::vector<double> il_Ax, il_bx, il_Au, il_bu;
-    float *d_il = nullptr;
     int set_instance_linear(const double *Ax, int mx, const double *bx, const double *Au, int mu, const double *bu);
     void drop_instance_linear();
     int upload_instance_linear();
@@ -260,13 +284,11 @@ struct Solver {
     int ncx = 0, ncu = 0;
     int Acx[8] = {0}, qcx[8] = {0}, Acu[8] = {0}, qcu[8] = {0};
     double cx[8] = {0}, cu[8] = {0};
-    float *d_sgc = nullptr, *d_svc = nullptr, *d_syc = nullptr, *d_szc = nullptr;
     bool cones_active() const { return (st.en_state_soc && ncx > 0) || (st.en_input_soc && ncu > 0); }
     // linear inequalities Alin_x x <= blin_x, Alin_u u <= blin_u at every knot (bindings.cpp:413-450; UNPINNED):
     // rows row-major fp64, at most LIN_MAX_ROWS per side
     int mlx = 0, mlu = 0;
     std::vector<double> lin_Ax, lin_bx, lin_Au, lin_bu;
-    float *d_lin = nullptr, *d_sgl = nullptr, *d_svl = nullptr, *d_syl = nullptr, *d_szl = nullptr;
     bool lin_dirty = false;
     bool lin_active() const { return (st.en_state_linear && mlx > 0) || (st.en_input_linear && mlu > 0); }
     // constraint sets whose arrays the stream / generic scratch lays out: box | + cones | + linear
@@ -280,9 +302,7 @@ struct Solver {
     // adaptive kernel leaves; false once the tables change under a live state): the matrix-core variant rebuilds an instance's
     // Kinf / Pinf from rho_b alone
     bool adapt_pure = true;
-    double *d_sens = nullptr, *d_adapt = nullptr;
-    unsigned char *d_adp_cols = nullptr;  // stream kernel, adaptive rho: per-lane coefficient columns (scratch)
-    size_t adp_cols_bytes = 0;
+    DevBuf<double> d_sens;
     int set_sensitivity(const double *dK, const double *dP);
     int get_adaptive_state(double *rho, double *Kinf, double *Pinf);
     // one problem family PER INSTANCE: per-instance A, B (column-major, concatenated),
@@ -292,7 +312,6 @@ struct Solver {
     bool layout_final = false;    // a constraint layout is specialised (jit_trans_for) from the first solve on, not while the setters run
     std::vector<double> het_A, het_B;
     std::vector<Cache> het_cache;
-    float *d_het_aux = nullptr;
     // references as last set by the host API: kind 0 zero / 1 shared / 2 per instance
     std::vector<float> h_xref, h_uref;
     int xref_kind = 0, uref_kind = 0;
@@ -315,7 +334,7 @@ struct Solver {
     bool lean_jit = false;                // no built-in lean instantiation: single variants specialised at the launches that need them
     const LeanEntry *le_var[LV_COUNT] = {};
     bool le_var_tried[LV_COUNT] = {};
-    double *d_lean = nullptr;
+    DevBuf<double> d_lean;
     bool lean_ok = false, lean_knot_bounds = false;
     bool lean_enabled = true;             // TINYMPC_HIP_NO_LEAN, read once at creation
     uint64_t lean_sp = 0;                 // the (A, B) pattern of the model (lean_pattern), set with the pack
@@ -324,20 +343,14 @@ struct Solver {
     int last_lean_form = LF_NONE;         // the sweeps of the most recent launch (LF_*), and the per-knot fp64 costs it
     int last_lean_cost[2] = {0, 0};       // weighed: the sparse form's (its pattern's), the form it replaces
     std::string last_launch_name;         // the kernel the most recent launch actually ran (family or its lean variant)
-    // device buffers
-    unsigned char *d_coef = nullptr;
-    float *d_bounds = nullptr;
-    float *d_x0 = nullptr, *d_xref = nullptr, *d_uref = nullptr;
-    size_t xref_cap = 0, uref_cap = 0;  // floats allocated
-    float *d_xout = nullptr, *d_uout = nullptr, *d_res = nullptr;
-    int *d_iter = nullptr, *d_solved = nullptr;
-    float *d_sd = nullptr, *d_sy = nullptr, *d_sz = nullptr, *d_sg = nullptr, *d_sv = nullptr;
-    uint32_t *d_gstat = nullptr;  // [2 * GSTAT_WORDS]: the public status block, then the kernels' accumulator
-    uint32_t *d_gslot = nullptr;  // [GSLOT_DEFAULT_CAP][GSLOT_WORDS]: the workgroups' status records (fold_status), never zeroed
-    uint32_t *h_gstat = nullptr;  // pinned
+    // device buffers that survive a re-batch (those that do not: BatchBuffers)
+    DevBuf<unsigned char> d_coef;
+    DevBuf<float> d_bounds;
+    DevBuf<uint32_t> d_gstat;     // [2 * GSTAT_WORDS]: the public status block, then the kernels' accumulator
+    DevBuf<uint32_t> d_gslot;     // [GSLOT_DEFAULT_CAP][GSLOT_WORDS]: the workgroups' status records (fold_status), never zeroed
+    PinnedBuf<uint32_t> h_gstat;
     // host round trips (fp64 caller buffers <-> fp32 device buffers): pinned staging, copy stream, two chunk slots
-    float *h_stage = nullptr;
-    size_t stage_cap = 0;  // floats
+    PinnedBuf<float> h_stage;
     hipStream_t s_copy = nullptr;
     hipEvent_t ev_copy[2] = {nullptr, nullptr};
     int d2h_double(const float *d, double *out, size_t n);
@@ -347,13 +360,7 @@ struct Solver {
     int pin_host_range(void *p, size_t bytes);
     int unpin_host_range(void *p);
     int h2d_float(float *d, const double *in, size_t n);
-    float *d_scratch = nullptr;
-    double *d_ws64 = nullptr;    // precision 2: the fp64 workspace block (admm_generic.hip.h, Ws64)
-    size_t ws64_cap = 0;
-    float *d_mpc_x = nullptr, *d_mpc_u = nullptr;  // fused closed-loop logs
-    int *d_mpc_iter = nullptr;
     int mpc_cap = 0, mpc_steps_last = 0;
-    size_t scratch_cap = 0;
     bool solved_once = false;
     bool g_maybe_nonzero = false;  // the workspace's state dual may hold non-zeros (see launch_pass)
     bool profiling = false;
@@ -403,7 +410,6 @@ struct Solver {
     int set_x0(const double *x0, int cols);
     int set_ref(bool is_x, const double *ref, int cols);
     int set_ref_sequence(const double *x_seq, const double *u_seq, int steps);
-    float *d_xref_seq = nullptr, *d_uref_seq = nullptr;  // shared references of every step of a fused closed loop
     int ref_seq_steps = 0;
     int set_bounds(const double *xmin, const double *xmax, const double *umin, const double *umax);
     int set_fdyn(const double *f);
@@ -466,7 +472,7 @@ struct Solver {
     // The plant of every chain, one image: d_plant is [A | B | f] column-major fp64, one block or [batch] blocks plant_stride()
     // apart — the installed plant (set_plant), else the model's A, B and affine term (a family solver: every instance's A_b, B_b
     // and the shared f).  plant_dirty: to be (re)written by ensure_plant before the next chain — set_plant, set_fdyn, a re-batch.
-    double *d_plant = nullptr, *d_x0d = nullptr;  // (d_x0d: [B][nx] plant state)
+    DevBuf<double> d_plant;
     bool plant_dirty = true;
     bool x0d_live = false;                        // d_x0d holds the plant state a from_x0 chain or the stream loop left (plant_start)
     int plant_start(hipStream_t stream, bool resume);   // x0d <- x0, or (resume, x0d_live) the state the last loop left where x0 still is its rounding
@@ -478,7 +484,7 @@ struct Solver {
     // solver, whose closed loop is the chain on the kernel a kept-workspace solve takes (plan_rollout).
     int plant_kind = 0, dist_kind = 0, dist_steps = 0;
     std::vector<double> own_A, own_B, own_f, dist_w;
-    double *d_dist = nullptr;
+    DevBuf<double> d_dist;
     bool own_plant() const { return plant_kind != 0 || dist_kind != 0 || noisy() || estimating(); }
     bool own_plant_per_instance() const { return plant_kind == 2 || (plant_kind == 0 && hetero); }
     long plant_stride() const { return own_plant_per_instance() ? (long)nx * nx + (long)nx * nu + nx : 0L; }
@@ -497,8 +503,7 @@ struct Solver {
     unsigned long long noise_seed[2] = {0, 0};
     int noise_cursor = 0;
     std::vector<double> noise_G[2];
-    double *d_noise_G[2] = {nullptr, nullptr};
-    float *d_mpc_y = nullptr;
+    DevBuf<double> d_noise_G[2];
     int mpc_y_cap = 0, mpc_y_steps = 0;   // steps allocated; steps of the loop that wrote it (0: none)
     bool noisy() const { return noise_kind[0] != 0 || noise_kind[1] != 0; }
     int noise_mode() const { return noise_kind[0] | (noise_kind[1] == 1 ? 4 : (noise_kind[1] == 2 ? 8 : 0)); }
@@ -516,9 +521,8 @@ struct Solver {
     // rollout takes xhat-_0 = (double)x0.  Logs: d_mpc_y takes (float)xhat_t, d_mpc_yout [batch][steps][ny] (float)y_t.
     int est_kind = 0, est_ny = 0;
     std::vector<double> est_C, est_L;
-    double *d_est_C = nullptr, *d_est_L = nullptr, *d_xhat = nullptr, *d_model = nullptr;
+    DevBuf<double> d_model;
     bool xhat_live = false;
-    float *d_mpc_yout = nullptr;
     int mpc_yout_cap = 0, mpc_yout_steps = 0;   // steps x ny floats allocated per instance / ny; steps of the loop that wrote it
     bool estimating() const { return est_kind != 0; }
     long model_stride() const { return hetero ? (long)nx * nx + (long)nx * nu + nx : 0L; }
@@ -543,7 +547,7 @@ struct Solver {
     int traj_kind = 0, traj_Lx = 0, traj_Lu = 0;   // traj_Lu 0: no u_traj
     int ref_cursor = 0, traj_dev_cursor = -1;
     std::vector<float> h_xtraj, h_utraj;
-    float *d_xtraj = nullptr, *d_utraj = nullptr;
+    DevBuf<float> d_xtraj, d_utraj;
     int set_ref_trajectory(const double *x_traj, int Lx, const double *u_traj, int Lu, int per_instance);
     int drop_ref_trajectory(bool install_window);   // install_window: the window at the cursor becomes the ordinary references
     int ensure_ref_window(hipStream_t stream, int cursor);
@@ -555,7 +559,6 @@ struct Solver {
     // A solver without them launches what it launched before.  set_precision keeps them, a re-batch drops them (free_batch).
     bool metrics_on = false;
     int metric_limits = 0;
-    double *d_metrics = nullptr, *d_metric_cfg = nullptr, *d_metric_part = nullptr;
     int set_rollout_metrics(int enable, const double *qw, const double *rw, const double *x_lo, const double *x_hi, const double *u_lo,
                             const double *u_hi);
     int reset_rollout_metrics();
@@ -564,8 +567,6 @@ struct Solver {
     int get_rollout_metrics(double *per_instance);
     int get_rollout_summary(double *summary);
     int chunk_iters = 0;  // 0: off
-    int *d_idx[2] = {nullptr, nullptr};
-    int *d_count = nullptr;
     int get_mpc_log(double *x, double *u, int *iter);
     int solve_status();
     double kernel_elapsed_ms();

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -122,44 +123,26 @@ static void narrow(const double *src, float *dst, size_t n) {
     });
 }
 
-template <class T>
-static int dev_alloc(T *&p, size_t n) {
-    if (p) {
-        (void)hipFree(p);
-        p = nullptr;
-    }
-    if (n == 0) n = 1;
-    HIP_TRY(hipMalloc((void **)&p, n * sizeof(T)));
+// every device allocation of the library (devbuf.h), and the bytes of them that are live (tmpc_device_bytes_live)
+static std::atomic<long long> g_device_bytes{0};
+int device_alloc_bytes(void **p, size_t bytes) {
+    *p = nullptr;
+    HIP_TRY(hipMalloc(p, bytes));
+    g_device_bytes += (long long)bytes;
     return 0;
 }
-template <class T>
-static void dev_free(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
+void device_free_bytes(void *p, size_t bytes) {
+    (void)hipFree(p);
+    g_device_bytes -= (long long)bytes;
 }
 
+// (the buffers go with the members that own them)
 Solver::~Solver() {
     for (const auto &r : pinned_ranges) (void)hipHostUnregister(r.first);
     pinned_ranges.clear();
     free_batch();
-    dev_free(d_coef);
-    dev_free(d_bounds);
-    dev_free(d_gstat);
-    dev_free(d_gslot);
-    dev_free(d_sens);
-    dev_free(d_lean);
-    dev_free(d_plant);
-    dev_free(d_model);
-    dev_free(d_dist);
-    dev_free(d_xtraj);
-    dev_free(d_utraj);
-    dev_free(d_noise_G[0]);
-    dev_free(d_noise_G[1]);
-    if (h_gstat) (void)hipHostFree(h_gstat);
-    h_gstat = nullptr;
     for (hipEvent_t e : ev_ring)
         if (e) (void)hipEventDestroy(e);
-    if (h_stage) (void)hipHostFree(h_stage);
     for (hipEvent_t e : ev_copy)
         if (e) (void)hipEventDestroy(e);
     if (s_copy) (void)hipStreamDestroy(s_copy);
@@ -205,56 +188,14 @@ int Solver::copy_family_state(const Solver &o) {
 }
 
 void Solver::free_batch() {
-    dev_free(d_x0);
-    dev_free(d_xref);
-    dev_free(d_uref);
-    dev_free(d_xout);
-    dev_free(d_uout);
-    dev_free(d_res);
-    dev_free(d_iter);
-    dev_free(d_solved);
-    dev_free(d_sd);
-    dev_free(d_sy);
-    dev_free(d_sz);
-    dev_free(d_sg);
-    dev_free(d_sv);
-    dev_free(d_scratch);
-    dev_free(d_ws64);
-    ws64_cap = 0;
-    dev_free(d_het_aux);
-    dev_free(d_ibx);
-    dev_free(d_ibu);
-    dev_free(d_il);
-    dev_free(d_sgc);
-    dev_free(d_svc);
-    dev_free(d_syc);
-    dev_free(d_szc);
-    dev_free(d_idx[0]);
-    dev_free(d_idx[1]);
-    dev_free(d_count);
-    dev_free(d_lin);
-    dev_free(d_sgl);
-    dev_free(d_svl);
-    dev_free(d_syl);
-    dev_free(d_szl);
-    dev_free(d_adapt);
-    dev_free(d_adp_cols);
-    adp_cols_bytes = 0;
-    dev_free(d_x0d);
+    static_cast<BatchBuffers &>(*this) = BatchBuffers{};
     x0d_live = false;
     adapt_dirty = true;
-    dev_free(d_mpc_x);
-    dev_free(d_mpc_u);
-    dev_free(d_mpc_iter);
-    dev_free(d_mpc_y);
     mpc_y_steps = 0;
-    dev_free(d_xref_seq);
-    dev_free(d_uref_seq);
     ref_seq_steps = 0;
     mpc_cap = 0;
     drop_rollout_metrics();   // (per-instance accumulators, and their configuration with them)
     drop_estimator();         // (the estimate is per instance, the matrices may be)
-    xref_cap = uref_cap = scratch_cap = 0;
 }
 
 int Solver::init(const double *A_, const double *B_, const double *Q_, const double *R_, double rho,
@@ -298,10 +239,9 @@ int Solver::init(const double *A_, const double *B_, const double *Q_, const dou
     u_max.assign((size_t)eu(), 1e17);
     batch = batch_;
     if (select_kernel()) return -1;
-    if (dev_alloc(d_gstat, (size_t)2 * GSTAT_WORDS)) return -1;
-    HIP_TRY(hipMemset(d_gstat, 0, 2 * GSTAT_WORDS * sizeof(uint32_t)));
-    if (dev_alloc(d_gslot, (size_t)GSLOT_DEFAULT_CAP * GSLOT_WORDS)) return -1;   // (written before it is read: fold_status)
-    HIP_TRY(hipHostMalloc((void **)&h_gstat, GSTAT_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+    if (d_gstat.alloc_zero((size_t)2 * GSTAT_WORDS)) return -1;
+    if (d_gslot.alloc((size_t)GSLOT_DEFAULT_CAP * GSLOT_WORDS)) return -1;   // (written before it is read: fold_status)
+    if (h_gstat.alloc(GSTAT_WORDS)) return -1;
     std::memset(h_gstat, 0, GSTAT_WORDS * sizeof(uint32_t));
     packs_dirty = true;
     return alloc_batch(batch_);
@@ -335,8 +275,7 @@ int Solver::init_families(const double *A_, const double *B_, const double *Q_, 
         for (int a = 0; a < nu; ++a) aux[(size_t)(nx + a) * Bn + b] = (float)het_cache[b].Rd[a];
         aux[(size_t)(nx + nu) * Bn + b] = (float)het_cache[b].rho;
     }
-    if (dev_alloc(d_het_aux, aux.size())) return -1;
-    HIP_TRY(hipMemcpy(d_het_aux, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (d_het_aux.upload(aux)) return -1;
     packs_dirty = true;
     return select_kernel() || ensure_extension_buffers();
 }
@@ -598,22 +537,14 @@ int Solver::alloc_batch(int batch_) {
     batch = batch_;
     if (select_kernel()) return -1;
     const size_t Bn = (size_t)batch, EX = (size_t)ex(), EU = (size_t)eu();
-    if (dev_alloc(d_x0, Bn * nx) || dev_alloc(d_xout, Bn * EX) || dev_alloc(d_uout, Bn * EU) ||
-        dev_alloc(d_res, Bn * 4) || dev_alloc(d_iter, Bn) || dev_alloc(d_solved, Bn) ||
-        dev_alloc(d_sd, Bn * EU) || dev_alloc(d_sy, Bn * EU) || dev_alloc(d_sz, Bn * EU) ||
-        dev_alloc(d_sg, Bn * EX) || dev_alloc(d_sv, Bn * EX))
+    // (the workspace and the residuals are zeroed by reset() below)
+    if (d_x0.alloc_zero(Bn * nx) || d_xout.alloc_zero(Bn * EX) || d_uout.alloc_zero(Bn * EU) ||
+        d_res.alloc(Bn * 4) || d_iter.alloc_zero(Bn) || d_solved.alloc_zero(Bn) ||
+        d_sd.alloc(Bn * EU) || d_sy.alloc(Bn * EU) || d_sz.alloc(Bn * EU) ||
+        d_sg.alloc(Bn * EX) || d_sv.alloc(Bn * EX))
         return -1;
     // shared-size reference buffers up front; per-instance ones on demand
-    if (dev_alloc(d_xref, EX) || dev_alloc(d_uref, EU)) return -1;
-    xref_cap = EX;
-    uref_cap = EU;
-    HIP_TRY(hipMemset(d_x0, 0, Bn * nx * sizeof(float)));
-    HIP_TRY(hipMemset(d_xout, 0, Bn * EX * sizeof(float)));
-    HIP_TRY(hipMemset(d_uout, 0, Bn * EU * sizeof(float)));
-    HIP_TRY(hipMemset(d_iter, 0, Bn * sizeof(int)));
-    HIP_TRY(hipMemset(d_solved, 0, Bn * sizeof(int)));
-    HIP_TRY(hipMemset(d_xref, 0, EX * sizeof(float)));
-    HIP_TRY(hipMemset(d_uref, 0, EU * sizeof(float)));
+    if (d_xref.alloc_zero(EX) || d_uref.alloc_zero(EU)) return -1;
     h_xref.clear();
     h_uref.clear();
     xref_kind = uref_kind = 0;
@@ -628,26 +559,10 @@ int Solver::alloc_batch(int batch_) {
 int Solver::reset() {
     HIP_TRY(hipSetDevice(device));
     if (wait_last_launch()) return -1;
-    const size_t Bn = (size_t)batch, EX = (size_t)ex(), EU = (size_t)eu();
-    HIP_TRY(hipMemset(d_sd, 0, Bn * EU * sizeof(float)));
-    HIP_TRY(hipMemset(d_sy, 0, Bn * EU * sizeof(float)));
-    HIP_TRY(hipMemset(d_sz, 0, Bn * EU * sizeof(float)));
-    HIP_TRY(hipMemset(d_sg, 0, Bn * EX * sizeof(float)));
-    HIP_TRY(hipMemset(d_sv, 0, Bn * EX * sizeof(float)));
-    HIP_TRY(hipMemset(d_res, 0, Bn * 4 * sizeof(float)));
-    if (d_sgc) {
-        HIP_TRY(hipMemset(d_sgc, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_svc, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_syc, 0, Bn * EU * sizeof(float)));
-        HIP_TRY(hipMemset(d_szc, 0, Bn * EU * sizeof(float)));
-    }
-    if (d_sgl) {
-        HIP_TRY(hipMemset(d_sgl, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_svl, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_syl, 0, Bn * EU * sizeof(float)));
-        HIP_TRY(hipMemset(d_szl, 0, Bn * EU * sizeof(float)));
-    }
-    if (d_ws64) HIP_TRY(hipMemset(d_ws64, 0, ws64_cap * sizeof(double)));
+    if (d_sd.zero() || d_sy.zero() || d_sz.zero() || d_sg.zero() || d_sv.zero() || d_res.zero()) return -1;
+    if (d_sgc && (d_sgc.zero() || d_svc.zero() || d_syc.zero() || d_szc.zero())) return -1;
+    if (d_sgl && (d_sgl.zero() || d_svl.zero() || d_syl.zero() || d_szl.zero())) return -1;
+    if (d_ws64 && d_ws64.zero()) return -1;
     adapt_dirty = true;  // adapted (rho, Kinf, Pinf) go back to the family's cache
     g_maybe_nonzero = false;
     return 0;
@@ -720,9 +635,7 @@ int Solver::upload_packs() {
         build_generic_coef(*this, coef);
         build_generic_bounds(*this, bnd);
     }
-    if (dev_alloc(d_coef, coef.size()) || dev_alloc(d_bounds, bnd.size())) return -1;
-    HIP_TRY(hipMemcpy(d_coef, coef.data(), coef.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_bounds, bnd.data(), bnd.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (d_coef.upload(coef) || d_bounds.upload(bnd)) return -1;
     // the lean kernel's own pack where the selected entry has one lane per instance and the shape a lean instantiation
     le = (ke && ke->G == 1 && lean_enabled) ? find_lean_kernel(nx, nu, N) : nullptr;
     // (a shape without one — cartpole at another horizon, a unit specialised at setup with four lanes per instance: where one
@@ -740,8 +653,7 @@ int Solver::upload_packs() {
         std::vector<double> lp;
         if (build_lean_pack(*this, lp, &lean_scaled_ok)) {
             if (!le && (!ke || ke->G != 1)) append_lean_bounds(*this, lp);   // (the selected entry's bound pack is not the one-lane one)
-            if (dev_alloc(d_lean, lp.size())) return -1;
-            HIP_TRY(hipMemcpy(d_lean, lp.data(), lp.size() * sizeof(double), hipMemcpyHostToDevice));
+            if (d_lean.upload(lp)) return -1;
             lean_ok = true;
             lean_knot_bounds = false;
             if (st.en_input_bound)
@@ -823,9 +735,7 @@ int Solver::set_ref_sequence(const double *x_seq, const double *u_seq, int steps
     std::vector<float> hx(EX * steps), hu(EU * steps);
     for (size_t i = 0; i < hx.size(); ++i) hx[i] = (float)x_seq[i];
     for (size_t i = 0; i < hu.size(); ++i) hu[i] = (float)u_seq[i];
-    if (dev_alloc(d_xref_seq, hx.size()) || dev_alloc(d_uref_seq, hu.size())) return -1;
-    HIP_TRY(hipMemcpy(d_xref_seq, hx.data(), hx.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_uref_seq, hu.data(), hu.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (d_xref_seq.upload(hx) || d_uref_seq.upload(hu)) return -1;
     // the solver's own references = step 0's, kept in shared mode even when they are all zero (later steps need not be)
     h_xref.assign(hx.begin(), hx.begin() + EX);
     h_uref.assign(hu.begin(), hu.begin() + EU);
@@ -843,12 +753,9 @@ int Solver::upload_refs() {
     if (wait_last_launch()) return -1;
     const int mode = xref_kind > uref_kind ? xref_kind : uref_kind;
     const size_t EX = (size_t)ex(), EU = (size_t)eu(), Bn = (size_t)batch;
-    auto put = [&](float *&dptr, size_t &cap, const std::vector<float> &h, int kind, size_t E) -> int {
+    auto put = [&](DevBuf<float> &dptr, const std::vector<float> &h, int kind, size_t E) -> int {
         const size_t need = mode == REF_PER_INSTANCE ? Bn * E : E;
-        if (cap < need) {
-            if (dev_alloc(dptr, need)) return -1;
-            cap = need;
-        }
+        if (dptr.reserve(need)) return -1;
         if (mode == REF_ZERO) return 0;
         std::vector<float> tmp;
         const float *src;
@@ -863,8 +770,8 @@ int Solver::upload_refs() {
         HIP_TRY(hipMemcpy(dptr, src, need * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     };
-    if (put(d_xref, xref_cap, h_xref, xref_kind, EX)) return -1;
-    if (put(d_uref, uref_cap, h_uref, uref_kind, EU)) return -1;
+    if (put(d_xref, h_xref, xref_kind, EX)) return -1;
+    if (put(d_uref, h_uref, uref_kind, EU)) return -1;
     ref_mode = mode;
     refs_dirty = false;
     return 0;
@@ -926,8 +833,8 @@ void Solver::drop_instance_bounds() {
     (void)wait_last_launch();
     bounds_mode = 0;
     ib_xmin.clear(), ib_xmax.clear(), ib_umin.clear(), ib_umax.clear();
-    dev_free(d_ibx);
-    dev_free(d_ibu);
+    d_ibx.free();
+    d_ibu.free();
     route_gen += 1;
     packs_dirty = true;
 }
@@ -949,7 +856,7 @@ int Solver::upload_instance_bounds() {
     ib_by_knot = bounds_mode == 2 || shared_by_knot;
     const size_t Bn = (size_t)batch, kx = ib_by_knot ? (size_t)N : 1, ku = ib_by_knot ? (size_t)(N - 1) : 1;
     const bool rep = !bounds_mode;   // every instance reads the shared arrays ([knot][row])
-    auto pack = [&](const std::vector<double> &lo, const std::vector<double> &hi, size_t rows, size_t knots, float *&dptr) -> int {
+    auto pack = [&](const std::vector<double> &lo, const std::vector<double> &hi, size_t rows, size_t knots, DevBuf<float> &dptr) -> int {
         const size_t half = knots * Bn * rows;
         std::vector<float> h(2 * half);
         for (size_t b = 0; b < Bn; ++b)
@@ -959,9 +866,7 @@ int Solver::upload_instance_bounds() {
                     h[dst] = (float)lo[src];
                     h[half + dst] = (float)hi[src];
                 }
-        if (dev_alloc(dptr, h.size())) return -1;
-        HIP_TRY(hipMemcpy(dptr, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-        return 0;
+        return dptr.upload(h);
     };
     if (rep) return pack(x_min, x_max, (size_t)nx, kx, d_ibx) || pack(u_min, u_max, (size_t)nu, ku, d_ibu);
     return pack(ib_xmin, ib_xmax, (size_t)nx, kx, d_ibx) || pack(ib_umin, ib_umax, (size_t)nu, ku, d_ibu);
@@ -1005,7 +910,7 @@ int Solver::set_instance_linear(const double *Ax, int mx, const double *bx, cons
         lin_mode = o_mode, mlx = o_mlx, mlu = o_mlu, st.en_state_linear = o_sl, st.en_input_linear = o_il;
         il_Ax.swap(o_ax), il_bx.swap(o_bx), il_Au.swap(o_au), il_bu.swap(o_bu);
         route_gen += 1;
-        dev_free(d_il);   // (re-made from the host copies at the next upload_packs where they are still per instance)
+        d_il.free();   // (re-made from the host copies at the next upload_packs where they are still per instance)
         (void)select_kernel();
         set_error(why);
         return -1;
@@ -1020,10 +925,10 @@ void Solver::drop_instance_linear() {
     mlx = mlu = 0;   // (the shared host arrays hold no rows while the per-instance ones are installed)
     il_Ax.clear(), il_bx.clear(), il_Au.clear(), il_bu.clear();
     lin_Ax.clear(), lin_bx.clear(), lin_Au.clear(), lin_bu.clear();
-    dev_free(d_il);
+    d_il.free();
     if (!bounds_mode) {
-        dev_free(d_ibx);
-        dev_free(d_ibu);
+        d_ibx.free();
+        d_ibu.free();
     }
     route_gen += 1;
     lin_dirty = true;
@@ -1054,9 +959,7 @@ int Solver::upload_instance_linear() {
     float *bx = h.data() + nax + nau, *n2x = bx + Bn * mlx, *bu = n2x + Bn * mlx, *n2u = bu + Bn * mlu;
     put(il_Ax, il_bx, (size_t)mlx, (size_t)nx, h.data(), bx, n2x);
     put(il_Au, il_bu, (size_t)mlu, (size_t)nu, h.data() + nax, bu, n2u);
-    if (dev_alloc(d_il, h.size())) return -1;
-    HIP_TRY(hipMemcpy(d_il, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return d_il.upload(h);
 }
 
 int Solver::set_fdyn(const double *f) {
@@ -1167,23 +1070,20 @@ int Solver::ensure_extension_buffers() {
             set_sensitivity(dK.a.data(), dP.a.data());
         }
         if (sens_dirty) {
-            if (dev_alloc(d_sens, nk + np)) return -1;
-            HIP_TRY(hipMemcpy(d_sens, sens.data(), (nk + np) * sizeof(double), hipMemcpyHostToDevice));
+            if (d_sens.upload(sens.data(), nk + np)) return -1;
             sens_dirty = false;
         }
-        if (!d_adapt && dev_alloc(d_adapt, (1 + nk + np) * Bn)) return -1;
+        if (!d_adapt && d_adapt.alloc((1 + nk + np) * Bn)) return -1;
         if (adapt_dirty) {
             std::vector<double> fam(1 + nk + np);
             fam[0] = cache.rho;
             std::copy(cache.Kinf.a.begin(), cache.Kinf.a.end(), fam.begin() + 1);
             std::copy(cache.Pinf.a.begin(), cache.Pinf.a.end(), fam.begin() + 1 + nk);
-            double *d_fam = nullptr;
-            if (dev_alloc(d_fam, fam.size())) return -1;
-            HIP_TRY(hipMemcpy(d_fam, fam.data(), fam.size() * sizeof(double), hipMemcpyHostToDevice));
+            DevBuf<double> d_fam;
+            if (d_fam.upload(fam)) return -1;
             const long total = (long)fam.size() * (long)Bn;
             adapt_fill_kernel<<<(unsigned)((total + 255) / 256), 256>>>(d_adapt, d_fam, (int)fam.size(), (long)Bn);
             HIP_TRY(hipDeviceSynchronize());
-            dev_free(d_fam);
             adapt_dirty = false;
             adapt_pure = true;
         }
@@ -1191,11 +1091,7 @@ int Solver::ensure_extension_buffers() {
             const size_t G = (size_t)se->lanes, rx = (nx + G - 1) / G, ru = (nu + G - 1) / G;
             const size_t len = ru * (G * rx) + rx * (G * ru) + rx * (G * rx);
             const size_t bytes = len * G * Bn * (precision == 0 ? 8 : 4);
-            if (bytes > adp_cols_bytes) {
-                dev_free(d_adp_cols);
-                if (dev_alloc(d_adp_cols, bytes)) return -1;
-                adp_cols_bytes = bytes;
-            }
+            if (d_adp_cols.reserve(bytes)) return -1;
         }
     }
     if (ke) return 0;  // (a quad kernel running an adaptive solve: the adaptive state above is all it needs)
@@ -1204,36 +1100,16 @@ int Solver::ensure_extension_buffers() {
     if (precision == 2) {   // fp64 state: the scratch arrays are doubles, and the workspace kept between solves is the fp64 block
         need *= 2;
         const size_t w = (size_t)Ws64::doubles((long)Bn, (long)EX, (long)EU, 3);
-        if (ws64_cap < w) {
-            dev_free(d_ws64);
-            if (dev_alloc(d_ws64, w)) return -1;
-            HIP_TRY(hipMemset(d_ws64, 0, w * sizeof(double)));
-            ws64_cap = w;
-        }
+        if (d_ws64.count() < w && d_ws64.alloc_zero(w)) return -1;
     }
     if (se) need = std::max(need, Bn * se->scratch_floats(N, (int)sets) * (precision == 2 ? 2 : 1));   // (fp64 state: doubles)
     if (ce) need = ce->scratch_floats(*this);
-    if (scratch_cap < need) {
-        if (dev_alloc(d_scratch, need)) return -1;
-        scratch_cap = need;
-    }
+    if (d_scratch.reserve(need)) return -1;
     if (cones_active() && !d_sgc) {
-        if (dev_alloc(d_sgc, Bn * EX) || dev_alloc(d_svc, Bn * EX) || dev_alloc(d_syc, Bn * EU) ||
-            dev_alloc(d_szc, Bn * EU))
-            return -1;
-        HIP_TRY(hipMemset(d_sgc, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_svc, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_syc, 0, Bn * EU * sizeof(float)));
-        HIP_TRY(hipMemset(d_szc, 0, Bn * EU * sizeof(float)));
+        if (d_sgc.alloc_zero(Bn * EX) || d_svc.alloc_zero(Bn * EX) || d_syc.alloc_zero(Bn * EU) || d_szc.alloc_zero(Bn * EU)) return -1;
     }
     if (lin_active() && !d_sgl) {
-        if (dev_alloc(d_sgl, Bn * EX) || dev_alloc(d_svl, Bn * EX) || dev_alloc(d_syl, Bn * EU) ||
-            dev_alloc(d_szl, Bn * EU))
-            return -1;
-        HIP_TRY(hipMemset(d_sgl, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_svl, 0, Bn * EX * sizeof(float)));
-        HIP_TRY(hipMemset(d_syl, 0, Bn * EU * sizeof(float)));
-        HIP_TRY(hipMemset(d_szl, 0, Bn * EU * sizeof(float)));
+        if (d_sgl.alloc_zero(Bn * EX) || d_svl.alloc_zero(Bn * EX) || d_syl.alloc_zero(Bn * EU) || d_szl.alloc_zero(Bn * EU)) return -1;
     }
     if (!lin_mode && (lin_dirty || (lin_active() && !d_lin))) {   // (per-instance rows: upload_instance_linear)
         // [mlx][nx] rows | b | |a|^2 | [mlu][nu] rows | b | |a|^2   (fp32)
@@ -1252,8 +1128,7 @@ int Solver::ensure_extension_buffers() {
         put(lin_Ax, lin_bx, st.en_state_linear ? mlx : 0, nx);
         put(lin_Au, lin_bu, st.en_input_linear ? mlu : 0, nu);
         if (pk.empty()) pk.push_back(0.f);
-        if (dev_alloc(d_lin, pk.size())) return -1;
-        HIP_TRY(hipMemcpy(d_lin, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (d_lin.upload(pk)) return -1;
         lin_dirty = false;
     }
     return 0;
@@ -1417,7 +1292,7 @@ int Solver::solve_chunked(hipStream_t stream) {
     const int ct = st.check_termination;
     const int chunk = std::max(ct, (chunk_iters + ct - 1) / ct * ct);
     if (!d_idx[0]) {
-        if (dev_alloc(d_idx[0], (size_t)batch) || dev_alloc(d_idx[1], (size_t)batch) || dev_alloc(d_count, 1)) return -1;
+        if (d_idx[0].alloc((size_t)batch) || d_idx[1].alloc((size_t)batch) || d_count.alloc(1)) return -1;
     }
     uint32_t acc[GSTAT_WORDS] = {0};
     const int *idx = nullptr;
@@ -1487,7 +1362,7 @@ LeanPlan Solver::plan_lean(const Pass &a) const {
 // the kernels' argument block: everything but the bound pack and the events, which depend on the kernel that runs
 void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     std::memset(&P, 0, sizeof(P));
-    P.coef = reinterpret_cast<const float *>(d_coef);
+    P.coef = reinterpret_cast<const float *>(static_cast<const unsigned char *>(d_coef));
     P.bounds = d_bounds;
     P.x0 = d_x0;
     P.x0d = a.x0d;
@@ -1590,7 +1465,7 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
 int Solver::ensure_mpc_log(int mpc_steps) {
     if (mpc_cap < mpc_steps) {
         const size_t n = (size_t)batch * mpc_steps;
-        if (dev_alloc(d_mpc_x, n * nx) || dev_alloc(d_mpc_u, n * nu) || dev_alloc(d_mpc_iter, n)) return -1;
+        if (d_mpc_x.alloc(n * nx) || d_mpc_u.alloc(n * nu) || d_mpc_iter.alloc(n)) return -1;
         mpc_cap = mpc_steps;
     }
     return 0;
@@ -1709,7 +1584,7 @@ __global__ void plant_resume_kernel(double *x0d, const float *x0, long n) {
 // the fp64 plant state a closed loop outside the selected kernel starts from.  resume: the from_x0 chains and the stream loop, which go on
 // from the state an earlier loop of theirs left (x0d_live); every other route starts from x0
 int Solver::plant_start(hipStream_t stream, bool resume) {
-    if (!d_x0d && dev_alloc(d_x0d, (size_t)batch * nx)) return -1;
+    if (!d_x0d && d_x0d.alloc((size_t)batch * nx)) return -1;
     const long n0 = (long)batch * nx;
     (resume && x0d_live ? plant_resume_kernel : plant_init_kernel)<<<(unsigned)((n0 + 255) / 256), 256, 0, stream>>>(d_x0d, d_x0, n0);
     HIP_TRY(hipGetLastError());
@@ -1739,8 +1614,7 @@ int Solver::ensure_plant() {
             for (int r = 0; r < nx; ++r) o[na + nb + r] = has_fdyn ? fdyn[r] : 0.0;
         }
     }
-    if (dev_alloc(d_plant, h.size())) return -1;
-    HIP_TRY(hipMemcpy(d_plant, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (d_plant.upload(h)) return -1;
     // ... and, for an estimator beside an installed plant, the model's image as a second one (its predict never steps the plant)
     if (estimating() && plant_kind) {
         const size_t nm = hetero ? (size_t)batch : 1;
@@ -1752,8 +1626,7 @@ int Solver::ensure_plant() {
             std::copy(Bm, Bm + nb, o + na);
             for (int r = 0; r < nx; ++r) o[na + nb + r] = has_fdyn ? fdyn[r] : 0.0;
         }
-        if (dev_alloc(d_model, h.size())) return -1;
-        HIP_TRY(hipMemcpy(d_model, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (d_model.upload(h)) return -1;
     }
     plant_dirty = false;
     return 0;
@@ -1788,13 +1661,12 @@ int Solver::set_disturbance(const double *w, int steps, int per_instance) {
     if (!w || steps <= 0) {
         dist_kind = 0, dist_steps = 0;
         dist_w.clear();
-        dev_free(d_dist);
+        d_dist.free();
         return 0;
     }
     const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)steps * nx;
     dist_w.assign(w, w + n);
-    if (dev_alloc(d_dist, n)) return -1;
-    HIP_TRY(hipMemcpy(d_dist, dist_w.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    if (d_dist.upload(dist_w)) return -1;
     dist_kind = per_instance ? 2 : 1, dist_steps = steps;
     return 0;
 }
@@ -1804,7 +1676,7 @@ void Solver::drop_own_plant() {
     (void)wait_last_launch();
     plant_kind = dist_kind = dist_steps = 0;
     own_A.clear(), own_B.clear(), own_f.clear(), dist_w.clear();
-    dev_free(d_dist);
+    d_dist.free();
     plant_dirty = true;
 }
 
@@ -1933,7 +1805,7 @@ int Solver::rollout_chain(hipStream_t stream, int mpc_steps, bool from_x0) {
     const long gw_stride = noise_kind[NOISE_PROCESS] == 2 ? (long)nx * nx : 0L, gv_stride = noise_kind[NOISE_MEASUREMENT] == 2 ? (long)nx * nx : 0L;
     if (measured) {
         if (mpc_y_cap < mpc_steps) {
-            if (dev_alloc(d_mpc_y, (size_t)batch * mpc_steps * nx)) return -1;
+            if (d_mpc_y.alloc((size_t)batch * mpc_steps * nx)) return -1;
             mpc_y_cap = mpc_steps;
         }
         mpc_y_steps = mpc_steps;
@@ -1977,17 +1849,16 @@ int Solver::set_noise(int which, const double *G, int per_instance, unsigned lon
     if (!G) {
         noise_kind[which] = 0;
         noise_G[which].clear();
-        dev_free(d_noise_G[which]);
+        d_noise_G[which].free();
         if (which == NOISE_MEASUREMENT) {
-            dev_free(d_mpc_y);
+            d_mpc_y.free();
             mpc_y_cap = mpc_y_steps = 0;
         }
         return 0;
     }
     const size_t n = (per_instance ? (size_t)batch : 1) * (size_t)nx * nx;
     noise_G[which].assign(G, G + n);
-    if (dev_alloc(d_noise_G[which], n)) return -1;
-    HIP_TRY(hipMemcpy(d_noise_G[which], noise_G[which].data(), n * sizeof(double), hipMemcpyHostToDevice));
+    if (d_noise_G[which].upload(noise_G[which])) return -1;
     noise_kind[which] = per_instance ? 2 : 1;
     noise_seed[which] = seed;
     return 0;
@@ -1999,9 +1870,9 @@ void Solver::drop_noise() {
     for (int k = 0; k < 2; ++k) {
         noise_kind[k] = 0;
         noise_G[k].clear();
-        dev_free(d_noise_G[k]);
+        d_noise_G[k].free();
     }
-    dev_free(d_mpc_y);
+    d_mpc_y.free();
     mpc_y_cap = mpc_y_steps = 0;
 }
 
@@ -2018,14 +1889,13 @@ int Solver::get_noise(int which, int t0, int steps, double *buf) {
     }
     HIP_TRY(hipSetDevice(device));
     if (wait_last_launch()) return -1;
-    double *d_out = nullptr;
+    DevBuf<double> d_out;
     const size_t n = (size_t)batch * steps * nx;
-    if (dev_alloc(d_out, n)) return -1;
+    if (d_out.alloc(n)) return -1;
     noise_fill_kernel<<<(unsigned)(groups * steps), 256>>>(d_out, d_noise_G[which], noise_kind[which] == 2 ? (long)nx * nx : 0L, noise_seed[which], which, nx,
                                                            (long)batch, steps, t0);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(buf, d_out, n * sizeof(double), hipMemcpyDeviceToHost);
-    dev_free(d_out);
     HIP_TRY(e);
     return 0;
 }
@@ -2109,23 +1979,14 @@ int Solver::set_ref_trajectory(const double *x_traj, int Lx, const double *u_tra
     std::vector<float> hx(nxf), hu(nuf);
     for (size_t i = 0; i < nxf; ++i) hx[i] = (float)x_traj[i];
     for (size_t i = 0; i < nuf; ++i) hu[i] = (float)u_traj[i];
-    if (dev_alloc(d_xtraj, nxf)) return -1;
-    HIP_TRY(hipMemcpy(d_xtraj, hx.data(), nxf * sizeof(float), hipMemcpyHostToDevice));
+    if (d_xtraj.upload(hx)) return -1;
     if (nuf) {
-        if (dev_alloc(d_utraj, nuf)) return -1;
-        HIP_TRY(hipMemcpy(d_utraj, hu.data(), nuf * sizeof(float), hipMemcpyHostToDevice));
+        if (d_utraj.upload(hu)) return -1;
     } else {
-        dev_free(d_utraj);
+        d_utraj.free();
     }
     // the reference arrays in the trajectory's mode, handed to the window kernel: the device-owned path (tinympc_set_ref_mode)
-    if (xref_cap < n * EX) {
-        if (dev_alloc(d_xref, n * EX)) return -1;
-        xref_cap = n * EX;
-    }
-    if (uref_cap < n * EU) {
-        if (dev_alloc(d_uref, n * EU)) return -1;
-        uref_cap = n * EU;
-    }
+    if (d_xref.reserve(n * EX) || d_uref.reserve(n * EU)) return -1;
     h_xtraj.swap(hx), h_utraj.swap(hu);
     traj_kind = per_instance ? 2 : 1, traj_Lx = Lx, traj_Lu = u_traj ? Lu : 0;
     ref_cursor = 0, traj_dev_cursor = -1;
@@ -2171,8 +2032,8 @@ int Solver::drop_ref_trajectory(bool install_window) {
     traj_kind = traj_Lx = traj_Lu = 0;
     traj_dev_cursor = -1;
     h_xtraj.clear(), h_utraj.clear();
-    dev_free(d_xtraj);
-    dev_free(d_utraj);
+    d_xtraj.free();
+    d_utraj.free();
     refs_device_owned = false;
     refs_dirty = true;
     return 0;
@@ -2281,12 +2142,7 @@ int Solver::d2h_double(const float *d, double *out, size_t n) {
         HIP_TRY(hipStreamCreate(&s_copy));  // callers have already waited for the last launch (wait_last_launch)
         for (hipEvent_t &e : ev_copy) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    if (stage_cap < 2 * CHUNK) {
-        if (h_stage) (void)hipHostFree(h_stage);
-        h_stage = nullptr;
-        HIP_TRY(hipHostMalloc((void **)&h_stage, 2 * CHUNK * sizeof(float), hipHostMallocDefault));
-        stage_cap = 2 * CHUNK;
-    }
+    if (h_stage.reserve(2 * CHUNK)) return -1;
     const size_t nchunks = (n + CHUNK - 1) / CHUNK;
     for (size_t c = 0; c <= nchunks; ++c) {
         if (c < nchunks) {
@@ -2405,3 +2261,7 @@ extern "C" int tmpc_lean_last_scaled(tinympc_solver *s) { return s ? (s->s.last_
 // (test hook like the one above) the number of solve-kernel launches the solver's last mpc_rollout took: `steps` for the
 // chains of launches, 1 for any in-kernel loop, -1 before any rollout
 extern "C" int tmpc_last_rollout_launches(tinympc_solver *s) { return s ? s->s.last_rollout_launches : -1; }
+
+// (test hook like the one above) the bytes of device memory the library holds in this process: every allocation goes through
+// devbuf.h's two functions above
+extern "C" long long tmpc_device_bytes_live(void) { return tmpc::g_device_bytes.load(); }
