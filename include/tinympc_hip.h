@@ -181,9 +181,21 @@ int set_rollout_metrics(int enable, double *qw_data, int qw_len, double *rw_data
 int reset_rollout_metrics(void);
 int get_rollout_metrics(double *per_instance);
 int get_rollout_summary(double *summary);
+/* One problem family PER INSTANCE on the process-global solver (tinympc_create_families / _create_families_device,
+ * tinympc_set_families, tinympc_get_family_cache, tinympc_families_setup_mode below, which describe them).  setup_families
+ * replaces the global solver as setup_solver does: A_data nx x (nx batch), B_data nx x (nu batch), Q_data nx x (nx batch),
+ * R_data nu x (nu batch) — the instances' column-major blocks side by side, the counts are checked — rho_data of batch
+ * entries; on_device: the Riccati caches by a kernel instead of the host.  set_families: the handle call's arrays, NULL
+ * keeps.  Not on a set_gpus solver. */
+int setup_families(double *A_data, int A_rows, int A_cols, double *B_data, int B_rows, int B_cols, double *Q_data, int Q_rows,
+                   int Q_cols, double *R_data, int R_rows, int R_cols, double *rho_data, int rho_len, int nx, int nu, int N,
+                   int batch, int on_device, int verbose);
+int set_families(double *A_data, double *B_data, double *Q_data, double *R_data, double *rho_data);
+int get_family_cache(int first, int count, double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps);
+int families_setup_mode(void);
 
 /* ------------------------------------------------------------------------- */
-/* (2) handle API                                                            */
+/* (2) handle API                                                           */
 /* ------------------------------------------------------------------------- */
 typedef struct tinympc_solver tinympc_solver;
 
@@ -199,6 +211,37 @@ int tinympc_create(tinympc_solver **out, const double *A, const double *B, const
 int tinympc_create_families(tinympc_solver **out, const double *A, const double *B, const double *Q,
                             const double *R, const double *rho, int nx, int nu, int N, int batch,
                             int device, int verbose);
+/* Families set up ON THE DEVICE.  tinympc_create_families_device takes what tinympc_create_families takes and
+ * makes the same solver, but every instance's Riccati cache is computed by a kernel (the rule: csrc/riccati.h — the host
+ * recursion of tinympc_host_precompute: at most 1000 sweeps, exit at max|K - K_prev| < 1e-5, LU with partial pivoting) and
+ * the stream kernel's coefficient pack is written on the device from that cache; the host keeps A, B, the diagonals of Q and
+ * R and rho, not the caches.  Fails, naming the first singular instance and their count, when R + B'PB is singular for one.
+ *
+ * tinympc_set_families replaces EVERY instance's family on an existing family solver of either setup mode: re-linearisation
+ * along a trajectory, gain scheduling, a sweep over rho.  Arrays as tinympc_create_families takes them; A and B come
+ * together, so do Q and R, and a NULL pair / a NULL rho keeps what the solver holds.  The caches are recomputed on the device
+ * and the solver is in device mode from then on.  Kept: settings, bounds (shared and per instance), linear rows, cones, the
+ * affine term, references and a reference trajectory, an installed plant, disturbance, noise, estimator and metrics, the
+ * precision, and the warm-start workspace (tinympc_reset clears it as always); the model plant and the estimator's predict
+ * follow the new A, B.  Waits for a launch in flight.  The new caches are computed into staging buffers and committed only if
+ * no instance is singular: otherwise -1, tinympc_last_error names the first singular instance and how many there are, and
+ * the solver is exactly as it was.  Refused on a solver that is not a family solver.
+ *
+ * tinympc_get_family_cache copies the caches of instances [first, first + count) in either mode: Kinf [count][nu*nx], Pinf
+ * [count][nx*nx], Quu_inv [count][nu*nu], AmBKt [count][nx*nx], each block column-major, and sweeps [count], the Riccati sweeps
+ * the instance ran (1000: it stopped at the cap); any output may be NULL.  tinympc_families_setup_mode: 0 not a family
+ * solver, 1 set up on the host, 2 on the device.  tinympc_families_setup_ms: the kernel times in ms of the last device setup
+ * (ms[0], riccati_families_kernel) and of the last pack fill (ms[1], fill_family_pack_kernel), -1 where none has run.
+ * Not built: a sharded handle for families, adaptive rho and precision 2 on families, a per-instance affine term. */
+int tinympc_create_families_device(tinympc_solver **out, const double *A, const double *B, const double *Q,
+                                   const double *R, const double *rho, int nx, int nu, int N, int batch,
+                                   int device, int verbose);
+int tinympc_set_families(tinympc_solver *s, const double *A, const double *B, const double *Q, const double *R,
+                         const double *rho);
+int tinympc_get_family_cache(tinympc_solver *s, int first, int count, double *Kinf, double *Pinf, double *Quu_inv,
+                             double *AmBKt, int *sweeps);
+int tinympc_families_setup_mode(tinympc_solver *s);
+int tinympc_families_setup_ms(tinympc_solver *s, double *ms);
 void tinympc_destroy(tinympc_solver *s);
 int tinympc_update_settings(tinympc_solver *s, double abs_pri_tol, double abs_dua_tol,
                             int max_iter, int check_termination, int en_state_bound,
@@ -631,6 +674,16 @@ int tinympc_specialise(int nx, int nu, int N, int verbose);
 int tinympc_host_precompute(const double *A, const double *B, const double *Q, const double *R,
                             double rho, int nx, int nu, double *Kinf, double *Pinf,
                             double *Quu_inv, double *AmBKt);
+/* Host-only (no GPU): the Riccati sweeps tinympc_host_precompute runs for that family (1000: it stopped at the cap), -1 if
+ * R + B'PB is singular. */
+int tinympc_host_precompute_sweeps(const double *A, const double *B, const double *Q, const double *R, double rho, int nx,
+                                   int nu);
+/* Host-only (no GPU): the same precompute by the rule the device setup of per-instance families runs (csrc/riccati.h), for the
+ * shapes that setup is built for (nx in {2,3,4,6,8,10,12}, nu <= 4).  Q, R full matrices (their diagonals are what enters);
+ * *sweeps (may be NULL): the sweeps run, 1000 at the cap.  Returns 0, or -1: R + B'PB singular (*sweeps = -1) or the shape is
+ * outside the grid.  On finite values it agrees with tinympc_host_precompute to the last bit. */
+int tinympc_host_family_cache(const double *A, const double *B, const double *Q, const double *R, double rho, int nx, int nu,
+                              double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps);
 /* Host-only (no GPU): the sensitivities tinympc_compute_sensitivity returns, for a family given directly. */
 int tinympc_host_sensitivity(const double *A, const double *B, const double *Q, const double *R, double rho, int nx,
                              int nu, double *dKinf, double *dPinf, double *dC1, double *dC2);

@@ -95,6 +95,8 @@ from .tinympc import (  # noqa: E402,F401
     get_solution,
     get_status,
     host_precompute,
+    host_family_cache,
+    host_precompute_sweeps,
     host_sensitivity,
     load_library,
     print_problem_data,

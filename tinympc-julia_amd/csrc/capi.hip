@@ -150,6 +150,41 @@ int tinympc_create_families(tinympc_solver **out, const double *A, const double 
     });
 }
 
+int tinympc_create_families_device(tinympc_solver **out, const double *A, const double *B, const double *Q,
+                                   const double *R, const double *rho, int nx, int nu, int N, int batch, int device,
+                                   int verbose) {
+    return guarded("tinympc_create_families_device", [&]() -> int {
+        if (!out || !A || !B || !Q || !R || !rho) {
+            set_error("tinympc_create_families_device: null argument");
+            return -1;
+        }
+        std::unique_ptr<tinympc_solver> s(new tinympc_solver());
+        if (s->s.init_families(A, B, Q, R, rho, nx, nu, N, batch, device, verbose, true)) return -1;
+        *out = s.release();
+        return 0;
+    });
+}
+
+int tinympc_set_families(tinympc_solver *s, const double *A, const double *B, const double *Q, const double *R,
+                         const double *rho) {
+    if (!s) return -1;
+    return guarded("set_families", [&] { return s->s.set_families(A, B, Q, R, rho); });
+}
+
+int tinympc_get_family_cache(tinympc_solver *s, int first, int count, double *Kinf, double *Pinf, double *Quu_inv,
+                             double *AmBKt, int *sweeps) {
+    if (!s) return -1;
+    return guarded("get_family_cache", [&] { return s->s.get_family_cache(first, count, Kinf, Pinf, Quu_inv, AmBKt, sweeps); });
+}
+
+int tinympc_families_setup_mode(tinympc_solver *s) { return s ? s->s.fam_mode : 0; }
+
+int tinympc_families_setup_ms(tinympc_solver *s, double *ms) {
+    if (!s || !ms) return -1;
+    ms[0] = s->s.fam_ms[0], ms[1] = s->s.fam_ms[1];
+    return 0;
+}
+
 void tinympc_destroy(tinympc_solver *s) { delete s; }
 
 int tinympc_update_settings(tinympc_solver *s, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -803,6 +838,42 @@ int tinympc_host_precompute(const double *A, const double *B, const double *Q, c
     });
 }
 
+int tinympc_host_precompute_sweeps(const double *A, const double *B, const double *Q, const double *R, double rho, int nx, int nu) {
+    int sweeps = -1;
+    (void)guarded("host_precompute_sweeps", [&]() -> int {
+        if (!A || !B || !Q || !R || nx < 1 || nu < 1) return -1;
+        tmpc::Cache c;
+        if (tmpc::precompute_cache(tmpc::Mat(nx, nx, A), tmpc::Mat(nx, nu, B), tmpc::Mat(nx, nx, Q), tmpc::Mat(nu, nu, R), rho, c)) {
+            set_error("Riccati precompute failed: R + B'PB is singular");
+            return -1;
+        }
+        sweeps = c.riccati_iters;
+        return 0;
+    });
+    return sweeps;
+}
+
+int tinympc_host_family_cache(const double *A, const double *B, const double *Q, const double *R, double rho, int nx, int nu,
+                              double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps) {
+    return guarded("host_family_cache", [&]() -> int {
+        if (!A || !B || !Q || !R || nx < 1 || nu < 1) return -1;
+        std::vector<double> qd((size_t)nx), rd((size_t)nu), K((size_t)nu * nx), P((size_t)nx * nx), Qi((size_t)nu * nu), At((size_t)nx * nx);
+        for (int i = 0; i < nx; ++i) qd[i] = Q[i + (size_t)i * nx];
+        for (int a = 0; a < nu; ++a) rd[a] = R[a + (size_t)a * nu];
+        const int st = tmpc::families_host_cache(nx, nu, A, B, qd.data(), rd.data(), rho, K.data(), P.data(), Qi.data(), At.data(), sweeps);
+        if (st) {
+            set_error(st == 1 ? "Riccati precompute failed: R + B'PB is singular"
+                              : "host_family_cache: the rule is built for nx in {2,3,4,6,8,10,12}, nu <= 4");
+            return -1;
+        }
+        if (Kinf) std::copy(K.begin(), K.end(), Kinf);
+        if (Pinf) std::copy(P.begin(), P.end(), Pinf);
+        if (Quu_inv) std::copy(Qi.begin(), Qi.end(), Quu_inv);
+        if (AmBKt) std::copy(At.begin(), At.end(), AmBKt);
+        return 0;
+    });
+}
+
 int tinympc_host_sensitivity(const double *A, const double *B, const double *Q, const double *R, double rho, int nx,
                              int nu, double *dKinf, double *dPinf, double *dC1, double *dC2) {
     return guarded("host_sensitivity", [&]() -> int {
@@ -1284,6 +1355,37 @@ int set_estimator(double *C_data, int C_rows, int C_cols, double *L_data, int L_
     }
     return tinympc_set_estimator(g_solver.get(), C_data, C_rows, L_data, per_instance);
 }
+// One family per instance on the global solver (julia/TinyMPC.jl: setup_families, set_families!, family_cache): the handle
+// entry points behind the process-global one.  A (nx, nx batch), B (nx, nu batch), Q (nx, nx batch), R (nu, nu batch): the
+// handle API's [batch] blocks seen as one column-major matrix; rho [batch].
+int setup_families(double *A_data, int A_rows, int A_cols, double *B_data, int B_rows, int B_cols, double *Q_data, int Q_rows, int Q_cols,
+                   double *R_data, int R_rows, int R_cols, double *rho_data, int rho_len, int nx, int nu, int N, int batch, int on_device,
+                   int verbose) {
+    return guarded("setup_families", [&]() -> int {
+        if (!A_data || !B_data || !Q_data || !R_data || !rho_data || batch < 1 || A_rows != nx || (long)A_cols != (long)nx * batch || B_rows != nx ||
+            (long)B_cols != (long)nu * batch || Q_rows != nx || (long)Q_cols != (long)nx * batch || R_rows != nu || (long)R_cols != (long)nu * batch ||
+            rho_len != batch) {
+            set_error("setup_families: expected A (nx, nx batch), B (nx, nu batch), Q (nx, nx batch), R (nu, nu batch) and rho of batch entries");
+            return -1;
+        }
+        g_sharded.reset();
+        tinympc_solver *s = nullptr;
+        if ((on_device ? tinympc_create_families_device : tinympc_create_families)(&s, A_data, B_data, Q_data, R_data, rho_data, nx, nu, N, batch, -1,
+                                                                                verbose)) {
+            g_solver.reset();
+            return -1;
+        }
+        g_solver.reset(s);   // (a second setup replaces the first, as setup_solver's does)
+        return 0;
+    });
+}
+int set_families(double *A_data, double *B_data, double *Q_data, double *R_data, double *rho_data) {
+    return need_unsharded("set_families") ? -1 : tinympc_set_families(g_solver.get(), A_data, B_data, Q_data, R_data, rho_data);
+}
+int get_family_cache(int first, int count, double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps) {
+    return need_unsharded("get_family_cache") ? -1 : tinympc_get_family_cache(g_solver.get(), first, count, Kinf, Pinf, Quu_inv, AmBKt, sweeps);
+}
+int families_setup_mode(void) { return need_unsharded("families_setup_mode") ? -1 : tinympc_families_setup_mode(g_solver.get()); }
 int set_estimator_state(double *xhat_data, int xhat_rows, int xhat_cols) {
     if (need_unsharded("set_estimator_state")) return -1;
     const tmpc::Solver &v = g_solver->s;

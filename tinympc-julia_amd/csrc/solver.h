@@ -164,6 +164,23 @@ struct StreamEntry {
     size_t (*il_lds_bytes)(int mlx, int mlu) = nullptr;
 };
 const StreamEntry *find_stream_kernel(int nx, int nu);
+// Per-instance families set up on the device (families_setup.hip; the rule: riccati.h).  The inputs are device pointers: A
+// [batch][nx*nx] and B [batch][nx*nu] column-major as the caller gave them, the diagonals of Q and R [batch][nx] / [batch][nu]
+// (rho not added) and rho [batch].
+struct FamilyInputs {
+    const double *A, *B, *Qdiag, *Rdiag, *rho;
+};
+bool families_shape_built(int nx, int nu);             // the stream kernel's grid: nx in {2,3,4,6,8,10,12}, nu <= 4
+int families_cache_elems(int nx, int nu);              // doubles of one instance's cache image
+size_t families_pack_elems(int nx, int nu, int lanes); // elements per column of the stream kernel's pack (0: not built for that)
+// every instance's cache into img [element][batch], its sweep count (-1: singular) into sweeps [batch]
+hipError_t families_riccati_launch(int nx, int nu, const FamilyInputs &in, int batch, double *img, int *sweeps, hipStream_t stream);
+// the stream kernel's per-instance pack (fp64 rows, precision 1: fp32) into coef and [Qd | Rd | rho] into aux; fdyn: host, nx
+hipError_t families_fill_launch(int nx, int nu, const double *img, const FamilyInputs &in, const double *fdyn, int batch, int precision,
+                                void *coef, float *aux, hipStream_t stream);
+// the rule on the host for one family: 0, 1 singular, -2 a shape outside the grid
+int families_host_cache(int nx, int nu, const double *A, const double *B, const double *Qdiag, const double *Rdiag, double rho, double *Kinf,
+                        double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps);
 // One (nx, nu) instantiation of the LDS-resident matrix-core kernel with a run-time horizon (admm_mfmac.hip.h):
 // one-shot solves with box bounds, the affine term and cones.
 struct ConeEntry {
@@ -312,6 +329,24 @@ struct Solver : BatchBuffers {
     bool layout_final = false;    // a constraint layout is specialised (jit_trans_for) from the first solve on, not while the setters run
     std::vector<double> het_A, het_B;
     std::vector<Cache> het_cache;
+    // Where the families were set up.  Host (tinympc_create_families): het_cache holds every instance's cache
+    // and upload_packs builds the coefficient pack from it on the host.  Device (tinympc_create_families_device,
+    // tinympc_set_families): het_cache is EMPTY; the caches are the fp64 image d_het_cache [element][batch] (riccati.h:
+    // Riccati<NX,NU>::E_*) written by riccati_families_kernel, d_het_sweeps [batch] its sweep counts, d_fam_* the inputs it read
+    // (A, B as given, the diagonals of Q and R, rho), and upload_packs has fill_family_pack_kernel write d_coef and d_het_aux
+    // from them (families_setup.hip).  In both modes the host keeps A and B (the plant image and the estimator's predict read
+    // them), the diagonals of Q and R as given and rho (what a partial set_families keeps).
+    enum { FAM_NONE = 0, FAM_HOST = 1, FAM_DEVICE = 2 };
+    int fam_mode = FAM_NONE;
+    std::vector<double> het_Qdiag, het_Rdiag, het_rho;   // [batch][nx], [batch][nu], [batch]
+    DevBuf<double> d_het_cache, d_fam_A, d_fam_B, d_fam_Qdiag, d_fam_Rdiag, d_fam_rho;
+    DevBuf<int> d_het_sweeps;
+    float fam_ms[2] = {-1.f, -1.f};   // kernel times of the last device setup and the last device pack fill (-1: none has run)
+    // replaces every instance's family (null pairs / rho: kept) by a device setup; commits only if no instance is singular
+    int set_families(const double *A_, const double *B_, const double *Q_, const double *R_, const double *rho_);
+    int get_family_cache(int first, int count, double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps);
+    int fill_family_pack();   // device mode's part of upload_packs
+    void family_diagonals(const double *Q_, const double *R_, const double *rho_);   // het_Qdiag / het_Rdiag / het_rho from what is given
     // references as last set by the host API: kind 0 zero / 1 shared / 2 per instance
     std::vector<float> h_xref, h_uref;
     int xref_kind = 0, uref_kind = 0;
@@ -376,7 +411,7 @@ struct Solver : BatchBuffers {
     int init(const double *A_, const double *B_, const double *Q_, const double *R_, double rho,
              int nx_, int nu_, int N_, int batch_, int device_, int verbose_);
     int init_families(const double *A_, const double *B_, const double *Q_, const double *R_, const double *rho_,
-                      int nx_, int nu_, int N_, int batch_, int device_, int verbose_);
+                      int nx_, int nu_, int N_, int batch_, int device_, int verbose_, bool on_device = false);
     int alloc_batch(int batch_);
     // family-level state of another solver of the SAME family (settings, bounds, affine term, cones, linear rows, cache,
     // sensitivities, precision / warm-start / compaction switches): what set_gpus() replays onto fresh shards

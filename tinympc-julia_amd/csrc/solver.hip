@@ -2,6 +2,7 @@
 #include "solver.h"
 #include "admm_generic.hip.h"   // Ws64 (layout of the precision-2 workspace)
 #include "noise.h"              // the draw rule of the closed loop's noise (host and device)
+#include "riccati.h"            // the Riccati rule's constants (families set up on the device: families_setup.hip)
 
 #include <cfloat>
 #include <climits>
@@ -250,13 +251,19 @@ int Solver::init(const double *A_, const double *B_, const double *Q_, const dou
 // One family per instance: B independent (A, B, Q, R, rho) sets, each with its own Riccati cache computed on
 // the host in fp64 (threaded); bounds, settings and references behave as in the single-family solver.
 int Solver::init_families(const double *A_, const double *B_, const double *Q_, const double *R_, const double *rho_,
-                          int nx_, int nu_, int N_, int batch_, int device_, int verbose_) {
+                          int nx_, int nu_, int N_, int batch_, int device_, int verbose_, bool on_device) {
     no_specialise = true;   // (a per-instance-family solver runs on the stream kernel: nothing to specialise at setup)
     if (init(A_, B_, Q_, R_, rho_[0], nx_, nu_, N_, batch_, device_, verbose_)) return -1;
     hetero = true, plant_dirty = true;   // (the plant image holds every instance's A_b, B_b)
     const size_t Bn = (size_t)batch, nxx = (size_t)nx * nx, nxu = (size_t)nx * nu, nuu = (size_t)nu * nu;
+    if (on_device) {   // every instance's cache by riccati_families_kernel: the setter's path on a solver that has no family yet
+        if (select_kernel() || set_families(A_, B_, Q_, R_, rho_)) return -1;
+        return ensure_extension_buffers();
+    }
     het_A.assign(A_, A_ + Bn * nxx);
     het_B.assign(B_, B_ + Bn * nxu);
+    family_diagonals(Q_, R_, rho_);
+    fam_mode = FAM_HOST;
     het_cache.assign(Bn, Cache());
     std::vector<int> bad(1, 0);
     parallel_chunks(Bn, [&](size_t lo, size_t hi) {
@@ -278,6 +285,181 @@ int Solver::init_families(const double *A_, const double *B_, const double *Q_, 
     if (d_het_aux.upload(aux)) return -1;
     packs_dirty = true;
     return select_kernel() || ensure_extension_buffers();
+}
+
+void Solver::family_diagonals(const double *Q_, const double *R_, const double *rho_) {
+    const size_t Bn = (size_t)batch, nxx = (size_t)nx * nx, nuu = (size_t)nu * nu;
+    if (Q_) {
+        het_Qdiag.resize(Bn * nx);
+        for (size_t b = 0; b < Bn; ++b)
+            for (int i = 0; i < nx; ++i) het_Qdiag[b * nx + i] = Q_[b * nxx + (size_t)i * nx + i];
+    }
+    if (R_) {
+        het_Rdiag.resize(Bn * nu);
+        for (size_t b = 0; b < Bn; ++b)
+            for (int a = 0; a < nu; ++a) het_Rdiag[b * nu + a] = R_[b * nuu + (size_t)a * nu + a];
+    }
+    if (rho_) het_rho.assign(rho_, rho_ + Bn);
+}
+
+// Every instance's family replaced on a live solver (tinympc_set_families), and the device route of creation: the inputs —
+// the caller's, or for a null pair the ones the solver holds — go to staging buffers, riccati_families_kernel writes a staging
+// image, and only an image without a singular instance is committed.  A refusal leaves the solver exactly as it was.
+int Solver::set_families(const double *A_, const double *B_, const double *Q_, const double *R_, const double *rho_) {
+    if (!hetero) {
+        set_error("set_families: not a per-instance-family solver (tinympc_create_families and tinympc_create_families_device make one)");
+        return -1;
+    }
+    if ((A_ == nullptr) != (B_ == nullptr) || (Q_ == nullptr) != (R_ == nullptr)) {
+        set_error("set_families: A and B come together, and so do Q and R (NULL for both keeps them)");
+        return -1;
+    }
+    if (!families_shape_built(nx, nu)) {
+        set_error("set_families: the device setup is built for the stream kernel's grid (nx in {2,3,4,6,8,10,12}, nu <= 4)");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (wait_last_launch()) return -1;   // (a launch still in flight reads the pack the next upload_packs overwrites)
+    const size_t Bn = (size_t)batch, nxx = (size_t)nx * nx, nxu = (size_t)nx * nu;
+    // the diagonals and rho as they will be: the caller's, else the solver's
+    std::vector<double> keepQ, keepR, keepRho;
+    if (Q_) keepQ.swap(het_Qdiag), keepR.swap(het_Rdiag);
+    if (rho_) keepRho.swap(het_rho);
+    family_diagonals(Q_, R_, rho_);
+    auto restore = [&] {
+        if (Q_) het_Qdiag.swap(keepQ), het_Rdiag.swap(keepR);
+        if (rho_) het_rho.swap(keepRho);
+    };
+    // staging: what was given (or is not on the device yet) is uploaded, what is kept and already there is read in place
+    DevBuf<double> sA, sB, sQ, sR, sRho, sImg;
+    DevBuf<int> sSw;
+    const bool upA = A_ || !d_fam_A, upQ = Q_ || !d_fam_Qdiag, upRho = rho_ || !d_fam_rho;
+    if ((upA && (sA.upload(A_ ? A_ : het_A.data(), Bn * nxx) || sB.upload(B_ ? B_ : het_B.data(), Bn * nxu))) ||
+        (upQ && (sQ.upload(het_Qdiag) || sR.upload(het_Rdiag))) || (upRho && sRho.upload(het_rho)) ||
+        sImg.alloc((size_t)families_cache_elems(nx, nu) * Bn) || sSw.alloc(Bn)) {
+        restore();
+        return -1;
+    }
+    const FamilyInputs in = {upA ? sA : d_fam_A, upA ? sB : d_fam_B, upQ ? sQ : d_fam_Qdiag, upQ ? sR : d_fam_Rdiag, upRho ? sRho : d_fam_rho};
+    std::vector<int> sweeps(Bn);
+    float ms = -1.f;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool launched = hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
+                          hip_ok(hipEventRecord(e0, nullptr), "hipEventRecord") &&
+                          hip_ok(families_riccati_launch(nx, nu, in, batch, sImg, sSw, nullptr), "riccati_families_kernel") &&
+                          hip_ok(hipEventRecord(e1, nullptr), "hipEventRecord") &&
+                          hip_ok(hipMemcpy(sweeps.data(), sSw, Bn * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy (sweeps)") &&
+                          hip_ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (!launched) {
+        restore();
+        return -1;
+    }
+    long bad = 0, first = -1;
+    for (size_t b = 0; b < Bn; ++b)
+        if (sweeps[b] < 0) {
+            if (first < 0) first = (long)b;
+            ++bad;
+        }
+    if (bad) {
+        restore();
+        set_error("set_families: R + B'PB is singular for instance " + std::to_string(first) + " (" + std::to_string(bad) + " of " +
+                  std::to_string(batch) + " instances singular); the solver keeps the families it had");
+        return -1;
+    }
+    // commit
+    if (A_) {
+        het_A.assign(A_, A_ + Bn * nxx);
+        het_B.assign(B_, B_ + Bn * nxu);
+        A = Mat(nx, nx, A_), B = Mat(nx, nu, B_);   // (instance 0's, as creation leaves them; no kernel of a family solver reads them)
+    }
+    if (Q_) Q = Mat(nx, nx, Q_), R = Mat(nu, nu, R_);
+    cache.rho = het_rho[0];
+    for (int i = 0; i < nx; ++i) cache.Qd[i] = het_Qdiag[i] + het_rho[0];
+    for (int a = 0; a < nu; ++a) cache.Rd[a] = het_Rdiag[a] + het_rho[0];
+    if (upA) d_fam_A = std::move(sA), d_fam_B = std::move(sB);
+    if (upQ) d_fam_Qdiag = std::move(sQ), d_fam_Rdiag = std::move(sR);
+    if (upRho) d_fam_rho = std::move(sRho);
+    d_het_cache = std::move(sImg);
+    d_het_sweeps = std::move(sSw);
+    std::vector<Cache>().swap(het_cache);
+    fam_mode = FAM_DEVICE;
+    fam_ms[0] = ms;
+    packs_dirty = true;
+    plant_dirty = true;   // (the plant image and the estimator's model hold every instance's A_b, B_b)
+    if (verbose) {
+        long cap = 0;
+        for (size_t b = 0; b < Bn; ++b) cap += sweeps[b] >= RICCATI_MAX_SWEEPS;
+        std::printf("tinympc_hip: %d families set up on the device in %.3f ms (%ld at the %d-sweep cap)\n", batch, ms, cap, RICCATI_MAX_SWEEPS);
+    }
+    return 0;
+}
+
+// device mode's part of upload_packs: the stream kernel's per-instance pack and het_aux written on the device
+int Solver::fill_family_pack() {
+    const size_t cols = (size_t)(se ? se->lanes : 0) * batch, cp = se ? families_pack_elems(nx, nu, se->lanes) : 0;
+    if (!cp || !d_het_cache) {
+        set_error("per-instance families set up on the device need the stream kernel's four-lane instantiation of (nx, nu)");
+        return -1;
+    }
+    if (d_coef.alloc(cp * cols * (precision == 1 ? sizeof(float) : sizeof(double))) || d_het_aux.reserve((size_t)(nx + nu + 1) * batch)) return -1;
+    const FamilyInputs in = {d_fam_A, d_fam_B, d_fam_Qdiag, d_fam_Rdiag, d_fam_rho};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = -1.f;
+    const bool ok = hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate") &&
+                    hip_ok(hipEventRecord(e0, nullptr), "hipEventRecord") &&
+                    hip_ok(families_fill_launch(nx, nu, d_het_cache, in, fdyn.data(), batch, precision, d_coef, d_het_aux, nullptr),
+                           "fill_family_pack_kernel") &&
+                    hip_ok(hipEventRecord(e1, nullptr), "hipEventRecord") &&
+                    hip_ok(hipEventSynchronize(e1), "hipEventSynchronize") &&   // (the next launch may go to any stream)
+                    hip_ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    fam_ms[1] = ms;
+    return ok ? 0 : -1;
+}
+
+// every block column-major, instance after instance; any output may be null
+int Solver::get_family_cache(int first, int count, double *Kinf, double *Pinf, double *Quu_inv, double *AmBKt, int *sweeps) {
+    if (!hetero) {
+        set_error("get_family_cache: not a per-instance-family solver");
+        return -1;
+    }
+    if (first < 0 || count < 0 || (long)first + count > batch) {
+        set_error("get_family_cache: the range [first, first + count) leaves the batch");
+        return -1;
+    }
+    const size_t n = (size_t)count, sz[4] = {(size_t)nu * nx, (size_t)nx * nx, (size_t)nu * nu, (size_t)nx * nx};
+    double *out[4] = {Kinf, Pinf, Quu_inv, AmBKt};
+    if (fam_mode != FAM_DEVICE) {
+        for (size_t i = 0; i < n; ++i) {
+            const Cache &c = het_cache[first + i];
+            const Mat *m[4] = {&c.Kinf, &c.Pinf, &c.Quu_inv, &c.AmBKt};
+            for (int k = 0; k < 4; ++k)
+                if (out[k]) std::copy(m[k]->a.begin(), m[k]->a.end(), out[k] + i * sz[k]);
+            if (sweeps) sweeps[i] = c.riccati_iters;
+        }
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(device));
+    if (!n) return 0;
+    const size_t elems = (size_t)families_cache_elems(nx, nu);
+    std::vector<double> h;   // [element][count]
+    if (Kinf || Pinf || Quu_inv || AmBKt) {   // (the sweep counts alone: nothing of the image travels)
+        h.resize(elems * n);
+        HIP_TRY(hipMemcpy2D(h.data(), n * sizeof(double), (const double *)d_het_cache + first, (size_t)batch * sizeof(double), n * sizeof(double),
+                            elems, hipMemcpyDeviceToHost));
+    }
+    size_t e0 = 0;
+    for (int k = 0; k < 4; ++k) {   // (the image's blocks in the order K, P, Quu_inv, AmBKt: Riccati<NX,NU>::E_*)
+        if (out[k])
+            for (size_t i = 0; i < n; ++i)
+                for (size_t e = 0; e < sz[k]; ++e) out[k][i * sz[k] + e] = h[(e0 + e) * n + i];
+        e0 += sz[k];
+    }
+    if (sweeps) HIP_TRY(hipMemcpy(sweeps, (const int *)d_het_sweeps + first, n * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- kernel routing ------------------------------------------------------------------------------------------------------
@@ -629,13 +811,15 @@ int Solver::upload_packs() {
         ce->build_coef(*this, coef);
         ce->build_bounds(*this, bnd);
     } else if (se) {
-        se->build_coef(*this, coef);
+        if (fam_mode != FAM_DEVICE) se->build_coef(*this, coef);
         se->build_bounds(*this, bnd);
     } else {
         build_generic_coef(*this, coef);
         build_generic_bounds(*this, bnd);
     }
-    if (d_coef.upload(coef) || d_bounds.upload(bnd)) return -1;
+    if (fam_mode == FAM_DEVICE) {   // (select_kernel leaves a family solver on the stream kernel or refuses)
+        if (fill_family_pack() || d_bounds.upload(bnd)) return -1;
+    } else if (d_coef.upload(coef) || d_bounds.upload(bnd)) return -1;
     // the lean kernel's own pack where the selected entry has one lane per instance and the shape a lean instantiation
     le = (ke && ke->G == 1 && lean_enabled) ? find_lean_kernel(nx, nu, N) : nullptr;
     // (a shape without one — cartpole at another horizon, a unit specialised at setup with four lanes per instance: where one

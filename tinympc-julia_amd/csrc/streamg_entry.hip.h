@@ -8,11 +8,11 @@
 
 namespace tmpc {
 
-// One family's rows for the G lane roles; put(q, idx, value) stores element idx of role q's pack.
-// A, B column-major (nx x nx, nx x nu) as the reference passes them (bindings.cpp:24-31).
-template <int NX, int NU, int G, class Put>
-void fill_streamg_family(const double *A, const double *Bm, const Cache &c, const std::vector<double> &fdyn,
-                         Put put) {
+// One family's rows for lane role q; put(q, idx, value) stores element idx of role q's pack.
+// A, B column-major (nx x nx, nx x nu) as the reference passes them (bindings.cpp:24-31); c: the family's cache, a Cache on the
+// host or a view of the device image (families_setup.hip) — THE element map of the per-instance pack, for both.
+template <int NX, int NU, int G, class CacheT, class Put>
+__host__ __device__ void fill_streamg_role(int q, const double *A, const double *Bm, const CacheT &c, const double *fdyn, Put put) {
     using PK = StreamPackG<NX, NU, G>;
     using S = typename PK::S;
     constexpr int RX = S::RX, RU = S::RU, NXP = S::NXP, NUP = S::NUP;
@@ -21,38 +21,43 @@ void fill_streamg_family(const double *A, const double *Bm, const Cache &c, cons
         Pf[i] = 0.0;
         for (int l = 0; l < NX; ++l) Pf[i] += c.Pinf(i, l) * fdyn[l];
     }
-    for (int q = 0; q < G; ++q) {
-        for (int m = 0; m < RX; ++m) {
-            const int row = q * RX + m;
-            if (row >= NX) continue;
-            double apf = 0.0;
-            for (int j = 0; j < NX; ++j) {
-                put(q, S::O_A + m * NXP + j, A[row + (size_t)j * NX]);
-                put(q, S::O_AT + m * NXP + j, c.AmBKt(row, j));
-                put(q, S::O_PT + m * NXP + j, c.Pinf(j, row));
-                put(q, PK::O_ATT + m * NXP + j, A[j + (size_t)row * NX]);   // A^T (adaptive rho: A' g)
-                apf += c.AmBKt(row, j) * Pf[j];
-            }
-            for (int a = 0; a < NU; ++a) {
-                put(q, S::O_B + m * NUP + a, Bm[row + (size_t)a * NX]);
-                put(q, S::O_KT + m * NUP + a, c.Kinf(a, row));
-            }
-            put(q, PK::O_F + m, fdyn[row]);
-            put(q, PK::O_APF + m, apf);
+    for (int m = 0; m < RX; ++m) {
+        const int row = q * RX + m;
+        if (row >= NX) continue;
+        double apf = 0.0;
+        for (int j = 0; j < NX; ++j) {
+            put(q, S::O_A + m * NXP + j, A[row + (size_t)j * NX]);
+            put(q, S::O_AT + m * NXP + j, c.AmBKt(row, j));
+            put(q, S::O_PT + m * NXP + j, c.Pinf(j, row));
+            put(q, PK::O_ATT + m * NXP + j, A[j + (size_t)row * NX]);   // A^T (adaptive rho: A' g)
+            apf += c.AmBKt(row, j) * Pf[j];
         }
-        for (int m = 0; m < RU; ++m) {
-            const int row = q * RU + m;  // no replication of a single input: lanes without a row carry zeros
-            if (row >= NU) continue;
-            double bpf = 0.0;
-            for (int j = 0; j < NX; ++j) {
-                put(q, S::O_K + m * NXP + j, c.Kinf(row, j));
-                put(q, S::O_BT + m * NXP + j, Bm[j + (size_t)row * NX]);
-                bpf += Bm[j + (size_t)row * NX] * Pf[j];
-            }
-            for (int a = 0; a < NU; ++a) put(q, S::O_QI + m * NUP + a, c.Quu_inv(row, a));
-            put(q, PK::O_BPF + m, bpf);
+        for (int a = 0; a < NU; ++a) {
+            put(q, S::O_B + m * NUP + a, Bm[row + (size_t)a * NX]);
+            put(q, S::O_KT + m * NUP + a, c.Kinf(a, row));
         }
+        put(q, PK::O_F + m, fdyn[row]);
+        put(q, PK::O_APF + m, apf);
     }
+    for (int m = 0; m < RU; ++m) {
+        const int row = q * RU + m;  // no replication of a single input: lanes without a row carry zeros
+        if (row >= NU) continue;
+        double bpf = 0.0;
+        for (int j = 0; j < NX; ++j) {
+            put(q, S::O_K + m * NXP + j, c.Kinf(row, j));
+            put(q, S::O_BT + m * NXP + j, Bm[j + (size_t)row * NX]);
+            bpf += Bm[j + (size_t)row * NX] * Pf[j];
+        }
+        for (int a = 0; a < NU; ++a) put(q, S::O_QI + m * NUP + a, c.Quu_inv(row, a));
+        put(q, PK::O_BPF + m, bpf);
+    }
+}
+
+// ... and for the G lane roles
+template <int NX, int NU, int G, class Put>
+void fill_streamg_family(const double *A, const double *Bm, const Cache &c, const std::vector<double> &fdyn,
+                         Put put) {
+    for (int q = 0; q < G; ++q) fill_streamg_role<NX, NU, G>(q, A, Bm, c, fdyn.data(), put);
 }
 
 template <int NX, int NU, int G, class RT>

@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds, set_instance_linear,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds, set_instance_linear, setup_families, set_families!, family_cache, families_setup_mode,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -94,6 +94,82 @@ function set_batch_size(solver::TinyMPCSolver, batch::Int)
     _ok(ccall((:set_batch_size, _lib_path()), Int32, (Int32,), batch), "Failed to set batch size")
     solver.batch = batch
     return 0
+end
+
+# One problem family PER INSTANCE: a parameter sweep, a fleet of unlike vehicles, a Monte-Carlo run over model error.  A (nx, nx,
+# batch), B (nx, nu, batch), Q (nx, nx, batch), R (nu, nu, batch), rho (batch,); every instance gets its own Riccati cache — computed
+# on the host, or with on_device=true by a kernel (the same recursion; the route for large batches).  Replaces setup(): settings are
+# pushed with every en_* flag false, bounds, references and the closed loop behave as on a single-family solver.  Needs (nx, nu)
+# in the stream kernel's grid (nx in {2,3,4,6,8,10,12}, nu <= 4); the batch is fixed.  solver.A / B / Q / R hold instance 1's.
+# (Written against the C-ABI like the rest of this file, not executed here.)
+function setup_families(solver::TinyMPCSolver, A::Array{Float64,3}, B::Array{Float64,3}, Q::Array{Float64,3}, R::Array{Float64,3},
+                        rho::Vector{Float64}, N::Int; on_device::Bool=false, verbose::Bool=false, abs_pri_tol::Float64=1e-3,
+                        abs_dua_tol::Float64=1e-3, max_iter::Int=100, check_termination::Bool=true)
+    _ensure_loaded()
+    nx, nu, batch = size(A, 1), size(B, 2), size(A, 3)
+    Am, Bm, Qm, Rm = _mat(A), _mat(B), _mat(Q), _mat(R)
+    status = ccall((:setup_families, _lib_path()), Int32,
+                   (Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Int32,
+                    Ptr{Float64}, Int32, Int32, Int32, Int32, Int32, Int32, Int32),
+                   Am, size(Am, 1), size(Am, 2), Bm, size(Bm, 1), size(Bm, 2), Qm, size(Qm, 1), size(Qm, 2), Rm, size(Rm, 1), size(Rm, 2),
+                   rho, length(rho), nx, nu, N, batch, _flag(on_device), _flag(verbose))
+    status == 0 || error("Setup failed with status: $status ($(_last_error()))")
+    solver.nx, solver.nu, solver.N, solver.rho, solver.batch = nx, nu, N, rho[1], batch
+    solver.A, solver.B, solver.Q, solver.R = A[:, :, 1], B[:, :, 1], Q[:, :, 1], R[:, :, 1]
+    solver.is_setup = true
+    update_settings(solver; abs_pri_tol=abs_pri_tol, abs_dua_tol=abs_dua_tol, max_iter=max_iter, check_termination=check_termination,
+                    verbose=verbose)
+    return status
+end
+
+# Replaces EVERY instance's family on a family solver: re-linearisation along a trajectory, gain scheduling, a sweep over rho.  A
+# and B come together, so do Q and R; what is nothing is kept.  The caches are recomputed on the device; settings, bounds, rows,
+# cones, references, the closed loop's configuration and the warm-start workspace are kept.  Fails, the solver unchanged, where
+# some instance's R + B'PB is singular (the error names the first such instance and their count).
+function set_families!(solver::TinyMPCSolver; A::Union{Array{Float64,3},Nothing}=nothing, B::Union{Array{Float64,3},Nothing}=nothing,
+                       Q::Union{Array{Float64,3},Nothing}=nothing, R::Union{Array{Float64,3},Nothing}=nothing,
+                       rho::Union{Vector{Float64},Nothing}=nothing)
+    _need(solver)
+    ((A === nothing) != (B === nothing) || (Q === nothing) != (R === nothing)) && error("set_families!: A and B come together, and so do Q and R")
+    want = Dict(:A => (solver.nx, solver.nx), :B => (solver.nx, solver.nu), :Q => (solver.nx, solver.nx), :R => (solver.nu, solver.nu))
+    for (name, m) in ((:A, A), (:B, B), (:Q, Q), (:R, R))
+        m === nothing || size(m) == (want[name]..., solver.batch) || error("set_families!: $name must be $((want[name]..., solver.batch))")
+    end
+    rho === nothing || length(rho) == solver.batch || error("set_families!: rho must have one entry per instance")
+    p(m) = m === nothing ? Ptr{Float64}(C_NULL) : pointer(m)
+    GC.@preserve A B Q R rho begin
+        _ok(ccall((:set_families, _lib_path()), Int32, (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                  p(A), p(B), p(Q), p(R), p(rho)), "Failed to set the families")
+    end
+    if A !== nothing
+        solver.A, solver.B = A[:, :, 1], B[:, :, 1]
+    end
+    if Q !== nothing
+        solver.Q, solver.R = Q[:, :, 1], R[:, :, 1]
+    end
+    rho === nothing || (solver.rho = rho[1])
+    return 0
+end
+
+# the Riccati caches of instances first .. first + count - 1 (1-based) of a family solver, whichever way it was set up:
+# (Kinf (nu, nx, n), Pinf (nx, nx, n), Quu_inv (nu, nu, n), AmBKt (nx, nx, n), sweeps (n,) — 1000: the instance stopped at the cap)
+function family_cache(solver::TinyMPCSolver; first::Integer=1, count::Union{Integer,Nothing}=nothing)
+    _need(solver)
+    n = count === nothing ? solver.batch - first + 1 : Int(count)
+    K, P = zeros(solver.nu, solver.nx, n), zeros(solver.nx, solver.nx, n)
+    Qi, Am = zeros(solver.nu, solver.nu, n), zeros(solver.nx, solver.nx, n)
+    sweeps = zeros(Int32, n)
+    _ok(ccall((:get_family_cache, _lib_path()), Int32, (Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+              first - 1, n, K, P, Qi, Am, sweeps), "Failed to get the family caches")
+    return (Kinf=K, Pinf=P, Quu_inv=Qi, AmBKt=Am, sweeps=sweeps)
+end
+
+# 0: not a family solver, 1: families set up on the host, 2: on the device
+function families_setup_mode(solver::TinyMPCSolver)
+    _need(solver)
+    m = ccall((:families_setup_mode, _lib_path()), Int32, ())
+    m < 0 && error("families_setup_mode failed ($(_last_error()))")
+    return Int(m)
 end
 
 # Spread the solver's batch over GPUs 0 .. n-1 of the node in contiguous shards (n = 1: back to one device).  Every

@@ -74,6 +74,19 @@ SIGNATURES = {
                                c_int, c_int, c_int, c_int]),
     "tinympc_create_families": (c_int, [ctypes.POINTER(c_vp), c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_int,
                                         c_int, c_int, c_int]),
+    "tinympc_create_families_device": (c_int, [ctypes.POINTER(c_vp), c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_int,
+                                               c_int, c_int, c_int]),
+    "tinympc_set_families": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "tinympc_get_family_cache": (c_int, [c_vp, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "tinympc_families_setup_mode": (c_int, [c_vp]),
+    "tinympc_families_setup_ms": (c_int, [c_vp, c_dp]),
+    "tinympc_host_precompute_sweeps": (c_int, [c_dp, c_dp, c_dp, c_dp, c_dbl, c_int, c_int]),
+    "tinympc_host_family_cache": (c_int, [c_dp, c_dp, c_dp, c_dp, c_dbl, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "setup_families": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_int, c_dp, c_int, c_int, c_dp, c_int, c_int, c_dp, c_int, c_int, c_int,
+                               c_int, c_int, c_int, c_int]),
+    "set_families": (c_int, [c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "get_family_cache": (c_int, [c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "families_setup_mode": (c_int, []),
     "tinympc_destroy": (None, [c_vp]),
     "tinympc_update_settings": (c_int, [c_vp, c_dbl, c_dbl, c_int, c_int, c_int, c_int]),
     "tinympc_set_bound_constraints": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
@@ -1082,6 +1095,30 @@ def host_precompute(A, B, Q, R, rho):
     return dict(Kinf=K, Pinf=P, Quu_inv=Qi, AmBKt=Am)
 
 
+def host_precompute_sweeps(A, B, Q, R, rho):
+    """the Riccati sweeps host_precompute runs for the family (1000: the cap); raises where R + B'PB is singular"""
+    A, B, Q, R = _mat(A), _mat(B), _mat(Q), _mat(R)
+    n = load_library().tinympc_host_precompute_sweeps(_dp(A), _dp(B), _dp(Q), _dp(R), float(rho), A.shape[0], B.shape[1])
+    if n < 0:
+        raise TinyMPCError(f"host_precompute_sweeps failed ({_err()})")
+    return int(n)
+
+
+def host_family_cache(A, B, Q, R, rho):
+    """the same cache by the rule the device setup of per-instance families runs (csrc/riccati.h), on the host, no GPU needed:
+    dict(Kinf, Pinf, Quu_inv, AmBKt, sweeps).  Shapes of the stream kernel's grid (nx in {2,3,4,6,8,10,12}, nu <= 4); raises
+    TinyMPCError where R + B'PB is singular."""
+    A, B, Q, R = _mat(A), _mat(B), _mat(Q), _mat(R)
+    nx, nu = A.shape[0], B.shape[1]
+    K, P = np.zeros((nu, nx), order="F"), np.zeros((nx, nx), order="F")
+    Qi, Am = np.zeros((nu, nu), order="F"), np.zeros((nx, nx), order="F")
+    sweeps = ctypes.c_int(0)
+    if load_library().tinympc_host_family_cache(_dp(A), _dp(B), _dp(Q), _dp(R), float(rho), nx, nu, _dp(K), _dp(P), _dp(Qi),
+                                                _dp(Am), ctypes.byref(sweeps)) != 0:
+        raise TinyMPCError(f"host_family_cache failed ({_err()})")
+    return dict(Kinf=K, Pinf=P, Quu_inv=Qi, AmBKt=Am, sweeps=int(sweeps.value))
+
+
 class BatchSolver:
     """Handle-API wrapper (tinympc_* in include/tinympc_hip.h): several solvers per process,
     device-resident I/O, stream-ordered solves.  Used by bench.py and the sharded driver."""
@@ -1098,21 +1135,77 @@ class BatchSolver:
         self.h = h
 
     @classmethod
-    def from_families(cls, A, B, Q, R, rho, N, device=-1, verbose=False):
+    def from_families(cls, A, B, Q, R, rho, N, device=-1, verbose=False, setup="host"):
         """One (A, B, Q, R, rho) family PER INSTANCE: A (nx, nx, batch), B (nx, nu, batch), Q (nx, nx, batch),
-        R (nu, nu, batch), rho (batch,).  Each instance gets its own Riccati cache (host, fp64)."""
+        R (nu, nu, batch), rho (batch,).  Each instance gets its own fp64 Riccati cache: computed on the host (setup="host",
+        the default) or by a kernel on the device (setup="device": the same recursion, and the coefficient pack is written
+        on the device too — the route for large batches)."""
+        if setup not in ("host", "device"):
+            raise TinyMPCError('from_families: setup is "host" or "device"')
         self = cls.__new__(cls)
         self.lib = load_library()
         A, B, Q, R = (np.asfortranarray(np.asarray(m, dtype=np.float64)) for m in (A, B, Q, R))
         rho = np.ascontiguousarray(np.asarray(rho, dtype=np.float64))
         self.nx, self.nu, self.N, self.batch = A.shape[0], B.shape[1], int(N), A.shape[2]
         h = c_vp()
-        st = self.lib.tinympc_create_families(ctypes.byref(h), _dp(A), _dp(B), _dp(Q), _dp(R), _dp(rho), self.nx,
-                                              self.nu, self.N, self.batch, int(device), 1 if verbose else 0)
+        create = self.lib.tinympc_create_families_device if setup == "device" else self.lib.tinympc_create_families
+        st = create(ctypes.byref(h), _dp(A), _dp(B), _dp(Q), _dp(R), _dp(rho), self.nx,
+                    self.nu, self.N, self.batch, int(device), 1 if verbose else 0)
         if st != 0:
-            raise TinyMPCError(f"tinympc_create_families failed ({_err()})")
+            raise TinyMPCError(f"tinympc_create_families{'_device' if setup == 'device' else ''} failed ({_err()})")
         self.h = h
         return self
+
+    def set_families(self, A=None, B=None, Q=None, R=None, rho=None):
+        """replaces EVERY instance's family on a family solver (either setup mode), arrays as from_families takes them; A and B
+        come together, so do Q and R; what is None is kept.  The caches are recomputed on the device (the solver is in device
+        mode afterwards); settings, bounds, rows, cones, the affine term, references, the closed loop's configuration and the
+        warm-start workspace are kept.  Raises, the solver unchanged, if some instance's R + B'PB is singular."""
+        if (A is None) != (B is None) or (Q is None) != (R is None):
+            raise TinyMPCError("set_families: A and B come together, and so do Q and R")
+        want = dict(A=(self.nx, self.nx), B=(self.nx, self.nu), Q=(self.nx, self.nx), R=(self.nu, self.nu))
+        arrs = {}
+        for name, m in (("A", A), ("B", B), ("Q", Q), ("R", R)):
+            if m is None:
+                arrs[name] = None
+                continue
+            m = np.asfortranarray(np.asarray(m, dtype=np.float64))
+            if m.shape != want[name] + (self.batch,):
+                raise TinyMPCError(f"set_families: {name} must be {want[name] + (self.batch,)}, got {m.shape}")
+            arrs[name] = m
+        if rho is not None:
+            rho = np.ascontiguousarray(np.asarray(rho, dtype=np.float64).reshape(-1))
+            if rho.size != self.batch:
+                raise TinyMPCError("set_families: rho must have one entry per instance")
+        self._chk(self.lib.tinympc_set_families(self.h, *[None if arrs[k] is None else _dp(arrs[k]) for k in "ABQR"],
+                                                None if rho is None else _dp(rho)), "set_families")
+
+    def family_cache(self, first=0, count=None, sweeps_only=False):
+        """the Riccati caches of instances [first, first + count) of a family solver, in either setup mode: dict(Kinf (nu, nx, n),
+        Pinf (nx, nx, n), Quu_inv (nu, nu, n), AmBKt (nx, nx, n), sweeps (n,) — 1000: the instance stopped at the cap);
+        sweeps_only: the sweep counts alone (no matrix is copied)"""
+        n = self.batch - int(first) if count is None else int(count)
+        if sweeps_only:
+            sw = np.zeros(n, dtype=np.int32)
+            self._chk(self.lib.tinympc_get_family_cache(self.h, int(first), n, None, None, None, None, sw.ctypes.data_as(c_ip)), "family_cache")
+            return dict(sweeps=sw)
+        K, P = np.zeros((self.nu, self.nx, n), order="F"), np.zeros((self.nx, self.nx, n), order="F")
+        Qi, Am = np.zeros((self.nu, self.nu, n), order="F"), np.zeros((self.nx, self.nx, n), order="F")
+        sw = np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.tinympc_get_family_cache(self.h, int(first), n, _dp(K), _dp(P), _dp(Qi), _dp(Am),
+                                                    sw.ctypes.data_as(c_ip)), "family_cache")
+        return dict(Kinf=K, Pinf=P, Quu_inv=Qi, AmBKt=Am, sweeps=sw)
+
+    @property
+    def families_setup_mode(self):
+        """0 not a family solver, 1 families set up on the host, 2 on the device"""
+        return int(self.lib.tinympc_families_setup_mode(self.h))
+
+    def families_setup_ms(self):
+        """kernel times in ms of the last device setup and the last device pack fill (-1.0: none has run)"""
+        ms = np.zeros(2)
+        self._chk(self.lib.tinympc_families_setup_ms(self.h, _dp(ms)), "families_setup_ms")
+        return float(ms[0]), float(ms[1])
 
     def close(self):
         if getattr(self, "h", None):
@@ -1288,6 +1381,11 @@ class BatchSolver:
         ru = lambda a: a.reshape((nu, N - 1, B), order="F")
         rx = lambda a: a.reshape((nx, N, B), order="F")
         return dict(d=ru(d), y=ru(y), z=ru(z), g=rx(g), v=rx(v))
+
+    def set_workspace(self, ws):
+        """installs a warm-start workspace: the dict get_workspace returns (d, y, z (nu, N-1, B); g, v (nx, N, B))"""
+        flat = {k: np.ascontiguousarray(np.asarray(ws[k], dtype=np.float64).ravel(order="F")) for k in ("d", "y", "g", "v", "z")}
+        self._chk(self.lib.tinympc_set_workspace(self.h, *[_dp(flat[k]) for k in ("d", "y", "g", "v", "z")]), "set_workspace")
 
     def device_buffers(self):
         ptrs = [c_vp() for _ in range(9)]
