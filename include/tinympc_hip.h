@@ -110,7 +110,10 @@ int print_problem_data(int verbose);
  * With batch > 1 the batch dimension may ride on the widths, as it does for set_bound_constraints: Alin_x rows_x x (nx*batch)
  * with blin_x_len = rows_x*batch, Alin_u rows_u x (nu*batch) with blin_u_len = rows_u*batch give every instance its own rows
  * (tinympc_set_instance_linear: [batch] blocks of rows x n, column-major, and [batch][rows]; a set_gpus solver scatters the
- * slices to its shards).  Every non-empty side must then have the per-instance width: mixed widths are an error. */
+ * slices to its shards).  Every non-empty side must then have the per-instance width: mixed widths are an error.
+ * set_cone_constraints takes the batch on its widths likewise: cu_len == Acu_len*batch and cx_len == Acx_len*batch, laid out
+ * [batch][cone], give every instance its own coefficients over the one layout (tinympc_set_instance_cones; +inf: a cone the
+ * instance does not have); mixed widths are an error. */
 int set_linear_constraints(double *Alin_x_data, int Alin_x_rows, int Alin_x_cols,
                            double *blin_x_data, int blin_x_len, double *Alin_u_data,
                            int Alin_u_rows, int Alin_u_cols, double *blin_u_data, int blin_u_len,
@@ -263,7 +266,8 @@ int tinympc_set_bound_constraints(tinympc_solver *s, const double *x_min, const 
  * precision 1 and 2; tinympc_kernel_name reports "stream4<NX,NU;ib>", "generic<ib>" or "generic<f64;ib>".  A per-instance-family
  * solver needs the stream form.  Refused, tinympc_last_error naming the condition: adaptive rho beside per-instance bounds (in
  * either order); tinympc_mpc_rollout, unless TINYMPC_HIP_STREAM_MPC=1 gives the solver the chain of launches (there is no
- * in-kernel loop with per-instance bounds).  Linear rows per instance: tinympc_set_instance_linear.  Per-instance cones do not exist. */
+ * in-kernel loop with per-instance bounds).  Linear rows per instance: tinympc_set_instance_linear; cone coefficients per instance:
+ * tinympc_set_instance_cones. */
 int tinympc_set_instance_bounds(tinympc_solver *s, const double *x_min, const double *x_max, const double *u_min,
                                 const double *u_max, int per_knot);
 /* 0: shared bounds, 1: per instance and constant over the horizon, 2: per instance and per knot */
@@ -303,12 +307,49 @@ int tinympc_enable_linear(tinympc_solver *s, int en_state_linear, int en_input_l
  * Refused, tinympc_last_error naming the condition: more than 8 rows on a side; a null side with rows > 0; adaptive rho beside
  * per-instance rows (in either order); tinympc_mpc_rollout unless the solver has a plant of its own / a disturbance / a
  * reference trajectory (whose loop is a chain of launches) or TINYMPC_HIP_STREAM_MPC=1 gives it that chain — there is no
- * in-kernel loop with per-instance rows.  Follow-ups, not built: rows per knot, per-instance cones, the on-chip families, the
+ * in-kernel loop with per-instance rows.  Cone coefficients per instance: tinympc_set_instance_cones.  Follow-ups, not built: rows per knot, the on-chip families, the
  * fp64-state and adaptive stream forms, loop forms, units specialised at setup, per-instance equality helpers. */
 int tinympc_set_instance_linear(tinympc_solver *s, const double *Alin_x, int rows_x, const double *blin_x,
                                 const double *Alin_u, int rows_u, const double *blin_u);
 /* 0: no rows or rows shared by the batch, 1: per instance */
 int tinympc_lin_mode(tinympc_solver *s);
+/* Second-order cones with a coefficient PER INSTANCE (no counterpart in the reference, whose solver holds one constraint set:
+ * a sweep over glide-slope angles or friction coefficients, a fleet whose vehicles have different thrust-vector limits, a
+ * policy trained under a randomised cone).  The LAYOUT stays one for the batch — first row Acu[i] / Acx[i] and dimension
+ * qcu[i] / qcx[i] of each cone, inputs first, at most 8 a side, the last row of a block the axis, as for
+ * tinympc_set_cone_constraints — and the coefficient becomes per instance:
+ *   cu: [batch][n_input_cones], cx: [batch][n_state_cones]
+ * Instance b projects cone i with its own mu[b][i], by exactly the rule of the shared set.  mu = +inf means "instance b has no
+ * cone i": its rows are then left as they are, as rows outside every cone are — that is how instances carry different cones.
+ * A side that is enabled carries its slack and dual for every instance, an instance whose cones on that side are all absent
+ * included — as a shared set whose cones never act does: such an instance's iterates are those of a solver with cones that
+ * never bind, not bit for bit those of a solver without cones.  Values are rounded to fp32 as the shared set's are, so
+ * coefficients that all equal a shared set reproduce the shared-cones stream kernel bit for bit.  Non-empty sides are enabled
+ * on success, as tinympc_set_cone_constraints does; tinympc_enable_cones / tinympc_update_settings switch a side off and on
+ * again without a new upload.  The solver keeps host copies (a later tinympc_set_precision keeps the coefficients);
+ * re-batching a solver (set_batch_size, set_gpus) drops them, as it resets every per-instance input;
+ * tinympc_set_cone_constraints afterwards drops them too: back to the shared set and to the kernels that serve it.  Both
+ * sides empty: no cones at all, shared mode.
+ * Such a solver runs on the `ic` forms of the run-time-shape kernels, whatever on-chip kernel its shape has (the matrix-core
+ * kernels and the units specialised for a cone list hold one coefficient set): the stream kernel's for (nx, nu) in {(4,1),
+ * (6,3), (12,4)} at precision 0 — any horizon the LDS image holds, one family or one per instance, the affine term,
+ * references, chunked solves — and the generic kernel's for every other shape and for precision 1 and 2;
+ * tinympc_kernel_name reports "stream4<NX,NU;ic>", "generic<ic>" or "generic<f64;ic>".  The `ic` forms are `il` forms: they read
+ * box bounds and linear rows per instance, so per-instance bounds and rows (tinympc_set_instance_bounds,
+ * tinympc_set_instance_linear) combine with the cones under the same names, and shared ones are uploaded replicated;
+ * tinympc_bounds_mode and tinympc_lin_mode keep reporting what the caller set.  A per-instance-family solver needs the stream
+ * form.  Refused, tinympc_last_error naming the condition: more than 8 cones on a side; a null side with cones > 0; a cone
+ * outside the rows; mu <= 0 or non-finite other than +inf; adaptive rho beside per-instance cones (in either order);
+ * precision 2 or adaptive rho on per-instance families, as without them; tinympc_mpc_rollout unless the solver has a plant
+ * of its own / a disturbance / a reference trajectory (whose loop is a chain of launches) or TINYMPC_HIP_STREAM_MPC=1 gives
+ * it that chain — there is no in-kernel loop with per-instance cones.  Follow-ups, not built: a per-instance cone layout
+ * (Ac, qc), cones per knot, the on-chip families and units specialised at setup, the fp64-state and adaptive stream forms,
+ * loop forms. */
+int tinympc_set_instance_cones(tinympc_solver *s, const int *Acu, const int *qcu, const double *cu /* [batch][n_input_cones] */,
+                               int n_input_cones, const int *Acx, const int *qcx, const double *cx /* [batch][n_state_cones] */,
+                               int n_state_cones);
+/* 0: no cones or cones shared by the batch, 1: a coefficient per instance */
+int tinympc_cone_mode(tinympc_solver *s);
 int tinympc_get_cache_terms(tinympc_solver *s, double *Kinf, double *Pinf, double *Quu_inv,
                             double *AmBKt);
 /* Adaptive rho — admm.cpp:147-174 + rho_benchmark.cpp, per instance: every 5th ADMM iteration each instance predicts
@@ -646,7 +687,8 @@ int tinympc_reload_switches(tinympc_solver *s);
 int tinympc_effective_precision(tinympc_solver *s);
 /* Name of the kernel family the solver's shape / options select: "quad<nx,nu,N,gG>", "mfma<...>", "mfmat<...>",
  * "stream4<nx,nu>", "generic", ...; with per-instance bounds "stream4<nx,nu;ib>", "generic<ib>", "generic<f64;ib>"; with
- * per-instance linear rows (beside per-instance bounds or not) "stream4<nx,nu;il>", "generic<il>", "generic<f64;il>" */
+ * per-instance linear rows (beside per-instance bounds or not) "stream4<nx,nu;il>", "generic<il>", "generic<f64;il>"; with
+ * per-instance cone coefficients (beside either or not) "stream4<nx,nu;ic>", "generic<ic>", "generic<f64;ic>" */
 const char *tinympc_kernel_name(tinympc_solver *s);
 /* Name of the kernel the most recent launch actually ran: the family above, or the variant a launch of that family took
  * for its calling pattern — "lean<nx,nu,N>" for one-shot solves (cold start, workspace not kept) of a one-lane-per-instance
@@ -655,7 +697,8 @@ const char *tinympc_last_launch_name(tinympc_solver *s);
 /* Algorithmic HBM bytes and FLOPs of one solve of the whole batch (SURVEY.md 8d formulas);
  * flops assume `iters` ADMM iterations per instance.  Per-instance bounds count too: given per knot, 2 (nx N + nu (N-1)) floats
  * per instance and iteration (max_iter of them); constant over the horizon, 2 (nx + nu) floats per instance, once.  Per-instance
- * linear rows: rows_x (nx + 2) + rows_u (nu + 2) floats per instance, once. */
+ * linear rows: rows_x (nx + 2) + rows_u (nu + 2) floats per instance, once.  Per-instance cone coefficients: one float per cone
+ * and instance, once. */
 double tinympc_algorithmic_bytes(tinympc_solver *s);
 double tinympc_algorithmic_flops(tinympc_solver *s, int iters);
 const char *tinympc_last_error(void);
@@ -731,6 +774,10 @@ int tinympc_sharded_set_instance_bounds(tinympc_sharded *s, const double *x_min,
  * gets the slice [lo_i, hi_i) */
 int tinympc_sharded_set_instance_linear(tinympc_sharded *s, const double *Alin_x, int rows_x, const double *blin_x,
                                         const double *Alin_u, int rows_u, const double *blin_u);
+/* per-instance cone coefficients over the WHOLE batch (arguments as tinympc_set_instance_cones): the layout goes to every
+ * shard, the coefficients are contiguous per instance, shard i gets the slice [lo_i, hi_i) */
+int tinympc_sharded_set_instance_cones(tinympc_sharded *s, const int *Acu, const int *qcu, const double *cu, int n_input_cones,
+                                       const int *Acx, const int *qcx, const double *cx, int n_state_cones);
 /* per-instance inputs over the WHOLE batch (cols as tinympc_set_x0 / _x_ref / _u_ref), scattered to the shards */
 int tinympc_sharded_set_x0(tinympc_sharded *s, const double *x0, int cols);
 int tinympc_sharded_set_x_ref(tinympc_sharded *s, const double *x_ref, int cols);
@@ -761,6 +808,8 @@ int get_gpus(void);
  * workspace persists between solves (admm.cpp:112-115).  The kernel the last solve ran on, for logs. */
 int set_warm_start(int warm_start);
 const char *get_kernel_name(void);
+/* tinympc_cone_mode of the process-global solver (a set_gpus solver: of its first shard); -1 without a solver */
+int get_cone_mode(void);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,7 @@ from .tinympc import (  # noqa: E402,F401
     set_gpus,
     set_warm_start,
     kernel_name,
+    cone_mode,
     shard_range,
     specialise,
     TinyMPCError,

@@ -12,10 +12,13 @@
 // callers who want its digits back rather than the 1e-5 of the fp32-state kernels (ill-conditioned families miss 1e-5
 // there by rounding their duals to fp32 every iteration: profiles/r03_fuzz_large.txt).  The precision-2 workspace lives in
 // its own fp64 block (P.ws64, layout below); inputs x0 / references and the returned solution stay fp32 arrays.
-#ifndef TMPC_ADMM_GENERIC_HIP_H   // (no #pragma once: the file includes itself once, at its end, for the per-instance-rows form's entry point)
+#ifndef TMPC_ADMM_GENERIC_HIP_H   // (no #pragma once: the file includes itself twice, at its end, for the per-instance-rows form's and the per-instance-cones form's entry points)
 #define TMPC_ADMM_GENERIC_HIP_H
 #define TMPC_GENERIC_IL 0
+#define TMPC_GENERIC_IC 0
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 #include "admm_params.h"
 
@@ -75,18 +78,25 @@ namespace tmpc {
 
 // IB: box bounds per instance (tinympc_set_instance_bounds) — read from P.ibx / P.ibu ([min | max][knot][instance][row], the
 // knot stride 0 where they are constant over the horizon) at this instance's column instead of the shared pack; fixed rho.
-// The kernel is compiled twice from this one text — the file includes itself at its end with TMPC_GENERIC_IL = 1 — as
-// admm_generic_kernel and as admm_generic_il_kernel<RT, ST>, the per-instance-rows form (tinympc_set_instance_linear): the IB
-// form whose linear rows are the instance's own, read [b]-strided from P.il_ax .. P.il_n2u ([row][instance][entry] and
-// [row][instance]).  A kernel of its own name, so that the other forms keep theirs.
-#if TMPC_GENERIC_IL
+// The kernel is compiled three times from this one text — the file includes itself at its end with TMPC_GENERIC_IL = 1, then
+// with TMPC_GENERIC_IC = 1 — as admm_generic_kernel, as admm_generic_il_kernel<RT, ST>, the per-instance-rows form
+// (tinympc_set_instance_linear): the IB form whose linear rows are the instance's own, read [b]-strided from P.il_ax ..
+// P.il_n2u ([row][instance][entry] and [row][instance]), and as admm_generic_ic_kernel<RT, ST>, the per-instance-cones form
+// (tinympc_set_instance_cones): the IL form whose cone coefficients are the instance's own, P.ic_cx / P.ic_cu
+// ([cone][instance]; +inf: the instance does not have the cone, which is then not projected).  Kernels of their own names,
+// so that the other forms keep theirs.
+#if TMPC_GENERIC_IC
+template <class RT, class ST>
+__global__ __launch_bounds__(256) void admm_generic_ic_kernel(const AdmmParams P) {
+    constexpr bool IB = true, IL = true, IC = true;
+#elif TMPC_GENERIC_IL
 template <class RT, class ST>
 __global__ __launch_bounds__(256) void admm_generic_il_kernel(const AdmmParams P) {
-    constexpr bool IB = true, IL = true;
+    constexpr bool IB = true, IL = true, IC = false;
 #else
 template <class RT, class ST = float, bool IB = false>
 __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
-    constexpr bool IL = false;
+    constexpr bool IL = false, IC = false;
 #endif
     constexpr bool WIDE = sizeof(ST) == 8;
     const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -127,6 +137,15 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
     auto rn2u = [&](int c) -> ST {
         if constexpr (IL) return (ST)P.il_n2u[(long)c * P.il_rb + b];
         else return (ST)ln2u[c];
+    };
+    // mu of cone c: the shared set's, or (IC) this instance's own
+    auto rcx = [&](int c) -> float {
+        if constexpr (IC) return P.ic_cx[(long)c * P.ic_rc + b];
+        else return P.cx[c];
+    };
+    auto rcu = [&](int c) -> float {
+        if constexpr (IC) return P.ic_cu[(long)c * P.ic_rc + b];
+        else return P.cu[c];
     };
     const float *xmin = P.bounds, *xmax = P.bounds + EX, *umin = P.bounds + 2 * EX,
                 *umax = P.bounds + 2 * EX + EU, *cQd = P.bounds + 2 * EX + 2 * EU,
@@ -265,7 +284,10 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
                 for (int a = 0; a < nu; ++a) AT(szcn, k * nu + a) = AT(su, k * nu + a) + AT(syc, k * nu + a);
                 for (int c = 0; c < P.ncu; ++c) {
                     const int s0 = k * nu + P.Acu[c], qd = P.qcu[c];
-                    const ST mu = (ST)P.cu[c];
+                    const float muf = rcu(c);
+                    if constexpr (IC)
+                        if (!(muf <= FLT_MAX)) continue;   // (+inf: not this instance's)
+                    const ST mu = (ST)muf;
                     ST a2 = 0;
                     for (int j = 0; j < qd - 1; ++j) a2 = gfma(AT(szcn, s0 + j), AT(szcn, s0 + j), a2);
                     const ST an = gsqrt(a2), u0 = AT(szcn, s0 + qd - 1) * mu;
@@ -327,7 +349,10 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
                 for (int r = 0; r < nx; ++r) AT(svcn, k * nx + r) = AT(sx, k * nx + r) + AT(sgc, k * nx + r);
                 for (int c = 0; c < P.ncx; ++c) {
                     const int s0 = k * nx + P.Acx[c], qd = P.qcx[c];
-                    const ST mu = (ST)P.cx[c];
+                    const float muf = rcx(c);
+                    if constexpr (IC)
+                        if (!(muf <= FLT_MAX)) continue;
+                    const ST mu = (ST)muf;
                     ST a2 = 0;
                     for (int j = 0; j < qd - 1; ++j) a2 = gfma(AT(svcn, s0 + j), AT(svcn, s0 + j), a2);
                     const ST an = gsqrt(a2), u0 = AT(svcn, s0 + qd - 1) * mu;
@@ -540,9 +565,14 @@ __global__ __launch_bounds__(256) void admm_generic_kernel(const AdmmParams P) {
 }
 
 }  // namespace tmpc
-#if !TMPC_GENERIC_IL
+#if !TMPC_GENERIC_IL && !TMPC_GENERIC_IC
 #undef TMPC_GENERIC_IL
 #define TMPC_GENERIC_IL 1
+#include "admm_generic.hip.h"
+#undef TMPC_GENERIC_IL
+#define TMPC_GENERIC_IL 0
+#undef TMPC_GENERIC_IC
+#define TMPC_GENERIC_IC 1
 #include "admm_generic.hip.h"
 #define TMPC_GENERIC_BOTH
 #endif

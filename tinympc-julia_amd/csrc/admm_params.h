@@ -121,6 +121,14 @@ struct AdmmParams {
     // shared bounds uploads them replicated).  NULL: the rows are the shared pack's (P.lin) ----
     const float *il_ax, *il_au, *il_bx, *il_n2x, *il_bu, *il_n2u;
     long il_rx, il_ru, il_rb;
+    // ---- stream / generic kernels, `ic` forms: the cone coefficient mu PER INSTANCE (tinympc_set_instance_cones), fp32,
+    // [cone][instance], a cone ic_rc elements (the solver's whole batch) behind the one before; P.ncx / P.ncu cones a side
+    // and the layout Acx .. qcu as for the shared set.  Indexed by the INSTANCE, as the `ib` bounds are.  +inf: the instance
+    // does not have the cone (no projection; its rows stay as they are).  The `ic` forms are `il` forms: they read their
+    // bounds from ibx / ibu and their rows from il_* (a solver with shared ones uploads them replicated).  NULL: the
+    // coefficients are cx / cu above ----
+    const float *ic_cx, *ic_cu;
+    long ic_rc;
 };
 enum : int { IB_STATE = 1, IB_INPUT = 2 };
 enum : int { HF_NO_REFILL = 1, HF_NO_UNI = 2, HF_NO_OS = 4, HF_LEAN_SCALED = 8 };   // (HF_LEAN_SCALED: the lean pack's scaled block is valid)

@@ -19,12 +19,15 @@
 //     quad kernel); one family per instance (HET): the same rows as per-lane columns in HBM;
 //   * second-order cones may straddle lanes: squared head norms and the axis value are summed over
 //     the group with DPP steps.
-#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself three times, at its end, for the loop form's, the per-instance-bounds form's and the per-instance-rows form's entry points)
+#ifndef TMPC_ADMM_STREAMG_HIP_H   // (no #pragma once: the file includes itself four times, at its end, for the loop form's, the per-instance-bounds form's, the per-instance-rows form's and the per-instance-cones form's entry points)
 #define TMPC_ADMM_STREAMG_HIP_H
 #define TMPC_STREAMG_MPC 0
 #define TMPC_STREAMG_IB 0
 #define TMPC_STREAMG_IL 0
+#define TMPC_STREAMG_IC 0
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 #include "admm_generic.hip.h"   // Ws64, the type-generic gmin / gmax / gsqrt / gfma / gupmax
 #include "admm_params.h"
@@ -294,10 +297,11 @@ namespace tmpc {
 // lanes' x_j and u_a by quad broadcasts; the next solve starts from (float)x+ with the workspace as the scratch block
 // already holds it (what saving and reloading it would give: the kept arrays stay, the work arrays are zeroed), with the
 // step's slice of P.xref_seq / P.uref_seq as its references.  The last solve leaves through the ordinary epilogue.
-// The kernel below is compiled four times from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1,
-// then with TMPC_STREAMG_IB = 1, then with TMPC_STREAMG_IL = 1 — as admm_streamg_kernel, as the loop form's
-// admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST>, as the per-instance-bounds form's admm_streamg_ib_kernel<NX, NU, G, EXT, HET, OS>
-// and as the per-instance-rows form's admm_streamg_il_kernel<NX, NU, G, HET, OS>.  The preprocessor decides what
+// The kernel below is compiled five times from this one text — the file includes itself at its end with TMPC_STREAMG_MPC = 1,
+// then with TMPC_STREAMG_IB = 1, then with TMPC_STREAMG_IL = 1, then with TMPC_STREAMG_IC = 1 — as admm_streamg_kernel, as the
+// loop form's admm_streamg_mpc_kernel<NX, NU, G, EXT, HET, ST>, as the per-instance-bounds form's admm_streamg_ib_kernel<NX, NU,
+// G, EXT, HET, OS>, as the per-instance-rows form's admm_streamg_il_kernel<NX, NU, G, HET, OS> and as the per-instance-cones
+// form's admm_streamg_ic_kernel<NX, NU, G, HET, OS>.  The preprocessor decides what
 // `if constexpr` cannot wrap (the loop over steps around the iteration loop, the step's reference pointers), so that the plain
 // kernel's text, name and code are what they were before the other forms existed (a further template parameter, even a
 // defaulted one, renames every stream kernel).
@@ -317,30 +321,46 @@ namespace tmpc {
 // wavefronts with little to spare, and 8 + 8 rows are 64 more), not re-read through the cache (a dependent load in front of
 // every row of a projection that takes them one after the other).  Only the rows present are held: 4 T (mlx RX + mlu RU) +
 // 8 (T / G) (mlx + mlu) bytes a workgroup.  The projection is project_halfspaces_group, the shared form's, on other pointers.
-#if TMPC_STREAMG_IL
+//
+// IC: the cone coefficient mu PER INSTANCE (tinympc_set_instance_cones), the file's fourth self-inclusion:
+// admm_streamg_ic_kernel<NX, NU, G, HET, OS>, the IL form in full — bounds and rows per instance, the sides of rows and cones
+// run-time flags — whose cones keep the batch's layout (P.Acx .. P.qcu, the membership masks) and take mu from P.ic_cx /
+// P.ic_cu, fp32, [cone][instance].  A group reads its instance's ncx + ncu values once, where the IL slice is filled, into a
+// group's part of that slice, behind b and |a|^2 ([state cones | input cones]: 4 (T / G) (ncx + ncu) bytes a workgroup) — not into
+// registers, of which (12, 4) has none to spare.  At the two projection sites the value comes from there; +inf — the instance
+// does not have the cone — skips the projection, a condition uniform over the group's lanes, so the quad sums inside
+// project_soc_group stay whole.  The projection is project_soc_group, the shared form's, on another mu.
+#if TMPC_STREAMG_IC
+template <int NX, int NU, int G, bool HET, bool OS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES_IB(G, NX)))) void admm_streamg_ic_kernel(const AdmmParams P) {
+    using RT = double;
+    using ST = float;
+    constexpr int EXT = 2;
+    constexpr bool ADP = false, MPC = false, IB = true, IL = true, IC = true;
+#elif TMPC_STREAMG_IL
 template <int NX, int NU, int G, bool HET, bool OS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES_IB(G, NX)))) void admm_streamg_il_kernel(const AdmmParams P) {
     using RT = double;
     using ST = float;
     constexpr int EXT = 2;
-    constexpr bool ADP = false, MPC = false, IB = true, IL = true;
+    constexpr bool ADP = false, MPC = false, IB = true, IL = true, IC = false;
 #elif TMPC_STREAMG_IB
 template <int NX, int NU, int G, int EXT, bool HET, bool OS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TMPC_STREAM_WAVES_IB(G, NX)))) void admm_streamg_ib_kernel(const AdmmParams P) {
     using RT = double;
     using ST = float;
-    constexpr bool ADP = false, MPC = false, IB = true, IL = false;
+    constexpr bool ADP = false, MPC = false, IB = true, IL = false, IC = false;
 #elif !TMPC_STREAMG_MPC
 template <int NX, int NU, int G, class RT, int EXT, bool HET, bool OS, bool ADP = false, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, OS) : TMPC_STREAM_WAVES(G)))) void admm_streamg_kernel(const AdmmParams P) {
-    constexpr bool MPC = false, IB = false, IL = false;
+    constexpr bool MPC = false, IB = false, IL = false, IC = false;
 #else
 template <int NX, int NU, int G, int EXT, bool HET, class ST = float>
 __global__ __launch_bounds__(256)
     __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 8 ? TMPC_STREAM_WAVES64(G, EXT, false) : TMPC_STREAM_WAVES(G)))) void admm_streamg_mpc_kernel(const AdmmParams P) {
     using RT = double;
-    constexpr bool OS = false, ADP = false, MPC = true, IB = false, IL = false;
+    constexpr bool OS = false, ADP = false, MPC = true, IB = false, IL = false, IC = false;
 #endif
     static_assert(!IB || (!ADP && sizeof(ST) == 4 && sizeof(RT) == 8 && G == 4), "per-instance bounds: fixed rho, fp32 state, fp64 recurrences, four lanes");
     static_assert(!ADP || (!HET && EXT == 0), "adaptive rho: one family, box sets only");
@@ -488,10 +508,15 @@ __global__ __launch_bounds__(256)
     // behind the bound image (filled below, once the instance offsets exist)
     constexpr int LSX = IL ? T * RX : G * RX, LSU = IL ? T * RU : G * RU;
     float *const s_il = IL ? s_bnd + bnd_len : nullptr;
-    float *const s_ilb = IL ? s_il + (long)T * (mlx * RX + mlu * RU) + (tid / G) * 2 * (mlx + mlu) : nullptr;
+    float *const s_ilb = IL ? s_il + (long)T * (mlx * RX + mlu * RU) + (tid / G) * (2 * (mlx + mlu) + (IC ? ncx + ncu : 0)) : nullptr;
     const float *lax = IL ? s_il + tid * RX : s_lax + q * RX, *lau = IL ? s_il + T * mlx * RX + tid * RU : s_lau + q * RU;
     const float *lbx = IL ? s_ilb : s_lb, *ln2x = IL ? s_ilb + mlx : s_lb + LIN_MAX_ROWS;
     const float *lbu = IL ? s_ilb + 2 * mlx : s_lb + 2 * LIN_MAX_ROWS, *ln2u = IL ? s_ilb + 2 * mlx + mlu : s_lb + 3 * LIN_MAX_ROWS;
+    // (IC) the group's cone coefficients, state cones then input cones, behind its b and |a|^2.  In the sweeps the IC form reaches
+    // them, and the four arrays in front of them, from s_ilb by offsets made opaque per use (knot_sgpr): pointers of their own are
+    // loop invariants, hoisted out of the iteration loop into a register each, and the (one family per instance, workspace kept)
+    // kernels of (6, 3) and (12, 4) have none to spare — with them they spill one and two registers, without them none
+    float *const s_ic = IC ? s_ilb + 2 * (mlx + mlu) : nullptr;
 
     // Scratch: [array][knot][instance][real row].  Addresses are (uniform 64-bit base in SGPRs) + (32-bit byte
     // offset of the lane); the knot index is made opaque per knot (knot_sgpr) so that no per-array 64-bit
@@ -631,6 +656,12 @@ __global__ __launch_bounds__(256)
 #pragma unroll
             for (int m = 0; m < RU; ++m) s_il[(long)T * mlx * RX + ((long)k * T + tid) * RU + m] = OKU(m) ? a[m] : 0.f;
             if (q == 0) s_ilb[2 * mlx + k] = P.il_bu[(long)k * P.il_rb + bi], s_ilb[2 * mlx + mlu + k] = P.il_n2u[(long)k * P.il_rb + bi];
+        }
+        if constexpr (IC) {   // ... and its cone coefficients, one lane of the group each side
+            if (q == 0)
+                for (int c = 0; c < ncx; ++c) s_ic[c] = P.ic_cx[(long)c * P.ic_rc + bi];
+            if (q == 1)
+                for (int c = 0; c < ncu; ++c) s_ic[ncx + c] = P.ic_cu[(long)c * P.ic_rc + bi];
         }
         __syncthreads();
     }
@@ -857,7 +888,11 @@ __global__ __launch_bounds__(256)
                         for (int m = 0; m < RX; ++m) wc[m] = xf[m] + mkx(f.gc[m], m);
                         for (int c = 0; c < ncx; ++c) {
                             const uint4 mk = cm[c * G];
-                            project_soc_group<G, RX>(wc, mk.x, mk.y, (ST)P.cx[c]);
+                            if constexpr (IC) {
+                                const float mu = s_ilb[knot_sgpr(2 * (mlx + mlu) + c)];
+                                if (mu <= FLT_MAX) project_soc_group<G, RX>(wc, mk.x, mk.y, (ST)mu);   // (+inf: not this instance's)
+                            } else
+                                project_soc_group<G, RX>(wc, mk.x, mk.y, (ST)P.cx[c]);
                         }
 #pragma unroll
                         for (int m = 0; m < RX; ++m) {
@@ -872,7 +907,10 @@ __global__ __launch_bounds__(256)
                     if (lin_x) {
 #pragma unroll
                         for (int m = 0; m < RX; ++m) wl[m] = xf[m] + mkx(f.gl[m], m);
-                        project_halfspaces_group<G, RX>(wl, lax, LSX, mlx, lbx, ln2x);
+                        if constexpr (IC)
+                            project_halfspaces_group<G, RX>(wl, lax, LSX, mlx, s_ilb, s_ilb + knot_sgpr(mlx));
+                        else
+                            project_halfspaces_group<G, RX>(wl, lax, LSX, mlx, lbx, ln2x);
 #pragma unroll
                         for (int m = 0; m < RX; ++m) {
                             gln[m] = (mkx(f.gl[m], m) + xf[m]) - wl[m];
@@ -978,7 +1016,11 @@ __global__ __launch_bounds__(256)
                             for (int m = 0; m < RU; ++m) zc2[m] = uf[m] + mku(f.yc[m], m);
                             for (int c = 0; c < ncu; ++c) {
                                 const uint4 mk = cm[c * G];
-                                project_soc_group<G, RU>(zc2, mk.z, mk.w, (ST)P.cu[c]);
+                                if constexpr (IC) {
+                                    const float mu = s_ilb[knot_sgpr(2 * (mlx + mlu) + ncx + c)];
+                                    if (mu <= FLT_MAX) project_soc_group<G, RU>(zc2, mk.z, mk.w, (ST)mu);
+                                } else
+                                    project_soc_group<G, RU>(zc2, mk.z, mk.w, (ST)P.cu[c]);
                             }
 #pragma unroll
                             for (int m = 0; m < RU; ++m) {
@@ -993,7 +1035,10 @@ __global__ __launch_bounds__(256)
                         if (lin_u) {
 #pragma unroll
                             for (int m = 0; m < RU; ++m) zl2[m] = uf[m] + mku(f.yl[m], m);
-                            project_halfspaces_group<G, RU>(zl2, lau, LSU, mlu, lbu, ln2u);
+                            if constexpr (IC)
+                                project_halfspaces_group<G, RU>(zl2, lau, LSU, mlu, s_ilb + knot_sgpr(2 * mlx), s_ilb + knot_sgpr(2 * mlx + mlu));
+                            else
+                                project_halfspaces_group<G, RU>(zl2, lau, LSU, mlu, lbu, ln2u);
 #pragma unroll
                             for (int m = 0; m < RU; ++m) {
                                 yln[m] = (mku(f.yl[m], m) + uf[m]) - zl2[m];
@@ -1433,7 +1478,7 @@ __global__ __launch_bounds__(256)
 }
 
 }  // namespace tmpc
-#if !TMPC_STREAMG_MPC && !TMPC_STREAMG_IB && !TMPC_STREAMG_IL
+#if !TMPC_STREAMG_MPC && !TMPC_STREAMG_IB && !TMPC_STREAMG_IL && !TMPC_STREAMG_IC
 #undef TMPC_STREAMG_MPC
 #define TMPC_STREAMG_MPC 1
 #include "admm_streamg.hip.h"
@@ -1446,6 +1491,11 @@ __global__ __launch_bounds__(256)
 #define TMPC_STREAMG_IB 0
 #undef TMPC_STREAMG_IL
 #define TMPC_STREAMG_IL 1
+#include "admm_streamg.hip.h"
+#undef TMPC_STREAMG_IL
+#define TMPC_STREAMG_IL 0
+#undef TMPC_STREAMG_IC
+#define TMPC_STREAMG_IC 1
 #include "admm_streamg.hip.h"
 #define TMPC_STREAMG_BOTH
 #endif

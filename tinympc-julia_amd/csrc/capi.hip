@@ -272,6 +272,15 @@ int tinympc_set_cone_constraints(tinympc_solver *s, const int *Acu, const int *q
                    [&] { return s->s.set_cones(Acu, qcu, cu, n_input_cones, Acx, qcx, cx, n_state_cones); });
 }
 
+int tinympc_set_instance_cones(tinympc_solver *s, const int *Acu, const int *qcu, const double *cu, int n_input_cones,
+                               const int *Acx, const int *qcx, const double *cx, int n_state_cones) {
+    if (!s) return -1;
+    return guarded("set_instance_cones",
+                   [&] { return s->s.set_instance_cones(Acu, qcu, cu, n_input_cones, Acx, qcx, cx, n_state_cones); });
+}
+
+int tinympc_cone_mode(tinympc_solver *s) { return s ? s->s.cone_mode : -1; }
+
 int tinympc_set_cache_terms(tinympc_solver *s, const double *Kinf, const double *Pinf,
                             const double *Quu_inv, const double *AmBKt) {
     if (!s || !Kinf || !Pinf || !Quu_inv || !AmBKt) return -1;
@@ -303,6 +312,10 @@ int tinympc_set_adaptive_rho(tinympc_solver *s, int enable, double rho_min, doub
     }
     if (enable && v.lin_mode) {
         set_error("adaptive_rho is not available with per-instance linear rows (set_instance_linear)");
+        return -1;
+    }
+    if (enable && v.cone_mode) {
+        set_error("adaptive_rho is not available with per-instance cones (set_instance_cones)");
         return -1;
     }
     if (enable && !(rho_min > 0.0 && rho_max >= rho_min)) {
@@ -797,6 +810,8 @@ double tinympc_algorithmic_bytes(tinympc_solver *s) {
     if (v.bounds_mode == 1) per += 4.0 * 2.0 * (v.nx + v.nu);
     // per-instance linear rows: coefficients, right-hand side and |a|^2 of every row, read once (they are constant over the horizon)
     if (v.lin_mode) per += 4.0 * (v.mlx * (v.nx + 2.0) + v.mlu * (v.nu + 2.0));
+    // per-instance cone coefficients: one float per cone, read once
+    if (v.cone_mode) per += 4.0 * (v.ncx + v.ncu);
     return per * v.batch;
 }
 
@@ -964,6 +979,10 @@ int set_precision(int precision) {
 const char *get_kernel_name(void) {
     if (!g_solver) return "";
     return (g_sharded ? global_shard(0)->s : g_solver->s).kernel_name.c_str();
+}
+int get_cone_mode(void) {
+    if (!g_solver) return -1;
+    return (g_sharded ? global_shard(0)->s : g_solver->s).cone_mode;
 }
 
 int set_x0(double *x0_data, int x0_rows, int x0_cols, int verbose) {
@@ -1237,7 +1256,42 @@ int set_cone_constraints(int *Acu_data, int Acu_len, int *qcu_data, int qcu_len,
                          double *cx_data, int cx_len, int verbose) {
     (void)verbose;
     if (need_global("set_cone_constraints")) return -1;
-    if (Acu_len != qcu_len || Acu_len != cu_len || Acx_len != qcx_len || Acx_len != cx_len) {
+    if (Acu_len != qcu_len || Acx_len != qcx_len) {
+        set_error("set_cone_constraints: Ac, qc and c of one side must have the same length");
+        return -1;
+    }
+    // the batch dimension rides on the widths, as set_linear_constraints' does: cu of Acu_len*batch entries, [batch][cone] in
+    // memory, is one coefficient set per instance (+inf: a cone the instance does not have)
+    const int gb = global_batch();
+    const bool has_u = Acu_len > 0, has_x = Acx_len > 0;
+    const bool wide_u = has_u && gb > 1 && (long)cu_len == (long)Acu_len * gb, wide_x = has_x && gb > 1 && (long)cx_len == (long)Acx_len * gb;
+    if (wide_u || wide_x) {
+        if ((has_u && !wide_u) || (has_x && !wide_x)) {
+            set_error("set_cone_constraints: mixed widths — per-instance cones need every non-empty side per instance (cu with n*batch entries "
+                      "for n input cones, cx likewise); shared cones need n entries");
+            return -1;
+        }
+        if (g_sharded) {
+            if (g_solver->s.st.adaptive_rho) {
+                set_error("set_cone_constraints: per-instance cones are not available with adaptive rho");
+                return -1;
+            }
+            const int rc = guarded("set_cone_constraints", [&] {
+                return tinympc_sharded_set_instance_cones(g_sharded.get(), Acu_data, qcu_data, cu_data, Acu_len, Acx_data, qcx_data, cx_data, Acx_len);
+            });
+            if (rc == 0) {
+                // the master keeps the family-level state, which a later set_gpus / set_batch_size replays on fresh shards: the
+                // per-instance coefficients replace whatever shared set it held and do not survive a re-batch, so it holds no cones
+                g_solver->s.drop_instance_cones();
+                g_solver->s.ncx = g_solver->s.ncu = 0;
+                if (has_x) g_solver->s.st.en_state_soc = 1;
+                if (has_u) g_solver->s.st.en_input_soc = 1;
+            }
+            return rc;
+        }
+        return tinympc_set_instance_cones(g_solver.get(), Acu_data, qcu_data, cu_data, Acu_len, Acx_data, qcx_data, cx_data, Acx_len);
+    }
+    if (Acu_len != cu_len || Acx_len != cx_len) {
         set_error("set_cone_constraints: Ac, qc and c of one side must have the same length");
         return -1;
     }

@@ -461,6 +461,15 @@ const StreamEntry *find_stream_kernel(int nx, int nu) {
 hipError_t launch_generic(const AdmmParams &P, int precision, hipStream_t stream) {
     const int threads = 256;
     const int grid = (P.batch + threads - 1) / threads;
+    if (P.ic_cx || P.ic_cu) {   // per-instance cone coefficients: the `ic` forms (bounds and rows per instance as the `il` forms read them)
+        if (precision == 2)
+            hipLaunchKernelGGL((admm_generic_ic_kernel<double, double>), dim3(grid), dim3(threads), 0, stream, P);
+        else if (precision == 0)
+            hipLaunchKernelGGL((admm_generic_ic_kernel<double, float>), dim3(grid), dim3(threads), 0, stream, P);
+        else
+            hipLaunchKernelGGL((admm_generic_ic_kernel<float, float>), dim3(grid), dim3(threads), 0, stream, P);
+        return hipGetLastError();
+    }
     if (P.il_bx) {   // per-instance linear rows: the `il` forms (bounds read per instance as the `ib` forms do; fixed rho)
         if (precision == 2)
             hipLaunchKernelGGL((admm_generic_il_kernel<double, double>), dim3(grid), dim3(threads), 0, stream, P);

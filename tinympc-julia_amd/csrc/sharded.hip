@@ -273,6 +273,27 @@ int tinympc_sharded_set_instance_linear(tinympc_sharded *s, const double *Alin_x
     }
     return 0;
 }
+// per-instance cone coefficients over the WHOLE batch: the layout goes to every shard, the coefficients are contiguous per
+// instance, shard i takes [lo_i, hi_i)
+int tinympc_sharded_set_instance_cones(tinympc_sharded *s, const int *Acu, const int *qcu, const double *cu, int n_input_cones,
+                                       const int *Acx, const int *qcx, const double *cx, int n_state_cones) {
+    if (!s) return -1;
+    if (n_input_cones < 0 || n_state_cones < 0 || n_input_cones > 8 || n_state_cones > 8) {
+        set_error("set_instance_cones: at most 8 cones per knot and side");
+        return -1;
+    }
+    if ((n_input_cones > 0 && (!Acu || !qcu || !cu)) || (n_state_cones > 0 && (!Acx || !qcx || !cx))) {
+        set_error("set_instance_cones: null layout or coefficients");
+        return -1;
+    }
+    for (int i = 0; i < s->n(); ++i) {
+        const size_t lo = (size_t)s->lo[i];
+        if (tinympc_set_instance_cones(s->shard[i], Acu, qcu, n_input_cones ? cu + lo * n_input_cones : nullptr, n_input_cones, Acx, qcx,
+                                       n_state_cones ? cx + lo * n_state_cones : nullptr, n_state_cones))
+            return -1;
+    }
+    return 0;
+}
 static int sharded_set_ref(tinympc_sharded *s, bool is_x, const double *ref, int cols) {
     if (!s || !ref) return -1;
     const int kn = is_x ? s->N : s->N - 1, rows = is_x ? s->nx : s->nu;

@@ -162,6 +162,12 @@ struct StreamEntry {
     hipError_t (*launch_il)(const AdmmParams &, bool het, hipStream_t) = nullptr;
     const char *name_il = nullptr;
     size_t (*il_lds_bytes)(int mlx, int mlu) = nullptr;
+    // the per-instance-cones form (tinympc_set_instance_cones; the `il` form with the instance's own cone coefficients), the
+    // name it reports, "stream4<NX,NU;ic>", and the LDS bytes its coefficients take behind the rows' slice — null where the
+    // form is not built (sinst_ic_*.hip)
+    hipError_t (*launch_ic)(const AdmmParams &, bool het, hipStream_t) = nullptr;
+    const char *name_ic = nullptr;
+    size_t (*ic_lds_bytes)(int ncx, int ncu) = nullptr;
 };
 const StreamEntry *find_stream_kernel(int nx, int nu);
 // Per-instance families set up on the device (families_setup.hip; the rule: riccati.h).  The inputs are device pointers: A
@@ -249,6 +255,7 @@ struct BatchBuffers {
     DevBuf<double> d_ws64;                // precision 2: the fp64 workspace block (admm_generic.hip.h, Ws64)
     DevBuf<float> d_het_aux;
     DevBuf<float> d_ibx, d_ibu, d_il;     // per-instance bounds and rows in the kernels' layout
+    DevBuf<float> d_ic;                   // per-instance cone coefficients, [state cones | input cones][instance]
     DevBuf<float> d_sgc, d_svc, d_syc, d_szc;
     DevBuf<int> d_idx[2], d_count;        // chunked solves: the index lists of the instances still iterating
     DevBuf<float> d_lin, d_sgl, d_svl, d_syl, d_szl;
@@ -294,6 +301,20 @@ struct Solver : BatchBuffers {
     int set_instance_linear(const double *Ax, int mx, const double *bx, const double *Au, int mu, const double *bu);
     void drop_instance_linear();
     int upload_instance_linear();
+    // Cone coefficients PER INSTANCE (tinympc_set_instance_cones).  cone_mode 0: the shared set below (or none); 1: the layout
+    // below (ncx / ncu, Acx .. qcu) is the batch's and every instance has its own mu — ic_cx [batch][ncx], ic_cu [batch][ncu],
+    // the caller's fp64 arrays as given (they survive a change of precision or of the settings; cx[] / cu[] below then hold
+    // nothing the kernels read); d_ic holds them rounded and transposed to the kernels' layout (AdmmParams::ic_cx).  +inf: the
+    // instance does not have the cone; a side that is enabled carries its slack and dual for every instance, those without a
+    // cone on it included (so does a shared set whose cones never act).  Such a solver runs on the `ic` forms of the stream
+    // and generic kernels only, which are `il` forms: they read their bounds and their rows per instance (shared ones are
+    // uploaded replicated: upload_instance_bounds, upload_instance_linear).
+    int cone_mode = 0;
+    std::vector<double> ic_cx, ic_cu;
+    int set_instance_cones(const int *Acu, const int *qcu, const double *cu, int ncu, const int *Acx, const int *qcx,
+                           const double *cx, int ncx);
+    void drop_instance_cones();
+    int upload_instance_cones();
     // affine dynamics term and cone constraints (parity UNPINNED: they exist only in the absent
     // TinyMPC submodule; run on the stream kernel, or the generic one for shapes outside its grid)
     std::vector<double> fdyn;  // nx, all zero by default

@@ -165,15 +165,18 @@ int Solver::copy_family_state(const Solver &o) {
         set_error("copy_family_state: solvers of different shape");
         return -1;
     }
+    // per-instance rows and cone coefficients are per-instance inputs, not family state, on either side: this solver's own go
+    // first, and a source that carries them hands over no rows / no cones (its shared cx[] / cu[] hold nothing valid then)
+    drop_instance_linear();
+    drop_instance_cones();
     st = o.st;
     x_min = o.x_min, x_max = o.x_max, u_min = o.u_min, u_max = o.u_max;
     fdyn = o.fdyn, has_fdyn = o.has_fdyn;
-    ncx = o.ncx, ncu = o.ncu;
+    ncx = o.cone_mode ? 0 : o.ncx, ncu = o.cone_mode ? 0 : o.ncu;
     for (int i = 0; i < 8; ++i) {
         Acx[i] = o.Acx[i], qcx[i] = o.qcx[i], cx[i] = o.cx[i];
         Acu[i] = o.Acu[i], qcu[i] = o.qcu[i], cu[i] = o.cu[i];
     }
-    drop_instance_linear();   // (per-instance rows are per-instance inputs: they are not family state, on either side)
     mlx = o.lin_mode ? 0 : o.mlx, mlu = o.lin_mode ? 0 : o.mlu;
     lin_Ax = o.lin_Ax, lin_bx = o.lin_bx, lin_Au = o.lin_Au, lin_bu = o.lin_bu;
     lin_dirty = true;
@@ -517,7 +520,7 @@ Switches read_switches() {
 // lanes-per-instance family, its adaptive-rho variants included (precision = 1 — fp32 recurrences, asked for to save time —
 // stays here only where no matrix-core kernel exists, or with TINYMPC_HIP_STRICT_FP32: route_mfma)
 const KernelEntry *Solver::route_quad(bool rollout) const {
-    if (sw.no_quad || extensions_active() || hetero || bounds_mode || lin_mode) return nullptr;   // (per-instance bounds / rows: the pack holds one image)
+    if (sw.no_quad || extensions_active() || hetero || bounds_mode || lin_mode || cone_mode) return nullptr;   // (per-instance bounds / rows / cones: the pack holds one image)
     if (!st.adaptive_rho) {
         const KernelEntry *k = sw.group ? find_quad_kernel(nx, nu, N, sw.group) : nullptr;
         if (!k) k = select_quad_kernel(nx, nu, N, batch);
@@ -543,7 +546,7 @@ const KernelEntry *Solver::route_quad(bool rollout) const {
 // on the quad kernel), and the adaptive-rho variant (the instance's own Kinf as a correction to the shared products) where
 // the quad family has none
 const KernelEntry *Solver::route_mfma(bool rollout, const KernelEntry *quad) const {
-    if (strict_fp32() || sw.group || sw.no_mfma || sw.no_quad || bounds_mode || lin_mode) return nullptr;
+    if (strict_fp32() || sw.group || sw.no_mfma || sw.no_quad || bounds_mode || lin_mode || cone_mode) return nullptr;
     const KernelEntry *m = find_mfma_kernel(nx, nu, N);
     if (!m || (m->jit && sw.no_jit)) return nullptr;
     if (st.adaptive_rho)
@@ -567,6 +570,9 @@ const StreamEntry *Solver::route_stream() const {
     if (s2 && bounds_mode && (precision != 0 || !s2->launch_ib)) s2 = nullptr;
     // per-instance rows: the `il` form, the same three shapes; its rows take LDS behind the image
     if (s2 && lin_mode && (precision != 0 || !s2->launch_il || s2->lds_bytes(N, precision) + s2->il_lds_bytes(mlx, mlu) > 150 * 1024)) s2 = nullptr;
+    // per-instance cones: the `ic` form, the `il` form with the coefficients behind the rows
+    if (s2 && cone_mode && (precision != 0 || !s2->launch_ic || s2->lds_bytes(N, precision) + s2->il_lds_bytes(mlx, mlu) + s2->ic_lds_bytes(ncx, ncu) > 150 * 1024))
+        s2 = nullptr;
     return s2;
 }
 
@@ -574,7 +580,7 @@ const StreamEntry *Solver::route_stream() const {
 // affine term, cones, linear rows, cold or kept workspace.  One family, fixed rho, the whole batch in one launch (no
 // chunks): everything else stays on the generic kernel's fp64-state form.
 const StreamEntry *Solver::route_stream_f64() const {
-    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0 || bounds_mode || lin_mode) return nullptr;
+    if (!sw.stream_f64 || sw.no_stream || st.adaptive_rho || hetero || chunk_iters != 0 || bounds_mode || lin_mode || cone_mode) return nullptr;
     const StreamEntry *s2 = find_stream_kernel(nx, nu);
     if (!s2 || !s2->launch_f64) return nullptr;
     if (32.0 * batch * std::max(nx, nu) >= 4.0e9) return nullptr;   // 32-bit lane byte offsets, 8-byte elements
@@ -587,7 +593,7 @@ const StreamEntry *Solver::route_stream_f64() const {
 // against 5.5 on the quad kernel), else the LDS-resident one (mfmac, any horizon).  Only where a workspace-carrying
 // kernel exists to fall back to (`fallback`).
 const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stream) const {
-    if (bounds_mode || lin_mode) return nullptr;
+    if (bounds_mode || lin_mode || cone_mode) return nullptr;
     const ConeEntry *cn = sw.no_mfmar ? nullptr : find_cone_kernel(nx, nu, N);
     if (cn && cn->supports && !cn->supports(*this)) cn = nullptr;
     const bool plain_ok = sw.mfmac_all || (cn != nullptr && cn->plain);
@@ -605,7 +611,7 @@ const ConeEntry *Solver::route_cone(bool rollout, bool have_quad, bool have_stre
 // transposed-sets matrix-core kernel: every kind of solve (one-shot, warm-started, workspace kept, chunked, the fused closed
 // loop) of a shape that has it, with the affine term / at most one cone per side (box-only problems where the entry says so)
 const ConeEntry *Solver::route_trans(bool rollout, const ConeEntry *oneshot) const {
-    if (sw.no_mfmat || sw.no_mfma || sw.group || bounds_mode || lin_mode) return nullptr;
+    if (sw.no_mfmat || sw.no_mfma || sw.group || bounds_mode || lin_mode || cone_mode) return nullptr;
     if (strict_fp32() || hetero || st.adaptive_rho || (rollout && refs_per_instance() && ref_seq_steps > 0) || st.max_iter < 1 || (double)batch * ex() >= 2.0e9)
         return nullptr;
     const ConeEntry *ct = find_trans_kernel(nx, nu, N);
@@ -640,7 +646,7 @@ std::vector<long> Solver::routing_key(bool rollout) const {
             cache_overridden, refs_device_owned, xref_kind, uref_kind, ref_mode, adapt_pure, adapt_dirty, ref_seq_steps,
             st.max_iter < 1, st.en_state_soc, st.en_input_soc, ncx, ncu, Acx[0], qcx[0], Acu[0], qcu[0], mlx, mlu, rollout, strict_precision,
             (long)route_gen, Acx[1], qcx[1], Acu[1], qcu[1], st.en_state_linear, st.en_input_linear,
-            extensions_active() && bounds_vary_by_knot(), layout_final, bounds_mode, lin_mode};   // (a unit specialised at setup is compiled for one bound kind)
+            extensions_active() && bounds_vary_by_knot(), layout_final, bounds_mode, lin_mode, cone_mode};   // (a unit specialised at setup is compiled for one bound kind)
 }
 
 int Solver::select_kernel(bool rollout) {
@@ -652,6 +658,10 @@ int Solver::select_kernel(bool rollout) {
     }
     if (st.adaptive_rho && bounds_mode) {
         set_error("adaptive_rho is not available with per-instance bounds (set_instance_bounds); shared bounds (set_bound_constraints) drop them");
+        return -1;
+    }
+    if (st.adaptive_rho && cone_mode) {
+        set_error("adaptive_rho is not available with per-instance cones (set_instance_cones); shared cones (set_cone_constraints) drop them");
         return -1;
     }
     if (st.adaptive_rho && lin_mode) {
@@ -672,7 +682,7 @@ int Solver::select_kernel(bool rollout) {
         // with the packs, from the extensions as they are now, also where the entries stay what they were)
         packs_dirty = true;
         ke = nullptr, se = s2, ce = nullptr;
-        kernel_name = se ? se->name_f64 : (lin_mode ? "generic<f64;il>" : (bounds_mode ? "generic<f64;ib>" : "generic<f64>"));
+        kernel_name = se ? se->name_f64 : (cone_mode ? "generic<f64;ic>" : lin_mode ? "generic<f64;il>" : (bounds_mode ? "generic<f64;ib>" : "generic<f64>"));
         routed_key = std::move(key);
         routed = true;
         return 0;
@@ -684,7 +694,8 @@ int Solver::select_kernel(bool rollout) {
     }
     const StreamEntry *s2 = k ? nullptr : route_stream();
     if (hetero && !s2) {
-        set_error(lin_mode ? "per-instance families with per-instance linear rows need the stream kernel's il form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
+        set_error(cone_mode ? "per-instance families with per-instance cones need the stream kernel's ic form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
+                  lin_mode ? "per-instance families with per-instance linear rows need the stream kernel's il form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
                   bounds_mode ? "per-instance families with per-instance bounds need the stream kernel's ib form: (nx, nu) in {(4,1), (6,3), (12,4)}, precision 0" :
                   "per-instance families need a stream-kernel instantiation for (nx, nu) (nx in {2,3,4,6,8,10,12}, nu <= 4)");
         return -1;
@@ -694,7 +705,7 @@ int Solver::select_kernel(bool rollout) {
     if (c2) k = nullptr, s2 = nullptr;
     if (k != ke || s2 != se || c2 != ce) packs_dirty = true;
     ke = k, se = s2, ce = c2;
-    kernel_name = ke ? ke->name : (se ? (lin_mode ? se->name_il : (bounds_mode ? se->name_ib : se->name)) : (ce ? ce->name : (lin_mode ? "generic<il>" : (bounds_mode ? "generic<ib>" : "generic"))));
+    kernel_name = ke ? ke->name : (se ? (cone_mode ? se->name_ic : lin_mode ? se->name_il : (bounds_mode ? se->name_ib : se->name)) : (ce ? ce->name : (cone_mode ? "generic<ic>" : lin_mode ? "generic<il>" : (bounds_mode ? "generic<ib>" : "generic"))));
     routed_key = std::move(key);
     routed = true;
     return 0;
@@ -713,6 +724,7 @@ int Solver::alloc_batch(int batch_) {
     free_batch();
     drop_instance_bounds();   // (per-instance inputs do not survive a re-batch: back to the shared bounds)
     drop_instance_linear();   // (... and to no rows)
+    drop_instance_cones();    // (... and to no cones)
     drop_own_plant();         // (... and back to the model plant)
     (void)drop_ref_trajectory(false);   // (... and to the references set below)
     drop_noise();             // (... and no noise: a factor may be per instance)
@@ -800,8 +812,9 @@ int Solver::upload_packs() {
                 state_bounds_active = true;
                 break;
             }
-    if ((bounds_mode || lin_mode) && upload_instance_bounds()) return -1;   // (the `il` forms read their bounds per instance too)
-    if (lin_mode && !d_il && upload_instance_linear()) return -1;
+    if ((bounds_mode || lin_mode || cone_mode) && upload_instance_bounds()) return -1;   // (the `il` and `ic` forms read their bounds per instance too)
+    if ((lin_mode || cone_mode) && !d_il && upload_instance_linear()) return -1;              // (... and the `ic` forms their rows)
+    if (cone_mode && !d_ic && upload_instance_cones()) return -1;
     std::vector<unsigned char> coef;
     std::vector<float> bnd;
     if (ke) {
@@ -828,7 +841,7 @@ int Solver::upload_packs() {
     // precision 2 (the generic kernel's fp64-state form, one lane per instance like this one): one-shot solves of a shape the lean
     // kernel holds run on ITS fp64-state form, specialised on request — the reference's digits at the headline kernel's speed
     // (`se` at precision 2 is the stream kernel's fp64-state form: it takes what the lean kernel leaves)
-    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise && !bounds_mode && !lin_mode) lean_jit = true;
+    if (precision == 2 && !ke && !ce && !hetero && !extensions_active() && lean_enabled && !sw.no_jit && !no_specialise && !bounds_mode && !lin_mode && !cone_mode) lean_jit = true;
     std::fill(le_var_tried, le_var_tried + LV_COUNT, false);
     lean_ok = false;
     lean_scaled_ok = false;
@@ -1024,7 +1037,7 @@ void Solver::drop_instance_bounds() {
 }
 
 // the host copies, narrowed to fp32 and transposed from the API's instance-major layout to [min | max][knot][instance][row].
-// A solver with shared bounds and per-instance rows (bounds_mode 0 under lin_mode) uploads the shared set replicated: one
+// A solver with shared bounds and per-instance rows or cones (bounds_mode 0 under lin_mode / cone_mode) uploads the shared set replicated: one
 // line per instance, constant over the horizon — or per knot, where the shared bounds differ between knots.
 int Solver::upload_instance_bounds() {
     HIP_TRY(hipSetDevice(device));
@@ -1110,7 +1123,7 @@ void Solver::drop_instance_linear() {
     il_Ax.clear(), il_bx.clear(), il_Au.clear(), il_bu.clear();
     lin_Ax.clear(), lin_bx.clear(), lin_Au.clear(), lin_bu.clear();
     d_il.free();
-    if (!bounds_mode) {
+    if (!bounds_mode && !cone_mode) {
         d_ibx.free();
         d_ibu.free();
     }
@@ -1122,27 +1135,30 @@ void Solver::drop_instance_linear() {
 // the host copies, rounded as the shared pack rounds them ((float)a, (float)b, (float) of the fp64 sum of squares of the
 // unrounded entries) and laid out as the kernels read them: Ax [row][instance][nx] | Au [row][instance][nu] | bx | |ax|^2 | bu |
 // |au|^2, each [row][instance].  An all-zero row: a = 0, b = FLT_MAX, |a|^2 = 1 — `dot > b` never holds.
+// A solver with shared rows and per-instance cones (lin_mode 0 under cone_mode) uploads the shared set (row-major, lin_Ax ..
+// lin_bu) replicated, every row of either side, switched on or not, as the per-instance ones are.
 int Solver::upload_instance_linear() {
     HIP_TRY(hipSetDevice(device));
     const size_t Bn = (size_t)batch, nax = (size_t)mlx * Bn * nx, nau = (size_t)mlu * Bn * nu;
-    std::vector<float> h(nax + nau + 2 * Bn * (mlx + mlu));
+    const bool rep = !lin_mode;
+    std::vector<float> h(std::max<size_t>(nax + nau + 2 * Bn * (mlx + mlu), 1));   // (no rows at all: one word, so that the pointer exists)
     auto put = [&](const std::vector<double> &A, const std::vector<double> &bv, size_t m, size_t n, float *a, float *rb, float *rn2) {
         for (size_t b = 0; b < Bn; ++b)
             for (size_t k = 0; k < m; ++k) {
                 double n2 = 0.0;
                 for (size_t j = 0; j < n; ++j) {
-                    const double v = A[b * m * n + k + j * m];
+                    const double v = rep ? A[k * n + j] : A[b * m * n + k + j * m];
                     a[(k * Bn + b) * n + j] = (float)v;
                     n2 += v * v;
                 }
                 const bool absent = !(n2 > 0.0);
-                rb[k * Bn + b] = absent ? FLT_MAX : (float)bv[b * m + k];
+                rb[k * Bn + b] = absent ? FLT_MAX : (float)bv[(rep ? 0 : b * m) + k];
                 rn2[k * Bn + b] = absent ? 1.f : (float)n2;
             }
     };
     float *bx = h.data() + nax + nau, *n2x = bx + Bn * mlx, *bu = n2x + Bn * mlx, *n2u = bu + Bn * mlu;
-    put(il_Ax, il_bx, (size_t)mlx, (size_t)nx, h.data(), bx, n2x);
-    put(il_Au, il_bu, (size_t)mlu, (size_t)nu, h.data() + nax, bu, n2u);
+    put(rep ? lin_Ax : il_Ax, rep ? lin_bx : il_bx, (size_t)mlx, (size_t)nx, h.data(), bx, n2x);
+    put(rep ? lin_Au : il_Au, rep ? lin_bu : il_bu, (size_t)mlu, (size_t)nu, h.data() + nax, bu, n2u);
     return d_il.upload(h);
 }
 
@@ -1157,6 +1173,114 @@ int Solver::set_fdyn(const double *f) {
     packs_dirty = true;
     plant_dirty = true;   // (the chained closed loop's plant carries f)
     return select_kernel() || ensure_extension_buffers();
+}
+
+// Cone coefficients PER INSTANCE.  The layout (Acu, qcu, Acx, qcx) is one for the batch; cu is [batch][ncu], cx [batch][ncx]: mu
+// of every cone for every instance, +inf for a cone the instance does not have.  Enables the non-empty sides, as set_cones
+// does; the solver leaves the on-chip families for the stream / generic kernels' `ic` forms (select_kernel).  Both sides
+// empty: no cones at all, shared mode.
+int Solver::set_instance_cones(const int *Acu_, const int *qcu_, const double *cu_, int ncu_, const int *Acx_, const int *qcx_,
+                               const double *cx_, int ncx_) {
+    if (ncu_ < 0 || ncx_ < 0 || ncu_ > 8 || ncx_ > 8) {
+        set_error("set_instance_cones: at most 8 cones per knot and side");
+        return -1;
+    }
+    if ((ncu_ > 0 && (!Acu_ || !qcu_ || !cu_)) || (ncx_ > 0 && (!Acx_ || !qcx_ || !cx_))) {
+        set_error("set_instance_cones: null layout or coefficients");
+        return -1;
+    }
+    for (int i = 0; i < ncu_; ++i)
+        if (Acu_[i] < 0 || qcu_[i] < 2 || Acu_[i] + qcu_[i] > nu) {
+            set_error("set_instance_cones: input cone out of range (need 0 <= Ac, qc >= 2, Ac + qc <= nu)");
+            return -1;
+        }
+    for (int i = 0; i < ncx_; ++i)
+        if (Acx_[i] < 0 || qcx_[i] < 2 || Acx_[i] + qcx_[i] > nx) {
+            set_error("set_instance_cones: state cone out of range (need 0 <= Ac, qc >= 2, Ac + qc <= nx)");
+            return -1;
+        }
+    const size_t Bn = (size_t)batch;
+    // (+inf: absent; NaN, -inf, <= 0 refused, and so is a finite value that fp32 would round to 0 or to +inf.  Non-finite values
+    // are told by their bits: this file is compiled with -fno-honor-nans, under which a comparison does not see a NaN)
+    auto bad = [](double mu) {
+        uint64_t u;
+        std::memcpy(&u, &mu, sizeof u);
+        if (((u >> 52) & 0x7ffu) == 0x7ffu) return u != 0x7ff0000000000000ull;   // only +inf passes
+        const float f = (float)mu;
+        return !(f > 0.f) || f > FLT_MAX;
+    };
+    for (size_t i = 0; i < Bn * ncu_; ++i)
+        if (bad(cu_[i])) {
+            set_error("set_instance_cones: mu must be positive and finite, or +inf for a cone the instance does not have (input side)");
+            return -1;
+        }
+    for (size_t i = 0; i < Bn * ncx_; ++i)
+        if (bad(cx_[i])) {
+            set_error("set_instance_cones: mu must be positive and finite, or +inf for a cone the instance does not have (state side)");
+            return -1;
+        }
+    if (st.adaptive_rho) {
+        set_error("set_instance_cones: per-instance cones are not available with adaptive rho");
+        return -1;
+    }
+    if (ncu_ == 0 && ncx_ == 0) return set_cones(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+    if (wait_last_launch()) return -1;
+    // what a refusal puts back
+    const int o_mode = cone_mode, o_ncx = ncx, o_ncu = ncu, o_ss = st.en_state_soc, o_is = st.en_input_soc;
+    int o_Acx[8], o_qcx[8], o_Acu[8], o_qcu[8];
+    for (int i = 0; i < 8; ++i) o_Acx[i] = Acx[i], o_qcx[i] = qcx[i], o_Acu[i] = Acu[i], o_qcu[i] = qcu[i];
+    std::vector<double> o_cx, o_cu;
+    o_cx.swap(ic_cx), o_cu.swap(ic_cu);
+    route_gen += 1;
+    cone_mode = 1;
+    ncx = ncx_, ncu = ncu_;
+    for (int i = 0; i < ncu; ++i) Acu[i] = Acu_[i], qcu[i] = qcu_[i];
+    for (int i = 0; i < ncx; ++i) Acx[i] = Acx_[i], qcx[i] = qcx_[i];
+    ic_cu.assign(cu_, cu_ + (ncu ? Bn * ncu : 0));
+    ic_cx.assign(cx_, cx_ + (ncx ? Bn * ncx : 0));
+    if (ncu > 0) st.en_input_soc = 1;
+    if (ncx > 0) st.en_state_soc = 1;
+    packs_dirty = true;
+    if (select_kernel() || ensure_extension_buffers() || upload_instance_cones()) {   // (no kernel takes the combination: the solver stays as it was)
+        const std::string why = last_error();
+        cone_mode = o_mode, ncx = o_ncx, ncu = o_ncu, st.en_state_soc = o_ss, st.en_input_soc = o_is;
+        for (int i = 0; i < 8; ++i) Acx[i] = o_Acx[i], qcx[i] = o_qcx[i], Acu[i] = o_Acu[i], qcu[i] = o_qcu[i];
+        ic_cx.swap(o_cx), ic_cu.swap(o_cu);
+        route_gen += 1;
+        d_ic.free();   // (re-made from the host copies at the next upload_packs where they are still per instance)
+        (void)select_kernel();
+        set_error(why);
+        return -1;
+    }
+    return 0;
+}
+
+void Solver::drop_instance_cones() {
+    if (!cone_mode) return;
+    (void)wait_last_launch();
+    cone_mode = 0;
+    ncx = ncu = 0;   // (the shared cx / cu hold no coefficient while the per-instance ones are installed)
+    ic_cx.clear(), ic_cu.clear();
+    d_ic.free();
+    if (!lin_mode) d_il.free();
+    if (!bounds_mode && !lin_mode) {
+        d_ibx.free();
+        d_ibu.free();
+    }
+    route_gen += 1;
+    packs_dirty = true;
+}
+
+// the host copies, rounded to fp32 as the shared set's are and transposed to [cone][instance], state cones then input cones
+int Solver::upload_instance_cones() {
+    HIP_TRY(hipSetDevice(device));
+    const size_t Bn = (size_t)batch;
+    std::vector<float> h(Bn * (ncx + ncu));
+    for (size_t b = 0; b < Bn; ++b) {
+        for (int c = 0; c < ncx; ++c) h[(size_t)c * Bn + b] = (float)ic_cx[b * ncx + c];
+        for (int c = 0; c < ncu; ++c) h[((size_t)ncx + c) * Bn + b] = (float)ic_cu[b * ncu + c];
+    }
+    return d_ic.upload(h);
 }
 
 int Solver::set_cones(const int *Acu_, const int *qcu_, const double *cu_, int ncu_, const int *Acx_,
@@ -1176,6 +1300,7 @@ int Solver::set_cones(const int *Acu_, const int *qcu_, const double *cu_, int n
             set_error("set_cone_constraints: state cone out of range (need 0 <= Ac, qc >= 2, Ac + qc <= nx, mu > 0)");
             return -1;
         }
+    drop_instance_cones();   // the shared set replaces a per-instance one
     ncu = ncu_;
     ncx = ncx_;
     for (int i = 0; i < ncu; ++i) {
@@ -1224,6 +1349,10 @@ int Solver::set_linear(const double *Ax, int mx, const double *bx, const double 
     if (!take(Ax, bx, mx, nx, ax, bxv) || !take(Au, bu, mu, nu, au, buv)) {
         set_error("set_linear_constraints: a constraint row is all zero");
         return -1;
+    }
+    if (cone_mode) {   // (the `ic` forms read the shared rows replicated: upload_instance_linear at the next upload_packs)
+        (void)wait_last_launch();
+        d_il.free();
     }
     mlx = mx;
     mlu = mu;
@@ -1387,6 +1516,8 @@ Solver::RolloutPlan Solver::plan_rollout(int mpc_steps) {
         if (precision == 2 && !sw.stream_mpc && !own_plant())
             return refuse("mpc_rollout: a reference sequence is not available at precision 2 (which has no fused closed loop; step it from the host)");
     }
+    if (cone_mode && !sw.stream_mpc && !(own_plant() || traj_kind))
+        return refuse("mpc_rollout: per-instance cones have no closed loop by default (a plant of its own, or TINYMPC_HIP_STREAM_MPC=1, gives one as a chain of launches; or step it from the host)");
     if (lin_mode && !sw.stream_mpc && !(own_plant() || traj_kind))
         return refuse("mpc_rollout: per-instance linear rows have no closed loop by default (a plant of its own, or TINYMPC_HIP_STREAM_MPC=1, gives one as a chain of launches; or step it from the host)");
     if (bounds_mode && !sw.stream_mpc)
@@ -1630,13 +1761,17 @@ void Solver::fill_params(AdmmParams &P, const Pass &a) const {
     P.ws64 = d_ws64;
     P.abs_pri_tol64 = st.abs_pri_tol;
     P.abs_dua_tol64 = st.abs_dua_tol;
-    if (bounds_mode || lin_mode) {   // (ib_by_knot: upload_instance_bounds — bounds_mode 2, or shared bounds that differ between knots under lin_mode)
+    if (bounds_mode || lin_mode || cone_mode) {   // (ib_by_knot: upload_instance_bounds — bounds_mode 2, or shared bounds that differ between knots under lin_mode / cone_mode)
         P.ibx = d_ibx, P.ibu = d_ibu;
         P.ib_kx = ib_by_knot ? (long)batch * nx : 0, P.ib_ku = ib_by_knot ? (long)batch * nu : 0;
         P.ib_hx = (long)batch * nx * (ib_by_knot ? N : 1), P.ib_hu = (long)batch * nu * (ib_by_knot ? N - 1 : 1);
         P.ib_on = (st.en_state_bound ? IB_STATE : 0) | (st.en_input_bound ? IB_INPUT : 0);
     }
-    if (lin_mode) {
+    if (cone_mode) {
+        P.ic_cx = d_ic, P.ic_cu = P.ic_cx + (long)ncx * batch;
+        P.ic_rc = batch;
+    }
+    if (lin_mode || cone_mode) {
         const long Bn = batch;
         P.il_ax = d_il, P.il_au = P.il_ax + (long)mlx * Bn * nx;
         P.il_bx = P.il_au + (long)mlu * Bn * nu, P.il_n2x = P.il_bx + Bn * mlx, P.il_bu = P.il_n2x + Bn * mlx, P.il_n2u = P.il_bu + Bn * mlu;
@@ -1680,7 +1815,7 @@ Solver::Pick Solver::pick_kernel(const Pass &a) {
         if (!le_var_tried[v]) le_var[v] = jit_lean_for(nx, nu, N, v, k.plan.form == LF_SPARSE ? k.plan.sp : 0, verbose), le_var_tried[v] = true;
         k.lean = le_var[v];
     }
-    k.stream_loop = a.stream_loop && !k.lean && se && !bounds_mode && !lin_mode && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);   // (no `ib` loop form)
+    k.stream_loop = a.stream_loop && !k.lean && se && !bounds_mode && !lin_mode && !cone_mode && se->launch_mpc && se->has_mpc(precision, stream_ext(), hetero);   // (no `ib` loop form)
     return k;
 }
 
@@ -1731,6 +1866,7 @@ int Solver::launch_pass(hipStream_t stream, const Pass &a) {
                    : (ce ? ce->launch(P, cones_active(), ce->lds_bytes(*this), stream)
                          : (se ? (sloop ? se->launch_mpc(P, precision, stream_ext(), hetero, stream)
                                         : (precision == 2 ? se->launch_f64(P, stream_ext(), stream)
+                                                          : cone_mode ? se->launch_ic(P, hetero, stream)
                                                           : lin_mode ? se->launch_il(P, hetero, stream)
                                                           : (bounds_mode ? se->launch_ib(P, stream_ext(), hetero, stream)
                                                                          : se->launch(P, precision, stream_ext(), hetero, stream))))

@@ -322,6 +322,42 @@ hipError_t launch_streamg_il(const AdmmParams &P, bool het, hipStream_t stream) 
     return hipGetLastError();
 }
 
+// LDS bytes the per-instance-cones form adds to the rows' slice: per group, behind its b and |a|^2, the coefficients of its
+// instance's cones, state cones then input cones (admm_streamg_ic_kernel)
+template <int NX, int NU, int G>
+size_t streamg_ic_lds_bytes(int ncx, int ncu) {
+    return 4 * (size_t)(256 / G) * (ncx + ncu);
+}
+
+// The per-instance-cones form (admm_streamg_ic_kernel: the `il` form whose cone coefficients are the instance's own, P.ic_cx /
+// P.ic_cu): one family or one per instance x OS, four kernels per (nx, nu).
+template <int NX, int NU, int G>
+hipError_t launch_streamg_ic(const AdmmParams &P, bool het, hipStream_t stream) {
+    const int grid = (P.batch + 256 / G - 1) / (256 / G);
+    const size_t lds = streamg_lds_bytes<NX, NU, G>(P.N, 0) + streamg_il_lds_bytes<NX, NU, G>(P.mlx, P.mlu) +
+                       streamg_ic_lds_bytes<NX, NU, G>(P.ncx, P.ncu);
+    const bool oneshot = P.cold_start && !P.save_state;
+#define TMPC_LAUNCH(HET_, OS_)                                                                                  \
+    do {                                                                                                        \
+        if (lds > 48 * 1024)                                                                                    \
+            (void)hipFuncSetAttribute((const void *)admm_streamg_ic_kernel<NX, NU, G, HET_, OS_>,               \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
+        hipLaunchKernelGGL((admm_streamg_ic_kernel<NX, NU, G, HET_, OS_>), dim3(grid), dim3(256), lds, stream, P); \
+    } while (0)
+    if (het) {
+        if (oneshot) TMPC_LAUNCH(true, true); else TMPC_LAUNCH(true, false);
+    } else {
+        if (oneshot) TMPC_LAUNCH(false, true); else TMPC_LAUNCH(false, false);
+    }
+#undef TMPC_LAUNCH
+    return hipGetLastError();
+}
+
+// the per-instance-cones launcher of a shape, in a translation unit of its own (sinst_ic_*.hip)
+#define TMPC_DEFINE_STREAMG_IC(NX, NU, GG)                                                               \
+    hipError_t launch_stream##GG##_ic_##NX##_##NU(const AdmmParams &P, bool het, hipStream_t stream) {   \
+        return launch_streamg_ic<NX, NU, GG>(P, het, stream);                                            \
+    }
 // the per-instance-rows launcher of a shape, in a translation unit of its own (sinst_il_*.hip)
 #define TMPC_DEFINE_STREAMG_IL(NX, NU, GG)                                                               \
     hipError_t launch_stream##GG##_il_##NX##_##NU(const AdmmParams &P, bool het, hipStream_t stream) {   \
@@ -343,13 +379,14 @@ hipError_t launch_streamg_il(const AdmmParams &P, bool het, hipStream_t stream) 
         return launch_streamg_f64<NX, NU, GG>(P, ext, stream);                                                \
     }
 // ... and the entry of a shape that has one: TMPC_DEFINE_STREAMG_ENTRY plus that launcher and its reported name — and, the same
-// three shapes having them, the loop launcher (sinst_mpc_*.hip), the per-instance-bounds launcher (sinst_ib_*.hip) and the
-// per-instance-rows launcher (sinst_il_*.hip)
+// three shapes having them, the loop launcher (sinst_mpc_*.hip), the per-instance-bounds launcher (sinst_ib_*.hip), the
+// per-instance-rows launcher (sinst_il_*.hip) and the per-instance-cones launcher (sinst_ic_*.hip)
 #define TMPC_DEFINE_STREAMG_ENTRY_F64(NX, NU, GG)                                                                   \
     hipError_t launch_stream##GG##_f64_##NX##_##NU(const AdmmParams &, int, hipStream_t);                          \
     hipError_t launch_stream##GG##_mpc_##NX##_##NU(const AdmmParams &, int, int, bool, hipStream_t);               \
     hipError_t launch_stream##GG##_ib_##NX##_##NU(const AdmmParams &, int, bool, hipStream_t);                     \
     hipError_t launch_stream##GG##_il_##NX##_##NU(const AdmmParams &, bool, hipStream_t);                          \
+    hipError_t launch_stream##GG##_ic_##NX##_##NU(const AdmmParams &, bool, hipStream_t);                          \
     const StreamEntry *stream##GG##_entry_##NX##_##NU() {                                                          \
         static const StreamEntry e = {NX, NU, GG, "stream" #GG "<" #NX "," #NU ">", &build_streamg_coef<NX, NU, GG>, \
                                       &build_streamg_bounds<NX, NU, GG>, &streamg_lds_bytes<NX, NU, GG>,           \
@@ -358,7 +395,9 @@ hipError_t launch_streamg_il(const AdmmParams &P, bool het, hipStream_t stream) 
                                       &launch_stream##GG##_mpc_##NX##_##NU, &streamg_mpc_has<NX, NU>,              \
                                       &launch_stream##GG##_ib_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";ib>",    \
                                       &launch_stream##GG##_il_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";il>",    \
-                                      &streamg_il_lds_bytes<NX, NU, GG>};                                          \
+                                      &streamg_il_lds_bytes<NX, NU, GG>,                                           \
+                                      &launch_stream##GG##_ic_##NX##_##NU, "stream" #GG "<" #NX "," #NU ";ic>",    \
+                                      &streamg_ic_lds_bytes<NX, NU, GG>};                                          \
         return &e;                                                                                                 \
     }
 

@@ -19,7 +19,7 @@ module TinyMPC
 # mirror (tinympc-julia_amd/tinympc.py) in tests/.  INTEGRATION.md shows the two-line change that
 # makes the reference's own src/TinyMPC.jl use this library without adopting this module.
 
-export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds, set_instance_linear, setup_families, set_families!, family_cache, families_setup_mode,
+export TinyMPCSolver, setup, solve, get_solution, get_solution!, pin_host!, unpin_host!, get_status, set_x0, set_x_ref, set_u_ref, set_ref_sequence, mpc_rollout, set_plant, set_disturbance, plant_mode, set_ref_trajectory, set_ref_cursor, ref_cursor, set_process_noise, set_measurement_noise, set_noise_cursor, noise_cursor, noise_mode, get_noise, host_noise, set_estimator, set_estimator_state, estimator_mode, get_estimator_state, host_estimator_step, kalman_gain, set_rollout_metrics, reset_rollout_metrics, get_rollout_metrics, get_rollout_summary, METRIC_NAMES, set_instance_bounds, set_instance_linear, set_instance_cones!, setup_families, set_families!, family_cache, families_setup_mode,
        set_bound_constraints, set_linear_constraints, set_equality_constraints, set_cone_constraints, update_settings,
        set_cache_terms, set_batch_size, set_gpus, get_gpus, set_warm_start, set_precision, kernel_name, reset_workspace, print_problem_data,
        compute_sensitivity_autograd, set_sensitivity, get_adaptive_rho
@@ -199,6 +199,8 @@ function set_warm_start(solver::TinyMPCSolver, on::Bool)
     return 0
 end
 kernel_name() = unsafe_string(ccall((:get_kernel_name, _lib_path()), Cstring, ()))
+# 0: no cones or cones shared by the batch, 1: a coefficient per instance (set_instance_cones!)
+cone_mode() = Int(ccall((:get_cone_mode, _lib_path()), Int32, ()))
 
 # x0: Vector (length nx, broadcast to the batch) or Matrix (nx, batch)
 function set_x0(solver::TinyMPCSolver, x0::AbstractVecOrMat{Float64}; verbose::Bool=false)
@@ -709,6 +711,24 @@ function set_cone_constraints(solver::TinyMPCSolver, Acu::Vector{Int32}, qcu::Ve
               Acu, length(Acu), qcu, length(qcu), cu, length(cu),
               Acx, length(Acx), qcx, length(qcx), cx, length(cx), _flag(verbose)),
         "Failed to set cone constraints")
+end
+
+# cone coefficients PER INSTANCE over one layout, batch > 1: Acu, qcu (n_u) with cu (n_u, batch), Acx, qcx (n_x) with cx (n_x, batch);
+# an empty side is Int32[] with zeros(0, batch); Inf is a cone that instance does not have.  The batch dimension rides on the
+# widths of the process-global entry point, [batch][cone] in memory, as for set_instance_linear.  The solver then runs on the
+# `ic` form of the stream or the generic kernel (kernel_name()); the shared method above returns it to shared cones.  Not with
+# adaptive rho; mpc_rollout only as a chain of launches.
+# (Written and not executed, like the rest of this file: no Julia on the build machine.)
+function set_instance_cones!(solver::TinyMPCSolver, Acu::Vector{Int32}, qcu::Vector{Int32}, cu::Matrix{Float64},
+                             Acx::Vector{Int32}, qcx::Vector{Int32}, cx::Matrix{Float64}; verbose::Bool=false)
+    _need(solver)
+    cuv, cxv = vec(cu), vec(cx)    # column-major (cone, batch) is [batch][cone] in memory
+    _ok(ccall((:set_cone_constraints, _lib_path()), Int32,
+              (Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Int32,
+               Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Int32),
+              Acu, length(Acu), qcu, length(qcu), cuv, length(cuv),
+              Acx, length(Acx), qcx, length(qcx), cxv, length(cxv), _flag(verbose)),
+        "Failed to set per-instance cone constraints")
 end
 
 function set_cache_terms(solver::TinyMPCSolver, Kinf::Matrix{Float64}, Pinf::Matrix{Float64},

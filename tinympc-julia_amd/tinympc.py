@@ -61,6 +61,7 @@ SIGNATURES = {
     "get_adaptive_rho": (c_int, [c_dp, c_ip]),
     "set_warm_start": (c_int, [c_int]),
     "get_kernel_name": (ctypes.c_char_p, []),
+    "get_cone_mode": (c_int, []),
     "print_problem_data": (c_int, [c_int]),
     "set_linear_constraints": (c_int, [c_dp, c_int, c_int, c_dp, c_int, c_dp, c_int, c_int, c_dp,
                                        c_int, c_int]),
@@ -101,6 +102,8 @@ SIGNATURES = {
     "tinympc_enable_linear": (c_int, [c_vp, c_int, c_int]),
     "tinympc_set_instance_linear": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_int, c_dp]),
     "tinympc_lin_mode": (c_int, [c_vp]),
+    "tinympc_set_instance_cones": (c_int, [c_vp, c_ip, c_ip, c_dp, c_int, c_ip, c_ip, c_dp, c_int]),
+    "tinympc_cone_mode": (c_int, [c_vp]),
     "tinympc_set_x0": (c_int, [c_vp, c_dp, c_int]),
     "tinympc_set_x_ref": (c_int, [c_vp, c_dp, c_int]),
     "tinympc_set_u_ref": (c_int, [c_vp, c_dp, c_int]),
@@ -219,6 +222,7 @@ SIGNATURES = {
     "tinympc_sharded_set_bound_constraints": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "tinympc_sharded_set_instance_bounds": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_int]),
     "tinympc_sharded_set_instance_linear": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_int, c_dp]),
+    "tinympc_sharded_set_instance_cones": (c_int, [c_vp, c_ip, c_ip, c_dp, c_int, c_ip, c_ip, c_dp, c_int]),
     "tinympc_sharded_set_warm_start": (c_int, [c_vp, c_int]),
     "tinympc_sharded_reset": (c_int, [c_vp]),
     "tinympc_sharded_set_precision": (c_int, [c_vp, c_int]),
@@ -355,6 +359,11 @@ def set_warm_start(solver, on):
 def kernel_name():
     """the kernel the global solver's last solve ran on"""
     return load_library().get_kernel_name().decode()
+
+
+def cone_mode():
+    """0 no cones or cones shared by the batch, 1 a coefficient per instance (the global solver; -1 without one)"""
+    return int(load_library().get_cone_mode())
 
 
 def set_batch_size(solver, batch):
@@ -988,10 +997,26 @@ def set_equality_constraints(solver, Aeq_x, beq_x, Aeq_u=None, beq_u=None):
                                   np.vstack([Au, -Au]), np.concatenate([bu, -bu]))
 
 
+def _instance_cones(Ac, qc, c, batch):
+    """one side of set_instance_cones: the layout (n,) and the coefficients (n, B), in the library's layout [B][n]; an empty
+    side (None, or no cone) gives 0 cones"""
+    if Ac is None or np.asarray(Ac).size == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0), 0
+    Ac = np.ascontiguousarray(np.asarray(Ac, dtype=np.int32).ravel())
+    qc = np.ascontiguousarray(np.asarray(qc, dtype=np.int32).ravel())
+    c = np.asarray(c, dtype=np.float64)
+    if len(qc) != len(Ac) or c.shape != (len(Ac), batch):
+        raise TinyMPCError(f"set_instance_cones: expected Ac, qc of one length n and coefficients ({len(Ac)}, {batch})")
+    return Ac, qc, np.ascontiguousarray(c.T).reshape(-1), len(Ac)
+
+
 def set_cone_constraints(solver, Acu, qcu, cu, Acx, qcx, cx, *, verbose=False):
-    """TinyMPC.jl:245-259.  Per-knot second-order cones, inputs first; parity unpinned."""
+    """TinyMPC.jl:245-259.  Per-knot second-order cones, inputs first; parity unpinned.  cu (n,) and cx (n,)
+    shared by the batch, or — batch > 1 — cu (n, batch) and cx (n, batch): every instance its own coefficients over the one
+    layout (+inf: a cone that instance does not have)."""
     ia = [np.asarray(a, dtype=np.int32) for a in (Acu, qcu, Acx, qcx)]
-    da = [np.asarray(a, dtype=np.float64) for a in (cu, cx)]
+    # a 2-D side travels with the batch on its width, [batch][cone]; the library refuses mixed widths by name
+    da = [np.ascontiguousarray(a.T).reshape(-1) if a.ndim == 2 else a for a in (np.asarray(a, dtype=np.float64) for a in (cu, cx))]
     status = load_library().set_cone_constraints(
         ia[0].ctypes.data_as(c_ip), len(ia[0]), ia[1].ctypes.data_as(c_ip), len(ia[1]), _dp(da[0]),
         len(da[0]), ia[2].ctypes.data_as(c_ip), len(ia[2]), ia[3].ctypes.data_as(c_ip), len(ia[3]),
@@ -1285,6 +1310,26 @@ class BatchSolver:
     def lin_mode(self):
         """0 no rows or rows shared by the batch, 1 per instance"""
         return int(self.lib.tinympc_lin_mode(self.h))
+
+    def set_instance_cones(self, Acu, qcu, cu, Acx, qcx, cx):
+        """cone coefficients PER INSTANCE over one layout: Acu, qcu (ncu,) with cu (ncu, B), Acx, qcx (ncx,) with cx (ncx, B); an
+        empty side is None or no cone; +inf is a cone that instance does not have.  The solver then runs on the `ic` form of
+        the stream or the generic kernel; set_cone_constraints returns it to shared cones.  Not with adaptive rho; mpc_rollout
+        only as a chain (a plant of its own, or TINYMPC_HIP_STREAM_MPC)."""
+        au, qu, cuv, n_u = _instance_cones(Acu, qcu, cu, self.batch)
+        ax, qx, cxv, n_x = _instance_cones(Acx, qcx, cx, self.batch)
+        self._chk(self.lib.tinympc_set_instance_cones(
+            self.h, au.ctypes.data_as(c_ip) if n_u else None, qu.ctypes.data_as(c_ip) if n_u else None, _dp(cuv) if n_u else None, n_u,
+            ax.ctypes.data_as(c_ip) if n_x else None, qx.ctypes.data_as(c_ip) if n_x else None, _dp(cxv) if n_x else None, n_x),
+            "set_instance_cones")
+
+    def enable_cones(self, en_state_soc, en_input_soc):
+        """the two cone switches of update_settings (TinyMPC.jl:100-101) on their own: a side keeps its cones while it is off"""
+        self._chk(self.lib.tinympc_enable_cones(self.h, int(bool(en_state_soc)), int(bool(en_input_soc))), "enable_cones")
+
+    def cone_mode(self):
+        """0 no cones or cones shared by the batch, 1 a coefficient per instance"""
+        return int(self.lib.tinympc_cone_mode(self.h))
 
     def enable_linear(self, en_state_linear, en_input_linear):
         """the two linear-row switches of update_settings (TinyMPC.jl:98-99) on their own: a side keeps its rows while it is off"""
@@ -1840,6 +1885,15 @@ class ShardedBatchSolver:
         Au, bu, mu = _instance_linear(Alin_u, blin_u, self.nu, self.batch)
         self._chk(self.lib.tinympc_sharded_set_instance_linear(self.h, _dp(Ax) if mx else None, mx, _dp(bx) if mx else None,
                                                                _dp(Au) if mu else None, mu, _dp(bu) if mu else None), "set_instance_linear")
+
+    def set_instance_cones(self, Acu, qcu, cu, Acx, qcx, cx):
+        """per-instance cone coefficients over the whole batch (shapes as BatchSolver.set_instance_cones), scattered to the shards"""
+        au, qu, cuv, n_u = _instance_cones(Acu, qcu, cu, self.batch)
+        ax, qx, cxv, n_x = _instance_cones(Acx, qcx, cx, self.batch)
+        self._chk(self.lib.tinympc_sharded_set_instance_cones(
+            self.h, au.ctypes.data_as(c_ip) if n_u else None, qu.ctypes.data_as(c_ip) if n_u else None, _dp(cuv) if n_u else None, n_u,
+            ax.ctypes.data_as(c_ip) if n_x else None, qx.ctypes.data_as(c_ip) if n_x else None, _dp(cxv) if n_x else None, n_x),
+            "set_instance_cones")
 
     def set_warm_start(self, on):
         self._chk(self.lib.tinympc_sharded_set_warm_start(self.h, 1 if on else 0), "set_warm_start")
